@@ -19,6 +19,14 @@ both figures are in the line under "row_exchange".  Round 6: `value` at N > 1 is
 iteration; "cross_rank_persistent" in the line) where the node offers peer access between the ranks' devices, and on the RCCL leg
 --row-exchange names otherwise (fixed by configuration, never best-of); config.multi_gpu_path says which.
 
+A plain run sets up, warms up, times the K steps and prints the headline line (at N > 1 together with the leg `value` is quoted
+on).  --full adds every secondary figure after that: the kernel microbenchmarks and the roofline object, Hess-vec by p, the CPU
+baseline, the solves to KKT 1e-8, the dense / n = 10^6 / affine / cross-rank figures and, at N > 1, the halo leg when `value`
+is not quoted on it and the row-sharded dense problem (the --no-* options switch single ones of them off).
+
+--dump-outputs DIR writes what the last timed step computed -- the factor Y (n x p, float64; at N > 1 all rows of the all-gather leg, gathered) and
+the statistics of its trustregions() call -- as DIR/<name>.npy; the inputs are the same from run to run (fixture, seed 0).
+
 One JSON line is printed by rank 0.
 """
 import argparse
@@ -371,6 +379,26 @@ def xr_unavailable(N, local_rank):
         return "%s: %s" % (type(e).__name__, e)
 
 
+# what a trustregions() call returns besides the factor (RtrStats without its wall time, which differs from run to run)
+DUMP_STATS = ("cost", "gradnorm", "Delta", "iters", "hessvecs", "accepted", "rejected", "cost_evals", "last_stop_inner")
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, Y, st):
+    """--dump-outputs: the factor after the last timed step and the statistics of that call, each as out_dir/<name>.npy in
+    float64.  A factor above the 64-MB bound of the option (--gpus 8 --p 64: 82 MB) is written as a fixed sample of its rows,
+    drawn with seed 0, with the sampled row numbers beside it (Y_rows.npy)."""
+    os.makedirs(out_dir, exist_ok=True)
+    Y = np.asarray(Y, dtype=np.float64)
+    if Y.nbytes > DUMP_BYTES // 2:
+        rows = np.sort(np.random.default_rng(0).choice(Y.shape[0], DUMP_BYTES // 2 // (8 * Y.shape[1]), replace=False))
+        np.save(os.path.join(out_dir, "Y_rows.npy"), rows.astype(np.float64))
+        Y = Y[rows]
+    np.save(os.path.join(out_dir, "Y.npy"), np.ascontiguousarray(Y))
+    for k in DUMP_STATS:
+        np.save(os.path.join(out_dir, k + ".npy"), np.array([getattr(st, k)], dtype=np.float64))
+
+
 def main():
     # stdout carries exactly ONE line (the JSON result of rank 0).  Native libraries print there too (RCCL's version
     # banner with NCCL_DEBUG=VERSION arrives from C stdio at exit, i.e. after the JSON line), so file descriptor 1 is
@@ -398,7 +426,14 @@ def main():
     ap.add_argument("--force-comm", action="store_true",
                     help="diagnostic: run the N = 1 workload through the RCCL code path of the multi-GPU run "
                          "(size-1 communicator: all-gather + all-reduces per trip, chunked tCG)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, every secondary one as well (kernel microbenchmarks and roofline, Hess-vec by p, "
+                         "CPU baseline, solves to KKT, dense / large sparse / affine / cross-rank figures; N > 1: halo leg, sharded dense)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the factor and the statistics of the last timed step as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -505,98 +540,14 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
-    # Kernel-level numbers, timed with HIP events on the library's stream.
-    #  * the S*U (ehess) kernel alone: algorithmic bytes of SURVEY.md 8(d) / average launch time;
-    #  * one whole tCG trip (S*U + every vector update + the three reductions).  On one GPU at this size the
-    #    trips run inside the persistent kernel k_tcg_persist_obl (working set resident in registers/LDS), which
-    #    is where >90% of the step's device time goes: it is the dominant kernel of the roofline object
-    #    (profiles/r2_bench_kernel_stats.csv: k_tcg_persist_obl<16,5,3,false> = the 512 timed trips of bench_tcg_trip).
-    h.set_point(Y0)
-    ms, abytes, aflops = h.bench_hessvec(200)
-    trip_ms = h.bench_tcg_trip(512)
+    if args.dump_outputs:
+        Yl = h.get_point_all() if N > 1 else h.get_point()       # (an all-gather at N > 1: every rank takes part)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, Yl, st)
+
     persistent = (N == 1 and h.tcg_path() == 1)
     # round 5: the persistent kernel's default trip has ONE grid reduction (msdp_pipe.h); the two-reduction trip timed beside it
     one_reduction = persistent and h.persist_form() == 2
-    trip2_ms = None
-    if one_reduction:
-        h.set_option("persist_pipe", 0)
-        trip2_ms = h.bench_tcg_trip(512)
-        h.set_option("persist_pipe", 1)
-    hess_achieved = abytes / (ms * 1e-3) / 1e9
-    # the algorithmic traffic of the path is that of the S*U (ehess) product, `abytes` per Hess-vec;
-    # one tCG trip = one Hess-vec.  For the persistent kernel (one launch = all trips of a solve) bytes and time are
-    # quoted per trip: achieved = abytes / trip time.  The streaming three-kernel formulation of a trip would move
-    # abytes + ~10 n*p*8 (tCG.m:166-287); that figure is kept as a labelled extra, it is NOT the roofline number.
-    trip_achieved = abytes / (trip_ms * 1e-3) / 1e9
-    streaming_trip_bytes = abytes + 10.0 * n * p * 8
-
-    def pmc(*names):
-        """A committed rocprofv3 --pmc summary (profiles/), with a mark when the kernel's sources changed after it was taken: a summary
-        carries the hash of the sources it was measured on (tools/pmc_to_json.py --sources); one without is of unknown generation."""
-        for name in names:
-            f = os.path.join(ROOT, "profiles", name)
-            if N == 1 and p == 32 and os.path.exists(f):
-                rec = json.load(open(f))
-                rec["_source"] = "profiles/" + name
-                rec["_stale"] = not rec.get("sources_sha16") or rec["sources_sha16"] != sources_sha16(rec.get("sources", []))
-                return rec
-        return None
-    # HBM traffic comes from rocprofv3 --pmc passes (their own runs: counters cannot be collected inside a timed run);
-    # the line carries the committed summary's value together with the file it was read from
-    pm_h = pmc("r6_pmc_hess_g81_p32.json", "r4_pmc_hess_g81_p32.json", "r3_pmc_hess_g81_p32.json")
-    pm_t = pmc("r6_pmc_pipe_g81_p32.json", "r5_pmc_pipe_g81_p32.json") if one_reduction else pmc("r6_pmc_persist_g81_p32.json", "r5_pmc_persist_g81_p32.json")
-    pm_f = pmc("r6_pmc_fused_g81_p32.json")
-    if persistent:
-        # The DOMINANT kernel of the timed step: on the fused path ONE launch of k_tcg_pipe_obl<.., FUSE> runs the whole trustregions() call
-        # (every trip, retraction, cost evaluation, decision) -- roofline.achieved = algorithmic bytes of that launch (its Hess-vecs x
-        # SURVEY.md 8(d)'s bytes per Hess-vec; the 40 cost / gradient evaluations it also makes are not counted) / its duration by HIP
-        # events on the library's stream over the timed steps.  `trip_only` = the trip microbenchmark (bench_tcg_trip: the per-iteration
-        # instance, 512 trips, exits disabled) that earlier rounds quoted as `frac`; `frac_of_value` = the same bytes x `value` / peak,
-        # i.e. with the host side of the step inside.
-        hv_step = hv / args.steps
-        fused_ms = sum(dev_ms) / len(dev_ms) if dev_ms and min(dev_ms) > 0 else None
-        trip_only = {"kernel": "k_tcg_pipe_obl" if one_reduction else "k_tcg_persist_obl", "kernel_us": trip_ms * 1e3, "per": "tCG trip (one Hess-vec)",
-                     "achieved": trip_achieved, "frac": trip_achieved / HBM_PEAK_GBS,
-                     "traffic": (pm_t or {}).get("hbm_bytes_per_trip"), "traffic_source": (pm_t or {}).get("_source"),
-                     "traffic_stale": (pm_t or {}).get("_stale"),
-                     "two_reduction_trip_us": None if trip2_ms is None else trip2_ms * 1e3}
-        if fused_ms is not None:
-            achieved = hv_step * abytes / (fused_ms * 1e-3) / 1e9
-            roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                        "traffic": (pm_f or {}).get("hbm_bytes_per_launch"), "traffic_source": (pm_f or {}).get("_source"),
-                        "traffic_stale": (pm_f or {}).get("_stale"),
-                        "traffic_note": "replayed from the committed rocprofv3 --pmc summary of the same kernel and workload, not measured in this run",
-                        "kernel": ("k_tcg_pipe_obl<.., FUSE>" if one_reduction else "k_tcg_persist_obl<.., FUSE>") + " (one launch = one trustregions() call)",
-                        "kernel_us": fused_ms * 1e3, "per": "launch (%d Hess-vecs)" % round(hv_step),
-                        "algorithmic_bytes_per_launch": hv_step * abytes, "algorithmic_bytes_per_hessvec": abytes,
-                        "frac_is": "algorithmic bytes of the fused launch / its HIP-event duration / peak",
-                        "frac_of_value": hv / dt * abytes / 1e9 / HBM_PEAK_GBS,
-                        "us_per_hessvec_in_the_launch": fused_ms * 1e3 / hv_step,
-                        "trip_only": trip_only}
-        else:
-            roofline = {"bound": "hbm", "achieved": trip_achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": trip_achieved / HBM_PEAK_GBS,
-                        "traffic": trip_only["traffic"], "traffic_source": trip_only["traffic_source"], "traffic_stale": trip_only["traffic_stale"],
-                        "kernel": trip_only["kernel"], "kernel_us": trip_ms * 1e3, "per": "tCG trip (one Hess-vec)",
-                        "algorithmic_bytes_per_launch": abytes, "frac_is": "algorithmic bytes of one trip / trip time of the trip microbenchmark / peak",
-                        "frac_of_value": hv / dt * abytes / 1e9 / HBM_PEAK_GBS}
-        roofline.update({
-                    "streaming_formulation_bytes_per_trip": streaming_trip_bytes,
-                    "note": "the working set is register / LDS resident and a trip is LATENCY, not HBM (n*p*8 = 5 MB per vector: the fraction of the "
-                            "HBM roofline is low by construction): one grid reduction per trip (msdp_pipe.h) -- profiles/r6_fused_timeline_p32.md: "
-                            "products + partial sums 1.4 us (fp64 VALU at two waves per SIMD), the reduction chain 3.3 us (wave butterfly, store "
-                            "drain + barrier, post + back-off, poll, sums), alpha .. new direction 0.5 us; a TR iteration costs 13 us outside "
-                            "its trips (round 5: 14; retraction, slot-line barrier, gather of the proposal rows through the fine-grained exchange "
-                            "buffer, the iteration's reduction, decision with an LDS role swap)"})
-    else:
-        roofline = {"bound": "hbm", "achieved": hess_achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": hess_achieved / HBM_PEAK_GBS, "traffic": (pm_h or {}).get("hbm_bytes_per_launch"),
-                    "traffic_source": (pm_h or {}).get("_source"), "traffic_stale": (pm_h or {}).get("_stale"),
-                    "kernel": "k_hess_ell_obl", "kernel_us": ms * 1e3, "algorithmic_bytes_per_launch": abytes}
-    hess_kernel = {"kernel": "k_hess_ell_obl", "kernel_us": ms * 1e3, "algorithmic_bytes_per_launch": abytes,
-                   "achieved_GBps": hess_achieved, "frac_of_hbm_peak": hess_achieved / HBM_PEAK_GBS,
-                   "traffic": (pm_h or {}).get("hbm_bytes_per_launch"), "traffic_source": (pm_h or {}).get("_source"),
-                   "traffic_stale": (pm_h or {}).get("_stale")}
-
     out = {
         "metric": "tCG Hess-vec prods/sec (n,p), G81 MaxCut",
         "value": hv * N / dt,
@@ -613,14 +564,105 @@ def main():
                    "parallelism": "rows%d" % N,
                    "tcg_path": ("persistent single-launch kernel, one grid reduction per trip" if one_reduction else "persistent single-launch kernel") if persistent else
                                "chunked hipGraph, two launches per trip (linear-product trip, msdp_trip1.hip)"},
-        "roofline": roofline,
-        "hessvec_kernel": hess_kernel,
-        "tcg_trip_us": trip_ms * 1e3,
-        "hessvec_per_s_kernel_only": 1e3 / ms,           # stand-alone S*U kernel back to back (both figures)
-        "hessvec_per_s_whole_tcg": 1e3 / trip_ms,        # one Hess-vec + all vector work and reductions of a tCG trip
         "hessvec_per_s_in_rtr": hv / rtr_s if rtr_s > 0 else None,
     }
-    if N == 1 and rank == 0 and not args.force_comm:
+    if args.full:
+        # Kernel-level numbers, timed with HIP events on the library's stream.
+        #  * the S*U (ehess) kernel alone: algorithmic bytes of SURVEY.md 8(d) / average launch time;
+        #  * one whole tCG trip (S*U + every vector update + the three reductions).  On one GPU at this size the
+        #    trips run inside the persistent kernel k_tcg_persist_obl (working set resident in registers/LDS), which
+        #    is where >90% of the step's device time goes: it is the dominant kernel of the roofline object
+        #    (profiles/r2_bench_kernel_stats.csv: k_tcg_persist_obl<16,5,3,false> = the 512 timed trips of bench_tcg_trip).
+        h.set_point(Y0)
+        ms, abytes, aflops = h.bench_hessvec(200)
+        trip_ms = h.bench_tcg_trip(512)
+        trip2_ms = None
+        if one_reduction:
+            h.set_option("persist_pipe", 0)
+            trip2_ms = h.bench_tcg_trip(512)
+            h.set_option("persist_pipe", 1)
+        hess_achieved = abytes / (ms * 1e-3) / 1e9
+        # the algorithmic traffic of the path is that of the S*U (ehess) product, `abytes` per Hess-vec;
+        # one tCG trip = one Hess-vec.  For the persistent kernel (one launch = all trips of a solve) bytes and time are
+        # quoted per trip: achieved = abytes / trip time.  The streaming three-kernel formulation of a trip would move
+        # abytes + ~10 n*p*8 (tCG.m:166-287); that figure is kept as a labelled extra, it is NOT the roofline number.
+        trip_achieved = abytes / (trip_ms * 1e-3) / 1e9
+        streaming_trip_bytes = abytes + 10.0 * n * p * 8
+
+        def pmc(*names):
+            """A committed rocprofv3 --pmc summary (profiles/), with a mark when the kernel's sources changed after it was taken: a summary
+            carries the hash of the sources it was measured on (tools/pmc_to_json.py --sources); one without is of unknown generation."""
+            for name in names:
+                f = os.path.join(ROOT, "profiles", name)
+                if N == 1 and p == 32 and os.path.exists(f):
+                    rec = json.load(open(f))
+                    rec["_source"] = "profiles/" + name
+                    rec["_stale"] = not rec.get("sources_sha16") or rec["sources_sha16"] != sources_sha16(rec.get("sources", []))
+                    return rec
+            return None
+        # HBM traffic comes from rocprofv3 --pmc passes (their own runs: counters cannot be collected inside a timed run);
+        # the line carries the committed summary's value together with the file it was read from
+        pm_h = pmc("r6_pmc_hess_g81_p32.json", "r4_pmc_hess_g81_p32.json", "r3_pmc_hess_g81_p32.json")
+        pm_t = pmc("r6_pmc_pipe_g81_p32.json", "r5_pmc_pipe_g81_p32.json") if one_reduction else pmc("r6_pmc_persist_g81_p32.json", "r5_pmc_persist_g81_p32.json")
+        pm_f = pmc("r6_pmc_fused_g81_p32.json")
+        if persistent:
+            # The DOMINANT kernel of the timed step: on the fused path ONE launch of k_tcg_pipe_obl<.., FUSE> runs the whole trustregions() call
+            # (every trip, retraction, cost evaluation, decision) -- roofline.achieved = algorithmic bytes of that launch (its Hess-vecs x
+            # SURVEY.md 8(d)'s bytes per Hess-vec; the 40 cost / gradient evaluations it also makes are not counted) / its duration by HIP
+            # events on the library's stream over the timed steps.  `trip_only` = the trip microbenchmark (bench_tcg_trip: the per-iteration
+            # instance, 512 trips, exits disabled) that earlier rounds quoted as `frac`; `frac_of_value` = the same bytes x `value` / peak,
+            # i.e. with the host side of the step inside.
+            hv_step = hv / args.steps
+            fused_ms = sum(dev_ms) / len(dev_ms) if dev_ms and min(dev_ms) > 0 else None
+            trip_only = {"kernel": "k_tcg_pipe_obl" if one_reduction else "k_tcg_persist_obl", "kernel_us": trip_ms * 1e3, "per": "tCG trip (one Hess-vec)",
+                         "achieved": trip_achieved, "frac": trip_achieved / HBM_PEAK_GBS,
+                         "traffic": (pm_t or {}).get("hbm_bytes_per_trip"), "traffic_source": (pm_t or {}).get("_source"),
+                         "traffic_stale": (pm_t or {}).get("_stale"),
+                         "two_reduction_trip_us": None if trip2_ms is None else trip2_ms * 1e3}
+            if fused_ms is not None:
+                achieved = hv_step * abytes / (fused_ms * 1e-3) / 1e9
+                roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                            "traffic": (pm_f or {}).get("hbm_bytes_per_launch"), "traffic_source": (pm_f or {}).get("_source"),
+                            "traffic_stale": (pm_f or {}).get("_stale"),
+                            "traffic_note": "replayed from the committed rocprofv3 --pmc summary of the same kernel and workload, not measured in this run",
+                            "kernel": ("k_tcg_pipe_obl<.., FUSE>" if one_reduction else "k_tcg_persist_obl<.., FUSE>") + " (one launch = one trustregions() call)",
+                            "kernel_us": fused_ms * 1e3, "per": "launch (%d Hess-vecs)" % round(hv_step),
+                            "algorithmic_bytes_per_launch": hv_step * abytes, "algorithmic_bytes_per_hessvec": abytes,
+                            "frac_is": "algorithmic bytes of the fused launch / its HIP-event duration / peak",
+                            "frac_of_value": hv / dt * abytes / 1e9 / HBM_PEAK_GBS,
+                            "us_per_hessvec_in_the_launch": fused_ms * 1e3 / hv_step,
+                            "trip_only": trip_only}
+            else:
+                roofline = {"bound": "hbm", "achieved": trip_achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": trip_achieved / HBM_PEAK_GBS,
+                            "traffic": trip_only["traffic"], "traffic_source": trip_only["traffic_source"], "traffic_stale": trip_only["traffic_stale"],
+                            "kernel": trip_only["kernel"], "kernel_us": trip_ms * 1e3, "per": "tCG trip (one Hess-vec)",
+                            "algorithmic_bytes_per_launch": abytes, "frac_is": "algorithmic bytes of one trip / trip time of the trip microbenchmark / peak",
+                            "frac_of_value": hv / dt * abytes / 1e9 / HBM_PEAK_GBS}
+            roofline.update({
+                        "streaming_formulation_bytes_per_trip": streaming_trip_bytes,
+                        "note": "the working set is register / LDS resident and a trip is LATENCY, not HBM (n*p*8 = 5 MB per vector: the fraction of the "
+                                "HBM roofline is low by construction): one grid reduction per trip (msdp_pipe.h) -- profiles/r6_fused_timeline_p32.md: "
+                                "products + partial sums 1.4 us (fp64 VALU at two waves per SIMD), the reduction chain 3.3 us (wave butterfly, store "
+                                "drain + barrier, post + back-off, poll, sums), alpha .. new direction 0.5 us; a TR iteration costs 13 us outside "
+                                "its trips (round 5: 14; retraction, slot-line barrier, gather of the proposal rows through the fine-grained exchange "
+                                "buffer, the iteration's reduction, decision with an LDS role swap)"})
+        else:
+            roofline = {"bound": "hbm", "achieved": hess_achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": hess_achieved / HBM_PEAK_GBS, "traffic": (pm_h or {}).get("hbm_bytes_per_launch"),
+                        "traffic_source": (pm_h or {}).get("_source"), "traffic_stale": (pm_h or {}).get("_stale"),
+                        "kernel": "k_hess_ell_obl", "kernel_us": ms * 1e3, "algorithmic_bytes_per_launch": abytes}
+        hess_kernel = {"kernel": "k_hess_ell_obl", "kernel_us": ms * 1e3, "algorithmic_bytes_per_launch": abytes,
+                       "achieved_GBps": hess_achieved, "frac_of_hbm_peak": hess_achieved / HBM_PEAK_GBS,
+                       "traffic": (pm_h or {}).get("hbm_bytes_per_launch"), "traffic_source": (pm_h or {}).get("_source"),
+                       "traffic_stale": (pm_h or {}).get("_stale")}
+        out.update({
+            "roofline": roofline,
+            "hessvec_kernel": hess_kernel,
+            "tcg_trip_us": trip_ms * 1e3,
+            "hessvec_per_s_kernel_only": 1e3 / ms,           # stand-alone S*U kernel back to back (SURVEY.md 8d: both figures)
+            "hessvec_per_s_whole_tcg": 1e3 / trip_ms,        # one Hess-vec + all vector work and reductions of a tCG trip
+        })
+    if args.full and N == 1 and rank == 0 and not args.force_comm:
         # SURVEY.md 8(d): the Hess-vec microbenchmark at p in {8, 16, 32} -- stand-alone S*U kernel and whole tCG trip
         sweep = {}
         for pp in (8, 16, 32):
@@ -636,9 +678,9 @@ def main():
             except Exception as e:  # noqa: BLE001
                 sweep["p%d" % pp] = {"error": "%s: %s" % (type(e).__name__, e)}
         out["hessvec_by_p"] = sweep
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(C, Y0) if N == 1 else None
-    if not args.no_kkt and N == 1 and rank == 0 and data_kind.startswith("Gset"):
+    if args.full and not args.no_kkt and N == 1 and rank == 0 and data_kind.startswith("Gset"):
         # second half of the metric: wall-clock to KKT 1e-8 on G81 with the reference's own example
         # setting options.p0 = 40 (example/example_maxcut.m:32), everything else default
         from manisdp_matlab_amd import solvers
@@ -682,7 +724,7 @@ def main():
                 out["g1_config0"] = {"error": "%s: %s" % (type(e).__name__, e)}
     h.close()
     _lib.release_cache()         # the parked escape workspace: the dense shapes below allocate up to 160 GB of their own
-    if not args.no_dense and N == 1 and rank == 0 and not args.force_comm:
+    if args.full and not args.no_dense and N == 1 and rank == 0 and not args.force_comm:
         # The dense tall-skinny contraction S*U is the one place the path uses the matrix cores (north_star): report its
         # fp64 MFMA and HBM fractions on the dense-C shapes of BASELINE configs 4 / 5 (synthetic symmetric C, seed 0).
         MFMA_F64_TFLOPS = 78.6                      # MI355X_MICROARCH.md: dense fp64 matrix peak
@@ -740,7 +782,7 @@ def main():
         except Exception as e:  # noqa: BLE001 -- secondary figure
             dense.append({"n": 100000, "p": 64, "error": "%s: %s" % (type(e).__name__, e)})
         out["dense_mfma"] = dense
-    if not args.no_large_sparse and N == 1 and rank == 0 and not args.force_comm:
+    if args.full and not args.no_large_sparse and N == 1 and rank == 0 and not args.force_comm:
         # The chunked tCG path -- what every sparse problem beyond the persistent kernel's reach takes -- at n = 10^6, p = 32
         # (toroidal grid MaxCut, the G81 family scaled up): the two launches of msdp_trip1.hip move 14 vectors per trip.
         try:
@@ -784,9 +826,9 @@ def main():
                 rec["traffic"] = json.load(open(os.path.join(ROOT, rec["traffic_source"]))).get("hbm_bytes_per_trip")
         except Exception as e:  # noqa: BLE001 -- secondary figure
             out["large_sparse_trip"] = {"error": "%s: %s" % (type(e).__name__, e)}
-    if not args.no_affine and N == 1 and rank == 0 and not args.force_comm:
+    if args.full and not args.no_affine and N == 1 and rank == 0 and not args.force_comm:
         out["affine_hessvec"] = affine_shapes(_lib, problems, not args.no_cpu_baseline)
-    if not args.no_xrank and N == 1 and rank == 0 and not args.force_comm:
+    if args.full and not args.no_xrank and N == 1 and rank == 0 and not args.force_comm:
         try:
             out["cross_rank_trip"] = cross_rank_trip(_lib, problems)
         except Exception as e:  # noqa: BLE001 -- secondary figure
@@ -832,13 +874,15 @@ def main():
             # travel before S*U -- 400 of 20000*N rows on this family -- instead of the all-gather of the whole direction).
             # Results are bit-identical (tests/test_gpu_local_ranks.py); the all-gather figure above was taken first and
             # stays in the line, so a failure of this leg costs nothing.
-            # Which of the two is `value` is fixed by --row-exchange, never chosen after the fact.
-            hl = halo_leg(_lib, join, sync, allmax, N, rank, C, Y0, p, opts, args.steps, args.warmup)
-            out["row_exchange"] = {"all_gather": {"value": out["value"], "ms_per_step": out["ms_per_step"]}, "halo": hl}
+            # Which of the two is `value` is fixed by --row-exchange, never chosen after the fact.  A plain run times the halo
+            # leg only when `value` is quoted on it.
             out["config"]["row_exchange"] = "all-gather"
-            if args.row_exchange == "halo" and "error" not in hl and hl["hessvecs"] == hv:
-                out["value"], out["ms_per_step"] = hl["value"], hl["ms_per_step"]
-                out["config"]["row_exchange"] = "halo (option halo_exchange): grouped ncclSend/ncclRecv of the referenced rows"
+            if args.full or args.row_exchange == "halo":
+                hl = halo_leg(_lib, join, sync, allmax, N, rank, C, Y0, p, opts, args.steps, args.warmup)
+                out["row_exchange"] = {"all_gather": {"value": out["value"], "ms_per_step": out["ms_per_step"]}, "halo": hl}
+                if args.row_exchange == "halo" and "error" not in hl and hl["hessvecs"] == hv:
+                    out["value"], out["ms_per_step"] = hl["value"], hl["ms_per_step"]
+                    out["config"]["row_exchange"] = "halo (option halo_exchange): grouped ncclSend/ncclRecv of the referenced rows"
             # Round 6: the N-GPU form of the persistent kernels -- one PROCESS group over HIP IPC / peer access, the cross-rank tCG
             # and TR tail with two-level grid reductions (each member over its own grid, eight sums per member over xGMI), boundary
             # rows pushed into the neighbours' buffers: no collective per trip, none per iteration.  `value` is quoted on THIS path
@@ -861,7 +905,7 @@ def main():
                     out["config"]["multi_gpu_path"] = ("cross-rank persistent tCG + TR tail over HIP IPC / xGMI, two-level grid reductions "
                                                        "(msdp_comm_init_ipc); RCCL legs: row_exchange")
                     out["config"]["tcg_path"] = "persistent kernels spanning the ranks: no collective per trip or TR iteration"
-        if not args.no_dense:
+        if args.full and not args.no_dense:
             try:
                 out["k5_dense_sharded"] = k5_dense_sharded(_lib, join, sync, allmax, N, rank)
             except Exception as e:  # noqa: BLE001 -- reported, never fatal for the headline line

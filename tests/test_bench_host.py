@@ -118,3 +118,27 @@ def test_xr_leg_reports_a_failure_on_every_rank_without_hanging():
         out, logs = _run(2, leg="xr", **kw)
         for o in out:
             assert "error" in o and "value" not in o
+
+
+def test_dump_outputs_writes_float64_arrays_within_the_bound(tmp_path):
+    """--dump-outputs: the factor and the statistics of the last timed step as <name>.npy in float64; a factor above the bound is
+    written as a fixed sample of its rows (seed 0), the same from run to run, with the row numbers beside it."""
+    class St:
+        cost, gradnorm, Delta, iters, hessvecs, accepted, rejected, cost_evals, last_stop_inner = -1.5, 2e-9, 0.25, 40, 997, 32, 8, 41, 2
+
+    Y = np.arange(20.0 * 4).reshape(20, 4)
+    bench.dump_outputs(str(tmp_path / "small"), Y, St)
+    assert np.array_equal(np.load(tmp_path / "small" / "Y.npy"), Y)
+    assert not (tmp_path / "small" / "Y_rows.npy").exists()
+    for k in bench.DUMP_STATS:
+        v = np.load(tmp_path / "small" / (k + ".npy"))
+        assert v.dtype == np.float64 and v.tolist() == [float(getattr(St, k))]
+
+    big = np.random.default_rng(1).standard_normal((160000, 64))          # --gpus 8 --p 64: 82 MB
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big, St)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64 << 20
+    rows = np.load(tmp_path / "a" / "Y_rows.npy").astype(np.int64)
+    Ya = np.load(tmp_path / "a" / "Y.npy")
+    assert Ya.dtype == np.float64 and np.array_equal(Ya, big[rows]) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(Ya, np.load(tmp_path / "b" / "Y.npy"))

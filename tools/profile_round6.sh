@@ -30,7 +30,7 @@ WHAT=" ${*:-all} "     # one or more of: bench dense affine sparse (default: all
 want() { [[ "$WHAT" == *" all "* || "$WHAT" == *" $1 "* ]]; }
 PERSIST_SRC=$C/msdp_persist.hip,$C/msdp_pipe.h,$C/msdp_psync.h,$C/msdp_device.h
 if want bench; then
-stats bench 400 python3 "$ROOT/bench.py" --steps 5 --warmup 2 --no-cpu-baseline --no-kkt --no-dense --no-affine --no-large-sparse --no-xrank
+stats bench 400 python3 "$ROOT/bench.py" --steps 5 --warmup 2 --full --no-cpu-baseline --no-kkt --no-dense --no-affine --no-large-sparse --no-xrank
 both fused 120 python3 "$ROOT/tools/pmc_fused_probe.py" 32 4
 both pipe 120 python3 "$ROOT/tools/pmc_probe.py" 32 1
 both persist 120 python3 "$ROOT/tools/pmc_probe.py" 32 0

@@ -52,6 +52,7 @@ typedef struct msdp_handle_s* msdp_handle;
 #define MSDP_KIND_GENERIC      4   /* src/primal/ManiSDP.m (Euclidean manifold) */
 #define MSDP_KIND_MULTIBLOCK   5   /* src/primal/ManiSDP_multiblock.m (product manifold) */
 #define MSDP_KIND_DUAL_UNITDIAG 6  /* src/dual/ManiDSDP_unitdiag.m (dual approach, diag(S) = 1) */
+#define MSDP_KIND_DUAL         7   /* src/dual/ManiDSDP.m (dual approach, Euclidean factor of S) */
 
 /* Options of one Riemannian trust-region solve: the fields ManiSDP sets
  * (ManiSDP_unitdiag.m:44-47) plus Manopt's defaults that are in force
@@ -178,6 +179,20 @@ int msdp_dual_set_penalty(msdp_handle h, double sigma, const double* w);
 int msdp_dual_outer_step(msdp_handle h, double* scal, double* Af, double* z);
 /* y of the last msdp_dual_outer_step (m values; data.y, :134) */
 int msdp_dual_get_y(msdp_handle h, double* y);
+/* Generic dual approach (src/dual/ManiDSDP.m:7-178): the arguments of msdp_create_dual_unitdiag, S = Y*Y' with Y on the
+ * Euclidean manifold (euclideanfactory(n, p), :60); the factor crosses the boundary as the n x p column-major array of
+ * MSDP_KIND_GENERIC.  Closures replaced: costgrad :162-171, hess :173-177, co / line_search :141-160.  The handle takes
+ * msdp_dual_set_penalty, msdp_dual_get_y, msdp_rtr and the single-operator / line-search calls as the unit-diagonal kind
+ * does; msdp_dual_outer_step performs :66-77 (x <- x + sigma*(iAB*(Af - w/sigma) + A'(iA'*(As - x/sigma)) - As), with
+ * scal[0] = b'y, scal[1] = <C, x + bA>, scal[2] = |As|^2 and Af = B'y - cf; z is not used and may be NULL) and leaves
+ * X = mat(x + bA) on the device for msdp_escape_eigs_dual / msdp_get_dual_slack.  A factor wider than 128 columns gives
+ * MSDP_EUNSUPPORTED. */
+int msdp_create_dual(int64_t n, int64_t m, const int64_t* at_jc, const int64_t* at_ir, const double* at_pr,
+                     const double* dAAt, const double* b, const double* c, int32_t nf, const int64_t* b_jc,
+                     const int64_t* b_ir, const double* b_pr, const double* cf, int32_t pcap, msdp_handle* out);
+/* *g_identity = 1 when the setup proved D\A*A' = I (rows of A with pairwise disjoint supports and dAAt equal to their
+ * squared norms bit for bit): the Hess-vec then skips the G*a terms of ManiDSDP.m:176.  Dual handles only. */
+int msdp_dual_info(msdp_handle h, int32_t* g_identity);
 
 int msdp_destroy(msdp_handle h);
 /* The library keeps ONE device allocation beyond the life of the handles: the Lanczos workspace of the escape (up to 24 GB for

@@ -15,7 +15,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libmanisdp_hip.so")
 
-KIND_ONLYUNITDIAG, KIND_UNITDIAG, KIND_UNITTRACE, KIND_GENERIC, KIND_MULTIBLOCK, KIND_DUAL_UNITDIAG = 1, 2, 3, 4, 5, 6
+KIND_ONLYUNITDIAG, KIND_UNITDIAG, KIND_UNITTRACE, KIND_GENERIC, KIND_MULTIBLOCK, KIND_DUAL_UNITDIAG, KIND_DUAL = 1, 2, 3, 4, 5, 6, 7
 
 
 class RtrOpts(C.Structure):
@@ -105,6 +105,9 @@ SIGNATURES = {
     "msdp_factor_append": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.c_double, C.c_int32]),
     "msdp_create_dual_unitdiag": (C.c_int, [C.c_int64, C.c_int64, _i64p, _i64p, _dp, _dp, _dp, _dp, C.c_int32, _i64p, _i64p, _dp,
                                             _dp, C.c_int32, C.POINTER(C.c_void_p)]),
+    "msdp_create_dual": (C.c_int, [C.c_int64, C.c_int64, _i64p, _i64p, _dp, _dp, _dp, _dp, C.c_int32, _i64p, _i64p, _dp,
+                                   _dp, C.c_int32, C.POINTER(C.c_void_p)]),
+    "msdp_dual_info": (C.c_int, [C.c_void_p, _P(C.c_int32)]),
     "msdp_dual_set_penalty": (C.c_int, [C.c_void_p, C.c_double, _dp]),
     "msdp_dual_outer_step": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
     "msdp_dual_get_y": (C.c_int, [C.c_void_p, _dp]),
@@ -289,6 +292,16 @@ class Handle:
     def dual_unitdiag(cls, A, b, c, dAAt, B=None, cf=None, pcap=32):
         """Dual approach, diag(S) = 1 (ManiDSDP_unitdiag.m).  ``A`` is the m x n^2 PSD part (rows = vec(A_k)), ``c`` its
         cost (n^2), ``B`` the m x nf free part with costs ``cf``, ``dAAt = diag(A A')``.  The factor of S is (n, p)."""
+        return cls._dual_create(KIND_DUAL_UNITDIAG, A, b, c, dAAt, B, cf, pcap)
+
+    @classmethod
+    def dual(cls, A, b, c, dAAt, B=None, cf=None, pcap=32):
+        """Generic dual approach (ManiDSDP.m): the data of :meth:`dual_unitdiag`, S = Y Y' with Y (n, p) on the
+        Euclidean manifold."""
+        return cls._dual_create(KIND_DUAL, A, b, c, dAAt, B, cf, pcap)
+
+    @classmethod
+    def _dual_create(cls, kind, A, b, c, dAAt, B, cf, pcap):
         import scipy.sparse as sp
         lib = load()
         out = C.c_void_p()
@@ -312,9 +325,10 @@ class Handle:
             args = (bjc.ctypes.data_as(_i64p), bir.ctypes.data_as(_i64p), _dptr(bpr), _dptr(cfv))
         else:
             args = (None, None, None, None)
-        _check(lib.msdp_create_dual_unitdiag(n, Atc.shape[1], jc.ctypes.data_as(_i64p), ir.ctypes.data_as(_i64p), _dptr(pr), _dptr(d),
-                                             _dptr(b), _dptr(c), nf, *args, pcap, C.byref(out)))
-        hd = cls(out.value, KIND_DUAL_UNITDIAG, n)
+        create = lib.msdp_create_dual if kind == KIND_DUAL else lib.msdp_create_dual_unitdiag
+        _check(create(n, Atc.shape[1], jc.ctypes.data_as(_i64p), ir.ctypes.data_as(_i64p), _dptr(pr), _dptr(d),
+                      _dptr(b), _dptr(c), nf, *args, pcap, C.byref(out)))
+        hd = cls(out.value, kind, n)
         hd.m = Atc.shape[1]
         hd.nf = nf
         return hd
@@ -324,12 +338,19 @@ class Handle:
         _check(self._lib.msdp_dual_set_penalty(self._h, float(sigma), _dptr(w)))
 
     def dual_outer_step(self):
-        """Outer step of ManiDSDP_unitdiag.m:70-81 on the device: returns (b'y, <C,eX>, |As|^2, Af, z)."""
+        """Outer step of ManiDSDP_unitdiag.m:70-81 (ManiDSDP.m:66-77) on the device: returns (b'y, <C,eX>, |As|^2, Af, z);
+        z is None for the generic kind."""
         scal = np.zeros(3)
         Af = np.zeros(max(self.nf, 1))
-        z = np.zeros(self.n)
-        _check(self._lib.msdp_dual_outer_step(self._h, _dptr(scal), _dptr(Af), _dptr(z)))
+        z = np.zeros(self.n) if self.kind == KIND_DUAL_UNITDIAG else None
+        _check(self._lib.msdp_dual_outer_step(self._h, _dptr(scal), _dptr(Af), _dptr(z) if z is not None else None))
         return float(scal[0]), float(scal[1]), float(scal[2]), Af[:self.nf], z
+
+    def dual_g_identity(self):
+        """Whether the setup proved D\\A*A' = I (the Hess-vec of the generic dual kind then skips the G terms)."""
+        g = C.c_int32(0)
+        _check(self._lib.msdp_dual_info(self._h, C.byref(g)))
+        return bool(g.value)
 
     def dual_get_y(self):
         y = np.zeros(self.m)
@@ -350,13 +371,13 @@ class Handle:
     # ---- layout helpers
     def _to_boundary(self, Y):
         Y = np.asarray(Y, dtype=np.float64)
-        if self.kind in (KIND_UNITTRACE, KIND_GENERIC):
+        if self.kind in (KIND_UNITTRACE, KIND_GENERIC, KIND_DUAL):
             return np.asfortranarray(Y)           # MATLAB n x p column-major
         return np.ascontiguousarray(Y)            # bytes of MATLAB p x n column-major
 
     def _empty(self):
         # zero-initialised: a row-sharded handle (comm_init / debug_shard) only writes its own rows
-        if self.kind in (KIND_UNITTRACE, KIND_GENERIC):
+        if self.kind in (KIND_UNITTRACE, KIND_GENERIC, KIND_DUAL):
             return np.zeros((self.n, self.p), dtype=np.float64, order="F")
         return np.zeros((self.n, self.p), dtype=np.float64, order="C")
 

@@ -933,7 +933,7 @@ __global__ __launch_bounds__(MSDP_BLOCK) void k_obl_grad_finish(Dev d, int slot,
 }
 
 // sphere gradient finish: Gr holds 2*eS*Y, z = <eS*Y, Y> partials in P_S2: G = 2 eS Y - 2 z Y.
-__global__ __launch_bounds__(MSDP_BLOCK) void k_sph_grad_finish(Dev d, int slot, double sigma) {
+__global__ __launch_bounds__(MSDP_BLOCK) void k_sph_grad_finish(Dev d, int slot, double sigma, const double* f_given) {
     __shared__ double sh[3 * MSDP_WAVES + 8];
     // Euclidean manifold (generic ManiSDP.m:153-156): G = 2*S*Y, no projection term
     const double z = (d.manifold == MANI_EUCLID) ? 0.0 : msdp_sum_partials_block(d.P, P_S2, d.G, sh);
@@ -955,7 +955,8 @@ __global__ __launch_bounds__(MSDP_BLOCK) void k_sph_grad_finish(Dev d, int slot,
         pgg += gq.x * gq.x + gq.y * gq.y;
     }
     double pf = 0.0;
-    if (blockIdx.x == 0 && threadIdx.x == 0) { if (d.row0 == 0) pf = cx + 0.5 * sigma * ss; d.ctl->z_sphere[slot] = z; }
+    // f_given: the generic dual kind's cost
+    if (blockIdx.x == 0 && threadIdx.x == 0) { if (d.row0 == 0) pf = f_given ? *f_given : cx + 0.5 * sigma * ss; d.ctl->z_sphere[slot] = z; }
     msdp_put_partials3(d.P, P_F, pf, P_GG, pgg, -1, 0.0, sh + 8);
 }
 
@@ -1131,7 +1132,7 @@ struct AffineState {
     double sigma = 1.0;
     double* Cdense = nullptr;      // n x nS
     double* d_y = nullptr;
-    struct DualState* dual = nullptr;   // MSDP_KIND_DUAL_UNITDIAG (below)
+    struct DualState* dual = nullptr;   // MSDP_KIND_DUAL_UNITDIAG / MSDP_KIND_DUAL (below)
     BlockedDev* blk = nullptr;          // multiblock kind with per-block storage (msdp_affine_setup_blocked); host copies of the block offsets:
     std::vector<int64_t> blk_r0, blk_off; std::vector<int> blk_n, blk_ns;
     // second stream of the Hess-vec: 2*eS*U does not depend on the A(.) / A'(.) chain and runs beside it (msdp_affine_hess)
@@ -1995,7 +1996,7 @@ int msdp_affine_costgrad(msdp_handle h, int slot) {
     if (d.manifold == MANI_OBLIQUE) {
         DISPATCH_LPR_A(k_obl_grad_finish, h, d.G, d, slot, sigma, (const double*)nullptr);
     } else {
-        hipLaunchKernelGGL(k_sph_grad_finish, dim3(d.G), dim3(MSDP_BLOCK), 0, h->stream, d, slot, sigma);
+        hipLaunchKernelGGL(k_sph_grad_finish, dim3(d.G), dim3(MSDP_BLOCK), 0, h->stream, d, slot, sigma, (const double*)nullptr);
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -2318,6 +2319,17 @@ int msdp_affine_al_dual(msdp_handle h, const double* y_host, double* z_host) {
 //   X = T + sigma*S - sigma*A'y,      sigma*As = bA - X.
 // New here: the dense Gram S = Y*Y' (k_gram_mfma, one product), the two p x p Gram matrices of the last Hessian
 // term, and the element-wise kernels.
+//
+// ------------------------------------------------------------------ dual, generic (MSDP_KIND_DUAL)
+// src/dual/ManiDSDP.m: S = Y*Y' on the Euclidean factor (n x p, :60), no diagonal constraint; G = D\A*A' (m x m).
+//   cost/grad :162-171  y, Af as above; X = bA + sigma*(iAB*Af + A'(iA'*As) - As); G = 2*X*Y
+//   hess      :173-177  a = iA'*vec(U*Y'); H = 2*X*U + 2*sigma*(U*(Y'Y) + Y*(U'Y)) + 4*sigma*mat(A'(D\B*B'a + G*a - 2a))*Y
+// cost/grad keeps As dense:  Q = (C - x/sigma) + A'y (one adjoint; C - x/sigma is rebuilt with the multipliers, in T),
+// As = Q - S, R = bA - sigma*As, v = sigma*D\(A*As + B*Af) (one row-gather SpMV of A on the dense As, B by rows), and
+// X = R + A'v (the second adjoint).  So X needs no G and holds for any A and dAAt; |As|^2 comes from the same pass.
+// The Hess-vec: launch_A, B'a when there are free variables, one m-vector fix-up, one adjoint -- plus, unless the setup
+// proved G = I (rows of A with pairwise disjoint supports and dAAt equal to their squared norms), G*a = D\A(A'a) by one
+// more adjoint and the SpMV.  The outer step :65-77 is the cost state at Y followed by x = X - bA (k_dgen_outer).
 struct DualState {
     int nf = 0;                     // free variables (K.f)
     const double* dinv = nullptr;   // 1 ./ dAAt                         (m)
@@ -2337,6 +2349,18 @@ struct DualState {
     double* pp_part = nullptr;      // DUAL_PP_BLOCKS x ld x ld partials
     double* scal = nullptr;         // [0] f, [1] b'y, [2] <C,eX>, [3] |As|^2
     bool T_valid = false;
+    // generic kind (MSDP_KIND_DUAL) only; T then holds C - x/sigma
+    bool generic = false;
+    bool g_identity = false;        // G = D\A*A' is exactly I (setup check)
+    const int64_t* arp = nullptr;   // A by rows: row pointers (m + 1), row-major positions i*nS + j, values
+    const int64_t* apos = nullptr;
+    const double* aval = nullptr;
+    const int* brp = nullptr;       // B by rows (m x nf CSR)
+    const int* bcol = nullptr;
+    const double* bval = nullptr;
+    double* R = nullptr;            // bA - sigma*As                     (n x nS)
+    double* v = nullptr;            // the m-vector of the current adjoint
+    double* tB = nullptr;           // B'a of the current Hess-vec        (nf)
 };
 static void msdp_dual_release(DualState* ds) { delete ds; }
 #define DUAL_PP_BLOCKS 64
@@ -2361,17 +2385,18 @@ __global__ void k_dual_scale(int64_t m, double* __restrict__ w, const double* __
     if (skip_flag && *skip_flag == skip_when) return;
     for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < m; k += (int64_t)gridDim.x * blockDim.x) w[k] *= dinv[k];
 }
-// Af_j = B(:,j)'y - cf_j - (wf ? wf_j / sigma : 0): one workgroup per free variable
+// Af_j = B(:,j)'(y .* ys) - cf_j - (wf ? wf_j / sigma : 0): one workgroup per free variable (ys, cf may be null: 1, 0)
 __global__ __launch_bounds__(256) void k_dual_free(const int* __restrict__ bjc, const int* __restrict__ bir, const double* __restrict__ bpr,
                                                    const double* __restrict__ y, const double* __restrict__ cf, const double* wf,
-                                                   double sigma, double* __restrict__ Af, const int* skip_flag, int skip_when) {
+                                                   double sigma, double* __restrict__ Af, const int* skip_flag, int skip_when,
+                                                   const double* __restrict__ ys = nullptr) {
     __shared__ double sh[MSDP_WAVES];
     if (skip_flag && *skip_flag == skip_when) return;
     const int j = blockIdx.x;
     double v = 0.0;
-    for (int t = bjc[j] + threadIdx.x; t < bjc[j + 1]; t += blockDim.x) v = fma(bpr[t], y[bir[t]], v);
+    for (int t = bjc[j] + threadIdx.x; t < bjc[j + 1]; t += blockDim.x) v = fma(bpr[t], ys ? y[bir[t]] * ys[bir[t]] : y[bir[t]], v);
     v = msdp_block_sum(v, sh);
-    if (threadIdx.x == 0) Af[j] = v - cf[j] - (wf ? wf[j] / sigma : 0.0);
+    if (threadIdx.x == 0) Af[j] = v - (cf ? cf[j] : 0.0) - (wf ? wf[j] / sigma : 0.0);
 }
 // X += sigma*S, and the partial sums of |bA - X|^2 (= sigma^2 |As|^2) -> P_AXB   (MSDP_MAX_GRID workgroups)
 __global__ __launch_bounds__(256) void k_dual_finish_X(int64_t tot, double* __restrict__ X, const double* __restrict__ S,
@@ -2403,11 +2428,73 @@ __global__ __launch_bounds__(MSDP_BLOCK) void k_dual_cost(Dev d, double sigma, c
         out[1] = by;
     }
 }
-// T = bA + x - sigma*C
+// T = cb*bA + cx*x + cc*C: bA + x - sigma*C (unit diagonal), C - x/sigma (generic)
 __global__ void k_dual_T(int64_t tot, double* __restrict__ T, const double* __restrict__ bA, const double* __restrict__ x,
-                         const double* __restrict__ C, double sigma) {
+                         const double* __restrict__ C, double cb, double cx, double cc) {
     for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < tot; e += (int64_t)gridDim.x * blockDim.x)
-        T[e] = bA[e] + x[e] - sigma * C[e];
+        T[e] = fma(cb, bA[e], fma(cx, x[e], cc * C[e]));
+}
+// generic: As = Q - S (Q = C - x/sigma + A'y in X), S <- As, R = bA - sigma*As; partial sums of (sigma*As)^2 -> P_AXB
+// (MSDP_MAX_GRID workgroups: k_dual_cost divides by sigma)
+__global__ __launch_bounds__(256) void k_dgen_as(int64_t tot, int n, int nS, const double* __restrict__ Q, double* __restrict__ S,
+                                                 const double* __restrict__ bA, double sigma, double* __restrict__ R, double* P,
+                                                 const int* skip_flag, int skip_when) {
+    __shared__ double sh[3 * MSDP_WAVES];
+    if (skip_flag && *skip_flag == skip_when) return;
+    double ps = 0.0;
+    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < tot; e += (int64_t)gridDim.x * blockDim.x) {
+        if ((int)(e % nS) >= n) continue;                  // pad columns stay as they are (zero)
+        const double as = Q[e] - S[e];
+        S[e] = as;
+        R[e] = fma(-sigma, as, bA[e]);
+        ps = fma(sigma * as, sigma * as, ps);
+    }
+    msdp_put_partial(P, P_AXB, ps, sh);
+}
+// generic, one wave per row k of A (no atomics):
+//   out_k = dinv_k * (ca * sum_t A_kt Dn[pos_t] + cb * sum_j B_kj f_j) + cw * w_k * (wd ? dinv_k : 1)
+// cost/grad: Dn = As, f = Af, ca = cb = sigma, cw = 0.  Hess-vec fix-up: f = B'a, cb = 1, w = A(U Y') with wd (a = w/dAAt),
+// cw = -1 when G = I; with G: Dn = A'a, ca = 1, w = a, cw = -2.  Dn / f may be null.
+__global__ __launch_bounds__(256) void k_dgen_rows(int64_t m, const int64_t* __restrict__ arp, const int64_t* __restrict__ apos,
+                                                   const double* __restrict__ aval, const double* __restrict__ Dn, double ca,
+                                                   const int* __restrict__ brp, const int* __restrict__ bcol, const double* __restrict__ bval,
+                                                   const double* __restrict__ f, double cb, const double* __restrict__ dinv,
+                                                   const double* __restrict__ w, double cw, int wd, double* __restrict__ out,
+                                                   const int* skip_flag, int skip_when) {
+    if (skip_flag && *skip_flag == skip_when) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t nw = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t k = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); k < m; k += nw) {
+        double sa = 0.0, sb = 0.0;
+        if (Dn) for (int64_t t = arp[k] + lane; t < arp[k + 1]; t += 64) sa = fma(aval[t], Dn[apos[t]], sa);
+        if (f) for (int t = brp[k] + lane; t < brp[k + 1]; t += 64) sb = fma(bval[t], f[bcol[t]], sb);
+        sa = msdp_wave_sum(sa);
+        sb = msdp_wave_sum(sb);
+        if (lane == 0) {
+            const double dk = dinv[k];
+            double o = dk * fma(ca, sa, cb * sb);
+            if (w) o = fma(cw * (wd ? dk : 1.0), w[k], o);
+            out[k] = o;
+        }
+    }
+}
+// generic outer step :73-77 after the cost state at Y: X (Xd) = bA + sigma*(...) of :169 with the pre-update x and w,
+// S holds As - x/sigma.  x <- X - bA; partial sums of <C, X> -> P_S2 and |As|^2 (As without x/sigma) -> P_S3   (grid d.G)
+__global__ __launch_bounds__(MSDP_BLOCK) void k_dgen_outer(Dev d, int nS, const double* __restrict__ Xd, const double* __restrict__ S,
+                                                           double* __restrict__ x, const double* __restrict__ bA,
+                                                           const double* __restrict__ C, double sigma) {
+    __shared__ double sh[3 * MSDP_WAVES];
+    const int64_t tot = (int64_t)d.n * nS;
+    double pc = 0.0, pa = 0.0;
+    for (int64_t e = blockIdx.x * (int64_t)MSDP_BLOCK + threadIdx.x; e < tot; e += (int64_t)gridDim.x * MSDP_BLOCK) {
+        if ((int)(e % nS) >= d.n) continue;
+        const double X = Xd[e], xo = x[e];
+        const double as = S[e] + xo / sigma;
+        x[e] = X - bA[e];
+        pc = fma(C[e], X, pc);
+        pa = fma(as, as, pa);
+    }
+    msdp_put_partials3(d.P, P_S2, pc, P_S3, pa, -1, 0.0, sh);
 }
 // P = Xa' * Xb (ld x ld) from two n x ld panels: per-workgroup partials over a row range, then their sum
 __global__ __launch_bounds__(256) void k_pp_gram_part(int n, int ld, const double* __restrict__ Xa, const double* __restrict__ Xb,
@@ -2472,6 +2559,11 @@ __global__ __launch_bounds__(MSDP_BLOCK) void k_dual_outer(Dev d, int nS, double
     msdp_put_partials3(d.P, P_S2, pc, P_S3, pa, -1, 0.0, sh);
 }
 
+static int dgen_rows_grid(int64_t m) {
+    int64_t g = (m + 3) / 4;                               // four waves (rows) per workgroup
+    if (g > 4096) g = 4096;
+    return (int)std::max<int64_t>(g, 1);
+}
 static int dual_pp_gram(msdp_handle h, DualState* ds, const double* Xa, const double* Xb, double* out, const int* flag, int when) {
     const Dev& d = h->d;
     hipLaunchKernelGGL(k_pp_gram_part, dim3(DUAL_PP_BLOCKS), dim3(256), 0, h->stream, d.n, d.ld, Xa, Xb, ds->pp_part, flag, when);
@@ -2504,10 +2596,23 @@ static int dual_cost_state(msdp_handle h, AffineState* st, const double* Ys, dou
     }
     hipLaunchKernelGGL(k_gram_mfma, dim3((a.nS + 63) / 64, (a.n + 63) / 64), dim3(512), 0, h->stream, a.n, a.nS, a.ld, Ys, Ys, ds->Sg, flag, when, 0);
     HIPCHK(hipGetLastError());
-    if ((rc = launch_adjoint(h, a, (const double*)ds->T, (const double*)a.w, -sigma, Xout, flag, when, false))) return rc;
-    hipLaunchKernelGGL(k_dual_finish_X, dim3(MSDP_MAX_GRID), dim3(256), 0, h->stream, (int64_t)a.n * a.nS, Xout, (const double*)ds->Sg,
-                       (const double*)ds->bA, sigma, d.P, flag, when);
-    HIPCHK(hipGetLastError());
+    if (ds->generic) {
+        // Q = (C - x/sigma) + A'y; As = Q - S (into Sg), R = bA - sigma*As; v = sigma*D\(A*As + B*Af); X = R + A'v
+        if ((rc = launch_adjoint(h, a, (const double*)ds->T, (const double*)a.w, 1.0, Xout, flag, when, false))) return rc;
+        hipLaunchKernelGGL(k_dgen_as, dim3(MSDP_MAX_GRID), dim3(256), 0, h->stream, (int64_t)a.n * a.nS, a.n, a.nS, (const double*)Xout,
+                           ds->Sg, (const double*)ds->bA, sigma, ds->R, d.P, flag, when);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_dgen_rows, dim3(dgen_rows_grid(a.m)), dim3(256), 0, h->stream, a.m, ds->arp, ds->apos, ds->aval,
+                           (const double*)ds->Sg, sigma, ds->brp, ds->bcol, ds->bval, ds->nf > 0 ? (const double*)ds->Af : (const double*)nullptr,
+                           sigma, ds->dinv, (const double*)nullptr, 0.0, 0, ds->v, flag, when);
+        HIPCHK(hipGetLastError());
+        if ((rc = launch_adjoint(h, a, (const double*)ds->R, (const double*)ds->v, 1.0, Xout, flag, when, false))) return rc;
+    } else {
+        if ((rc = launch_adjoint(h, a, (const double*)ds->T, (const double*)a.w, -sigma, Xout, flag, when, false))) return rc;
+        hipLaunchKernelGGL(k_dual_finish_X, dim3(MSDP_MAX_GRID), dim3(256), 0, h->stream, (int64_t)a.n * a.nS, Xout, (const double*)ds->Sg,
+                           (const double*)ds->bA, sigma, d.P, flag, when);
+        HIPCHK(hipGetLastError());
+    }
     hipLaunchKernelGGL(k_dual_cost, dim3(1), dim3(MSDP_BLOCK), 0, h->stream, d, sigma, (const double*)ds->Af, ds->nf, ds->scal, flag, when);
     HIPCHK(hipGetLastError());
     return 0;
@@ -2527,7 +2632,12 @@ static int dual_costgrad(msdp_handle h, AffineState* st, int slot) {
     if ((rc = msdp_dense_gemm(h, 1, M, X, sc, nullptr, &slab, &stride, &SK))) return rc;
     DISPATCH_LPR_A(k_rowdot_slabs, h, d.G, d, Ys, slab, stride, SK, 2.0, d.Gr[slot], d.eG[slot], P_S2);
     HIPCHK(hipGetLastError());
-    DISPATCH_LPR_A(k_obl_grad_finish, h, d.G, d, slot, st->sigma, (const double*)ds->scal);
+    if (ds->generic) {
+        // G = 2*X*Y as is (euclideanfactory: no projection, :170)
+        hipLaunchKernelGGL(k_sph_grad_finish, dim3(d.G), dim3(MSDP_BLOCK), 0, h->stream, d, slot, st->sigma, (const double*)ds->scal);
+    } else {
+        DISPATCH_LPR_A(k_obl_grad_finish, h, d.G, d, slot, st->sigma, (const double*)ds->scal);
+    }
     HIPCHK(hipGetLastError());
     return dual_pp_gram(h, ds, Ys, Ys, ds->G2[slot], done, 1);
 }
@@ -2542,15 +2652,40 @@ static int dual_hess(msdp_handle h, AffineState* st) {
     const int* act = &d.F[0].active;
     int rc;
     if ((rc = dual_check(h, ds))) return rc;
-    if ((rc = launch_A(h, a, st->nnz, d.Y[cur], d.md, act, 0, 0, (double*)nullptr, sigma))) return rc;
-    { int64_t g = (a.m + 255) / 256; if (g > 2048) g = 2048;
-      hipLaunchKernelGGL(k_dual_scale, dim3((int)g), dim3(256), 0, h->stream, a.m, a.w, ds->dinv, act, 0); }
-    HIPCHK(hipGetLastError());
-    if ((rc = launch_adjoint(h, a, (const double*)nullptr, (const double*)a.w, 1.0, d.AyU, act, 0, false))) return rc;
+    double cA = -4.0 * sigma;
+    if (ds->generic) {
+        // w = A(U Y') (a = w/dAAt); v = D\B*(B'a) + G*a - 2a; AyU = A'v   (:175-176)
+        if ((rc = launch_A(h, a, st->nnz, d.md, d.Y[cur], act, 0, 0, (double*)nullptr, sigma))) return rc;
+        const bool gI = ds->g_identity;
+        if (!gI) {
+            int64_t g = (a.m + 255) / 256; if (g > 2048) g = 2048;
+            hipLaunchKernelGGL(k_dual_scale, dim3((int)g), dim3(256), 0, h->stream, a.m, a.w, ds->dinv, act, 0);
+            HIPCHK(hipGetLastError());
+            if ((rc = launch_adjoint(h, a, (const double*)nullptr, (const double*)a.w, 1.0, d.AyU, act, 0, false))) return rc;
+        }
+        if (ds->nf > 0) {
+            hipLaunchKernelGGL(k_dual_free, dim3(ds->nf), dim3(256), 0, h->stream, ds->bjc, ds->bir, ds->bpr, (const double*)a.w,
+                               (const double*)nullptr, (const double*)nullptr, sigma, ds->tB, act, 0, gI ? ds->dinv : (const double*)nullptr);
+            HIPCHK(hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_dgen_rows, dim3(dgen_rows_grid(a.m)), dim3(256), 0, h->stream, a.m, ds->arp, ds->apos, ds->aval,
+                           gI ? (const double*)nullptr : (const double*)d.AyU, 1.0, ds->brp, ds->bcol, ds->bval,
+                           ds->nf > 0 ? (const double*)ds->tB : (const double*)nullptr, 1.0, ds->dinv, (const double*)a.w,
+                           gI ? -1.0 : -2.0, gI ? 1 : 0, ds->v, act, 0);
+        HIPCHK(hipGetLastError());
+        if ((rc = launch_adjoint(h, a, (const double*)nullptr, (const double*)ds->v, 1.0, d.AyU, act, 0, false))) return rc;
+        cA = 4.0 * sigma;
+    } else {
+        if ((rc = launch_A(h, a, st->nnz, d.Y[cur], d.md, act, 0, 0, (double*)nullptr, sigma))) return rc;
+        { int64_t g = (a.m + 255) / 256; if (g > 2048) g = 2048;
+          hipLaunchKernelGGL(k_dual_scale, dim3((int)g), dim3(256), 0, h->stream, a.m, a.w, ds->dinv, act, 0); }
+        HIPCHK(hipGetLastError());
+        if ((rc = launch_adjoint(h, a, (const double*)nullptr, (const double*)a.w, 1.0, d.AyU, act, 0, false))) return rc;
+    }
     const double* slab; int64_t stride; int SK;
     const double* M[2] = {d.eS[cur], d.AyU};
     const double* X[2] = {d.md, d.Y[cur]};
-    const double sc[2] = {2.0, -4.0 * sigma};
+    const double sc[2] = {2.0, cA};
     if ((rc = msdp_dense_gemm(h, 2, M, X, sc, act, &slab, &stride, &SK))) return rc;
     if ((rc = dual_pp_gram(h, ds, d.md, d.Y[cur], ds->M1, act, 0))) return rc;
     double* extra = const_cast<double*>(slab) + (int64_t)SK * stride;
@@ -2559,6 +2694,7 @@ static int dual_hess(msdp_handle h, AffineState* st) {
                          (const double*)ds->M1, (const double*)ds->G2[cur], 2.0 * sigma, extra, act, 0); }
     HIPCHK(hipGetLastError());
     ++SK;
+    if (ds->generic) return msdp_sphere_hess_raw(h, slab, stride, SK);      // Euclidean epilogue: H as is
     return msdp_dense_hess_epilogue_obl(h, slab, stride, SK);
 }
 
@@ -2577,9 +2713,10 @@ static int dual_linesearch_cost(msdp_handle h, AffineState* st, const double* Yt
     return 0;
 }
 
-// Second half of msdp_create_dual_unitdiag: msdp_affine_setup has uploaded At (= A'), b and C = reshape(c).
+// Second half of msdp_create_dual_unitdiag / msdp_create_dual: msdp_affine_setup has uploaded At (= A'), b and C = reshape(c).
 int msdp_dual_setup(msdp_handle h, const int64_t* at_jc, const int64_t* at_ir, const double* at_pr, const double* b, const double* c,
-                    const double* dAAt, int32_t nf, const int64_t* b_jc, const int64_t* b_ir, const double* b_pr, const double* cf) {
+                    const double* dAAt, int32_t nf, const int64_t* b_jc, const int64_t* b_ir, const double* b_pr, const double* cf,
+                    bool generic) {
     AffineState* st = astate(h);
     if (!st) { msdp_set_error("affine state missing"); return MSDP_ESTATE; }
     Dev& d = h->d;
@@ -2641,10 +2778,59 @@ int msdp_dual_setup(msdp_handle h, const int64_t* at_jc, const int64_t* at_ir, c
     if ((rc = msdp_dev_alloc_bytes(h, &p, 8 * sizeof(double)))) return rc;
     ds->scal = (double*)p; HIPCHK(hipMemset(p, 0, 8 * sizeof(double)));
     // the adjoint of the dual kind always sweeps the whole matrix (X and As are dense)
+    if (!generic) return 0;
+    ds->generic = true;
+    // A by rows (the columns of At) with row-major positions; G = I check: disjoint supports, dAAt(k) == sum_t A_kt^2 bit for bit
+    std::vector<int64_t> arp((size_t)m + 1, 0), apos;
+    std::vector<double> aval;
+    std::vector<unsigned char> used((size_t)n * n, 0);
+    bool gI = true;
+    for (int64_t k = 0; k < m; ++k) {
+        double ss = 0.0;
+        for (int64_t t = at_jc[k]; t < at_jc[k + 1]; ++t) {
+            const int64_t r = at_ir[t];
+            if (r < 0 || r >= (int64_t)n * n) { msdp_set_error("dual kind: row index of At out of range"); return MSDP_EINVAL; }
+            if (used[(size_t)r]) gI = false;
+            used[(size_t)r] = 1;
+            ss += at_pr[t] * at_pr[t];
+            apos.push_back((r % n) * nS + r / n);
+            aval.push_back(at_pr[t]);
+        }
+        if (ss != dAAt[k]) gI = false;
+        arp[(size_t)k + 1] = (int64_t)apos.size();
+    }
+    if (apos.empty()) { apos.push_back(0); aval.push_back(0.0); }
+    ds->g_identity = gI;
+    std::vector<int> brp((size_t)m + 1, 0), bcol(std::max<size_t>(bir.size(), 1), 0);
+    std::vector<double> bval(std::max<size_t>(bir.size(), 1), 0.0);
+    for (int j = 0; j < nf; ++j)
+        for (int t = bjc[(size_t)j]; t < bjc[(size_t)j + 1]; ++t) ++brp[(size_t)bir[(size_t)t] + 1];
+    for (int64_t k = 0; k < m; ++k) brp[(size_t)k + 1] += brp[(size_t)k];
+    {
+        std::vector<int> fill(brp.begin(), brp.end() - 1);
+        for (int j = 0; j < nf; ++j)
+            for (int t = bjc[(size_t)j]; t < bjc[(size_t)j + 1]; ++t) {
+                const int q = fill[(size_t)bir[(size_t)t]]++;
+                bcol[(size_t)q] = j; bval[(size_t)q] = bpr[(size_t)t];
+            }
+    }
+    if ((rc = up(h, arp, &ds->arp)) || (rc = up(h, apos, &ds->apos)) || (rc = up(h, aval, &ds->aval)) ||
+        (rc = up(h, brp, &ds->brp)) || (rc = up(h, bcol, &ds->bcol)) || (rc = up(h, bval, &ds->bval))) return rc;
+    if ((rc = msdp_dev_alloc_bytes(h, &p, msz))) return rc;
+    ds->R = (double*)p; HIPCHK(hipMemset(p, 0, msz));
+    if ((rc = msdp_dev_alloc_bytes(h, &p, (size_t)m * sizeof(double)))) return rc;
+    ds->v = (double*)p; HIPCHK(hipMemset(p, 0, (size_t)m * sizeof(double)));
+    if ((rc = msdp_dev_alloc_bytes(h, &p, nfb))) return rc;
+    ds->tB = (double*)p; HIPCHK(hipMemset(p, 0, nfb));
     return 0;
 }
 
-// sigma and the free multipliers w for the next trustregions() call; T = bA + x - sigma*C
+int msdp_dual_g_identity(msdp_handle h) {
+    AffineState* st = astate(h);
+    return (st && st->dual && st->dual->g_identity) ? 1 : 0;
+}
+
+// sigma and the free multipliers w for the next trustregions() call; T = bA + x - sigma*C (generic: C - x/sigma)
 int msdp_dual_set_penalty_impl(msdp_handle h, double sigma, const double* wf_host) {
     AffineState* st = astate(h);
     if (!st || !st->dual) { msdp_set_error("dual_set_penalty: not a dual handle"); return MSDP_ESTATE; }
@@ -2657,8 +2843,12 @@ int msdp_dual_set_penalty_impl(msdp_handle h, double sigma, const double* wf_hos
     st->sigma = sigma;
     h->h_ctl->sigma = sigma;
     const int64_t tot = (int64_t)st->a.n * st->a.nS;
-    hipLaunchKernelGGL(k_dual_T, dim3(2048), dim3(256), 0, h->stream, tot, ds->T, (const double*)ds->bA, (const double*)ds->x,
-                       (const double*)h->d.Cd, sigma);
+    if (ds->generic)
+        hipLaunchKernelGGL(k_dual_T, dim3(2048), dim3(256), 0, h->stream, tot, ds->T, (const double*)ds->bA, (const double*)ds->x,
+                           (const double*)h->d.Cd, 0.0, -1.0 / sigma, 1.0);
+    else
+        hipLaunchKernelGGL(k_dual_T, dim3(2048), dim3(256), 0, h->stream, tot, ds->T, (const double*)ds->bA, (const double*)ds->x,
+                           (const double*)h->d.Cd, 1.0, 1.0, -sigma);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
     ds->T_valid = true;
@@ -2677,6 +2867,25 @@ int msdp_dual_outer_step_impl(msdp_handle h, double* scal_host, double* Af_host,
     const double sigma = st->sigma;
     const double* Ys = d.Y[h->h_ctl->cur];
     int rc;
+    if (ds->generic) {
+        // :66-77: X of :169 at Y with the multipliers of the solve (x, w/sigma in T and wf) -> d.Sdual; then x = X - bA
+        if ((rc = dual_check(h, ds))) return rc;
+        if ((rc = dual_cost_state(h, st, Ys, d.Sdual, (const int*)nullptr, 0))) return rc;
+        if (ds->nf > 0) {                                  // Af = B'y - cf (:70)
+            hipLaunchKernelGGL(k_dual_free, dim3(ds->nf), dim3(256), 0, h->stream, ds->bjc, ds->bir, ds->bpr, (const double*)a.w, ds->cf,
+                               (const double*)nullptr, sigma, ds->Af, (const int*)nullptr, 0, (const double*)nullptr);
+            HIPCHK(hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_dgen_outer, dim3(d.G), dim3(MSDP_BLOCK), 0, h->stream, d, a.nS, (const double*)d.Sdual, (const double*)ds->Sg,
+                           ds->x, (const double*)ds->bA, (const double*)d.Cd, sigma);
+        HIPCHK(hipGetLastError());
+        if ((rc = msdp_k_sum_to_fwd(h, P_S2, ds->scal + 2)) || (rc = msdp_k_sum_to_fwd(h, P_S3, ds->scal + 3))) return rc;
+        HIPCHK(msdp_memcpy_async(scal_host, ds->scal + 1, 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        if (ds->nf > 0) HIPCHK(msdp_memcpy_async(Af_host, ds->Af, (size_t)ds->nf * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        ds->T_valid = false;
+        return 0;
+    }
     if ((rc = launch_A(h, a, st->nnz, Ys, Ys, (const int*)nullptr, 0, 0, (double*)nullptr, sigma))) return rc;
     hipLaunchKernelGGL(k_dual_y, dim3(d.G), dim3(MSDP_BLOCK), 0, h->stream, a.m, a.w, ds->dinv, ds->Ac, a.b, d.P, (const int*)nullptr, 0);
     HIPCHK(hipGetLastError());

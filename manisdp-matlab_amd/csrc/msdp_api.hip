@@ -290,7 +290,8 @@ void msdp_host_kits_release() {                               // msdp_release_ca
     g_kits.clear();
 }
 
-static bool boundary_colmajor(msdp_handle h) { return h->kind == MSDP_KIND_UNITTRACE || h->kind == MSDP_KIND_GENERIC; }
+static bool boundary_colmajor(msdp_handle h) { return h->kind == MSDP_KIND_UNITTRACE || h->kind == MSDP_KIND_GENERIC || h->kind == MSDP_KIND_DUAL; }
+static bool dual_kind(msdp_handle h) { return h->kind == MSDP_KIND_DUAL_UNITDIAG || h->kind == MSDP_KIND_DUAL; }
 
 static int rows_capacity(msdp_handle h) {
     // equal per-rank row count so the all-gather is one uniform RCCL call
@@ -725,7 +726,8 @@ extern "C" int msdp_create_multiblock(int32_t nb, const int64_t* block_n, int32_
 
 void msdp_escape_workspace_park(double* ptr, size_t cap_doubles);     // msdp_escape.hip
 int msdp_dual_setup(msdp_handle h, const int64_t* at_jc, const int64_t* at_ir, const double* at_pr, const double* b, const double* c,
-                    const double* dAAt, int32_t nf, const int64_t* b_jc, const int64_t* b_ir, const double* b_pr, const double* cf);
+                    const double* dAAt, int32_t nf, const int64_t* b_jc, const int64_t* b_ir, const double* b_pr, const double* cf,
+                    bool generic);
 int msdp_dual_set_penalty_impl(msdp_handle h, double sigma, const double* wf_host);
 int msdp_dual_outer_step_impl(msdp_handle h, double* scal_host, double* Af_host, double* z_host);
 int msdp_dual_get_y_impl(msdp_handle h, double* y_host);
@@ -739,23 +741,47 @@ extern "C" int msdp_create_dual_unitdiag(int64_t n, int64_t m, const int64_t* at
     int rc = msdp_create_affine(MSDP_KIND_UNITDIAG, n, m, at_jc, at_ir, at_pr, b, c, pcap, &h);
     if (rc) return rc;
     h->kind = MSDP_KIND_DUAL_UNITDIAG;
-    if ((rc = msdp_dual_setup(h, at_jc, at_ir, at_pr, b, c, dAAt, nf, b_jc, b_ir, b_pr, cf))) { msdp_destroy(h); return rc; }
+    if ((rc = msdp_dual_setup(h, at_jc, at_ir, at_pr, b, c, dAAt, nf, b_jc, b_ir, b_pr, cf, false))) { msdp_destroy(h); return rc; }
     *out = h;
+    return 0;
+}
+
+// src/dual/ManiDSDP.m: the same data on the Euclidean factor (the affine generic kind's manifold and boundary)
+extern "C" int msdp_create_dual(int64_t n, int64_t m, const int64_t* at_jc, const int64_t* at_ir, const double* at_pr,
+                                const double* dAAt, const double* b, const double* c, int32_t nf, const int64_t* b_jc,
+                                const int64_t* b_ir, const double* b_pr, const double* cf, int32_t pcap, msdp_handle* out) {
+    if (!at_jc || !at_ir || !at_pr || !dAAt || !b || !c || m <= 0) { msdp_set_error("dual: null/empty data"); return MSDP_EINVAL; }
+    if (nf < 0 || (nf > 0 && (!b_jc || !b_ir || !b_pr || !cf))) { msdp_set_error("dual: bad free part"); return MSDP_EINVAL; }
+    msdp_handle h = nullptr;
+    int rc = msdp_create_affine(MSDP_KIND_GENERIC, n, m, at_jc, at_ir, at_pr, b, c, pcap, &h);
+    if (rc) return rc;
+    h->kind = MSDP_KIND_DUAL;
+    if ((rc = msdp_dual_setup(h, at_jc, at_ir, at_pr, b, c, dAAt, nf, b_jc, b_ir, b_pr, cf, true))) { msdp_destroy(h); return rc; }
+    *out = h;
+    return 0;
+}
+
+int msdp_dual_g_identity(msdp_handle h);      // msdp_affine.hip
+extern "C" int msdp_dual_info(msdp_handle h, int32_t* g_identity) {
+    CHECK_H(h);
+    if (!dual_kind(h) || !g_identity) { msdp_set_error("dual_info: not a dual handle / null out"); return MSDP_ESTATE; }
+    *g_identity = msdp_dual_g_identity(h);
     return 0;
 }
 
 extern "C" int msdp_dual_set_penalty(msdp_handle h, double sigma, const double* w) {
     CHECK_H(h);
-    if (h->kind != MSDP_KIND_DUAL_UNITDIAG) { msdp_set_error("dual_set_penalty: not a dual handle"); return MSDP_ESTATE; }
+    if (!dual_kind(h)) { msdp_set_error("dual_set_penalty: not a dual handle"); return MSDP_ESTATE; }
     h->state_valid = false;
     h->gradnorm_valid = false;
+    h->chunk_len = 0;      // sigma is baked into the captured Hess-vec launches (both dual kinds): force a re-capture
     return msdp_dual_set_penalty_impl(h, sigma, w);
 }
 
 extern "C" int msdp_dual_outer_step(msdp_handle h, double* scal, double* Af, double* z) {
     CHECK_H(h);
-    if (h->kind != MSDP_KIND_DUAL_UNITDIAG) { msdp_set_error("dual_outer_step: not a dual handle"); return MSDP_ESTATE; }
-    if (!scal || !z) { msdp_set_error("dual_outer_step: null argument"); return MSDP_EINVAL; }
+    if (!dual_kind(h)) { msdp_set_error("dual_outer_step: not a dual handle"); return MSDP_ESTATE; }
+    if (!scal || (!z && h->kind == MSDP_KIND_DUAL_UNITDIAG)) { msdp_set_error("dual_outer_step: null argument"); return MSDP_EINVAL; }
     if (!h->have_point) { msdp_set_error("no resident point"); return MSDP_ESTATE; }
     h->state_valid = false;
     int rc = msdp_dual_outer_step_impl(h, scal, Af, z);
@@ -765,7 +791,7 @@ extern "C" int msdp_dual_outer_step(msdp_handle h, double* scal, double* Af, dou
 
 extern "C" int msdp_dual_get_y(msdp_handle h, double* y) {
     CHECK_H(h);
-    if (h->kind != MSDP_KIND_DUAL_UNITDIAG || !h->dual_valid || !y) { msdp_set_error("dual_get_y: call msdp_dual_outer_step first"); return MSDP_ESTATE; }
+    if (!dual_kind(h) || !h->dual_valid || !y) { msdp_set_error("dual_get_y: call msdp_dual_outer_step first"); return MSDP_ESTATE; }
     return msdp_dual_get_y_impl(h, y);
 }
 
@@ -806,7 +832,7 @@ extern "C" int msdp_destroy(msdp_handle h) {
 extern "C" int msdp_set_multipliers(msdp_handle h, const double* y, double sigma) {
     CHECK_H(h);
     if (h->d.costkind != COST_AFFINE) { msdp_set_error("set_multipliers: handle has no affine constraints"); return MSDP_ESTATE; }
-    if (h->kind == MSDP_KIND_DUAL_UNITDIAG) { msdp_set_error("set_multipliers: dual handles take msdp_dual_set_penalty"); return MSDP_ESTATE; }
+    if (dual_kind(h)) { msdp_set_error("set_multipliers: dual handles take msdp_dual_set_penalty"); return MSDP_ESTATE; }
     h->state_valid = false;
     h->chunk_len = 0;      // sigma is baked into the captured launches: force a re-capture
     return msdp_affine_set_multipliers(h, y, sigma);
@@ -1822,7 +1848,7 @@ extern "C" int msdp_comm_init_local(msdp_handle h, int32_t nranks, int32_t rank,
     if (nranks < 1 || nranks > LOCAL_MAX_RANKS || rank < 0 || rank >= nranks) { msdp_set_error("comm_init_local: bad arguments"); return MSDP_EINVAL; }
     if (h->have_point || h->use_comm) { msdp_set_error("comm_init_local must precede set_point / comm_init"); return MSDP_ESTATE; }
     if (h->presharded && (nranks != h->nranks || rank != h->rank)) { msdp_set_error("comm_init_local: shard was created as rank %d of %d", h->rank, h->nranks); return MSDP_EINVAL; }
-    if (h->kind == MSDP_KIND_MULTIBLOCK || h->kind == MSDP_KIND_DUAL_UNITDIAG) { msdp_set_error("row sharding is not implemented for the multiblock and dual kinds"); return MSDP_EUNSUPPORTED; }
+    if (h->kind == MSDP_KIND_MULTIBLOCK || dual_kind(h)) { msdp_set_error("row sharding is not implemented for the multiblock and dual kinds"); return MSDP_EUNSUPPORTED; }
     {
         std::lock_guard<std::mutex> lk(g_groups_mutex);
         LocalGroup*& g = g_groups[group_id];
@@ -1843,7 +1869,7 @@ extern "C" int msdp_comm_init_ipc(msdp_handle h, int32_t nranks, int32_t rank, c
     if (nranks < 1 || nranks > LOCAL_MAX_RANKS || rank < 0 || rank >= nranks || !name || name[0] != '/') { msdp_set_error("comm_init_ipc: bad arguments (the name starts with '/')"); return MSDP_EINVAL; }
     if (h->have_point || h->use_comm) { msdp_set_error("comm_init_ipc must precede set_point / comm_init"); return MSDP_ESTATE; }
     if (h->presharded && (nranks != h->nranks || rank != h->rank)) { msdp_set_error("comm_init_ipc: shard was created as rank %d of %d", h->rank, h->nranks); return MSDP_EINVAL; }
-    if (h->kind == MSDP_KIND_MULTIBLOCK || h->kind == MSDP_KIND_DUAL_UNITDIAG) { msdp_set_error("row sharding is not implemented for the multiblock and dual kinds"); return MSDP_EUNSUPPORTED; }
+    if (h->kind == MSDP_KIND_MULTIBLOCK || dual_kind(h)) { msdp_set_error("row sharding is not implemented for the multiblock and dual kinds"); return MSDP_EUNSUPPORTED; }
     // The host segment: rank 0 removes whatever a crashed run left under this name, creates the segment anew (O_EXCL),
     // clears it and writes the magic word LAST; the others open it without O_CREAT, wait for the magic word and check that the name
     // still leads to the segment they mapped (a stale one that rank 0 has replaced meanwhile does not).
@@ -2026,7 +2052,7 @@ extern "C" int msdp_comm_init(msdp_handle h, int32_t nranks, int32_t rank, const
     if (nranks < 1 || rank < 0 || rank >= nranks || !id128) { msdp_set_error("bad comm arguments"); return MSDP_EINVAL; }
     if (h->have_point) { msdp_set_error("comm_init must precede set_point"); return MSDP_ESTATE; }
     if (h->presharded && (nranks != h->nranks || rank != h->rank)) { msdp_set_error("comm_init: shard was created as rank %d of %d", h->rank, h->nranks); return MSDP_EINVAL; }
-    if (h->kind == MSDP_KIND_MULTIBLOCK || h->kind == MSDP_KIND_DUAL_UNITDIAG) {
+    if (h->kind == MSDP_KIND_MULTIBLOCK || dual_kind(h)) {
         msdp_set_error("row sharding is not implemented for the multiblock and dual kinds");
         return MSDP_EUNSUPPORTED;
     }
@@ -2064,7 +2090,7 @@ extern "C" int msdp_debug_shard(msdp_handle h, int32_t nranks, int32_t rank) {
     CHECK_H(h);
     if (nranks < 1 || rank < 0 || rank >= nranks) { msdp_set_error("bad shard (%d of %d)", rank, nranks); return MSDP_EINVAL; }
     if (h->have_point || h->use_comm) { msdp_set_error("debug_shard must precede set_point / comm_init"); return MSDP_ESTATE; }
-    if (h->d.costkind == COST_DENSE || h->kind == MSDP_KIND_MULTIBLOCK || h->kind == MSDP_KIND_DUAL_UNITDIAG) {
+    if (h->d.costkind == COST_DENSE || h->kind == MSDP_KIND_MULTIBLOCK || dual_kind(h)) {
         msdp_set_error("debug_shard: sparse-C and affine (unitdiag / unittrace / generic) handles only");
         return MSDP_EUNSUPPORTED;
     }

@@ -15,7 +15,9 @@
 //                                                        sparse n^2 x m, dAAt = diag(A*A'), c the PSD part of the cost,
 //                                                        B = A(:,1:K.f) sparse m x nf (or []), cf its costs
 //       manisdp_mex('dual_set_penalty', h, sigma, w)     before every rtr of a dual handle (w: nf x 1)
-//   [by, cex, as2, Af, z] = manisdp_mex('dual_outer_step', h)   ManiDSDP_unitdiag.m:70-81 on the device
+//   h = manisdp_mex('create_dual', At, dAAt, b, c, n, B, cf)   generic dual approach (ManiDSDP.m): the arguments of
+//                                                        create_dual_unitdiag, Euclidean n x p factor
+//   [by, cex, as2, Af, z] = manisdp_mex('dual_outer_step', h)   ManiDSDP_unitdiag.m:70-81 (ManiDSDP.m:66-77, z = 0) on the device
 //   y = manisdp_mex('dual_get_y', h)
 //       manisdp_mex('set_multipliers', h, y, sigma)
 //       manisdp_mex('set_point', h, Y)                   Y in the reference layout of the handle's kind
@@ -117,7 +119,7 @@ double field_or(const mxArray* s, const char* name, double dflt) {
     return f ? mxGetScalar(f) : dflt;
 }
 
-bool factor_is_n_by_p(int kind) { return kind == MSDP_KIND_UNITTRACE || kind == MSDP_KIND_GENERIC; }
+bool factor_is_n_by_p(int kind) { return kind == MSDP_KIND_UNITTRACE || kind == MSDP_KIND_GENERIC || kind == MSDP_KIND_DUAL; }
 
 // p of a factor handed over in the layout of `kind`; checks the other dimension against n
 int32_t width_of(const mxArray* Y, const Meta& me) {
@@ -230,8 +232,9 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         return;
     }
 
-    if (cmd == "create_dual_unitdiag") {
-        need(nrhs == 8, "h = manisdp_mex('create_dual_unitdiag', At, dAAt, b, c, n, B, cf)");
+    if (cmd == "create_dual_unitdiag" || cmd == "create_dual") {
+        const bool generic = cmd == "create_dual";
+        need(nrhs == 8, "h = manisdp_mex('create_dual_unitdiag' | 'create_dual', At, dAAt, b, c, n, B, cf)");
         const mxArray* At = prhs[1];
         if (!mxIsSparse(At)) mexErrMsgIdAndTxt("ManiSDP:hip:arg", "At must be sparse (n^2 x m)");
         const int64_t n = (int64_t)mxGetScalar(prhs[5]);
@@ -246,11 +249,11 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         if (nf > 0 && (!mxIsSparse(B) || (int64_t)mxGetM(B) != m)) mexErrMsgIdAndTxt("ManiSDP:hip:arg", "B must be sparse m x nf");
         const std::vector<double> cf = as_dense(prhs[7], (size_t)(nf > 0 ? nf : 1));
         msdp_handle h = nullptr;
-        const int rc = msdp_create_dual_unitdiag(n, m, (const int64_t*)mxGetJc(At), (const int64_t*)mxGetIr(At), mxGetPr(At), dAAt.data(),
-                                                 b.data(), c.data(), (int32_t)nf, nf ? (const int64_t*)mxGetJc(B) : nullptr,
-                                                 nf ? (const int64_t*)mxGetIr(B) : nullptr, nf ? mxGetPr(B) : nullptr, cf.data(), 32, &h);
-        if (rc) fail("create_dual_unitdiag", rc);
-        plhs[0] = wrap_handle(h, MSDP_KIND_DUAL_UNITDIAG, n, m, nf);
+        const int rc = (generic ? msdp_create_dual : msdp_create_dual_unitdiag)(
+            n, m, (const int64_t*)mxGetJc(At), (const int64_t*)mxGetIr(At), mxGetPr(At), dAAt.data(), b.data(), c.data(), (int32_t)nf,
+            nf ? (const int64_t*)mxGetJc(B) : nullptr, nf ? (const int64_t*)mxGetIr(B) : nullptr, nf ? mxGetPr(B) : nullptr, cf.data(), 32, &h);
+        if (rc) fail(generic ? "create_dual" : "create_dual_unitdiag", rc);
+        plhs[0] = wrap_handle(h, generic ? MSDP_KIND_DUAL : MSDP_KIND_DUAL_UNITDIAG, n, m, nf);
         return;
     }
 

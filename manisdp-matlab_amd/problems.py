@@ -465,6 +465,50 @@ def qsmom(n, coe):
 
 
 # -------------------------------------------------------------------------- sensor network localization
+def qssos(n, coe):
+    """Second-order SOS relaxation of ``min coe'[x]_4, |x|^2 = 1`` in SeDuMi format (dual side of :func:`qsmom`):
+    find the largest lambda with ``coe'[x]_4 - lambda = sum_i h_i(x) (|x|^2 - 1) + m(x)' S m(x)``, S psd, m(x) = [x]_2.
+    Restates src/basicfunction/qssos.m:7-57.  Returns ``(A, b, c, K, dAAt)``: A is m x (mb^2 + mb + 1), m = C(n+4, 4),
+    mb = C(n+2, 2), its columns the constant lambda (column 0), the mb multiplier coefficients h (columns 1..mb) and
+    vec(S) column-major (:39-42); ``K = {'f': mb + 1, 's': mb}``, ``b = coe``, ``c = e_1``; ``dAAt`` = diag(A_psd A_psd')
+    as the reference accumulates it (:43, :46)."""
+    coe = np.asarray(coe, dtype=np.float64).ravel()
+    sp2 = get_basis(n, 2).astype(np.int64)
+    sp4 = get_basis(n, 4).astype(np.int64)
+    mb = sp2.shape[1]
+    lsp = sp4.shape[1]
+    if coe.size != lsp:
+        raise ValueError(f"qssos: coe must have length C(n+4,4) = {lsp}")
+    index = {tuple(sp4[:, k]): k for k in range(lsp)}          # bfind (:28, :37)
+    rows, cols, vals = [0], [0], [1.0]                          # :16-17
+    dAAt = np.zeros(lsp)
+    for i in range(mb):                                         # :19-33: h_i(x) (x_1^2 + ... + x_n^2 - 1)
+        for j in range(n + 1):
+            bi = sp2[:, i].copy()
+            if j < n:
+                bi[j] += 2
+            rows.append(index[tuple(bi)])
+            cols.append(i + 1)
+            vals.append(1.0 if j < n else -1.0)
+    for i in range(mb):                                         # :34-50: m(x)' S m(x)
+        for j in range(i, mb):
+            locb = index[tuple(sp2[:, i] + sp2[:, j])]
+            rows.append(locb)
+            cols.append((i + 1) * mb + j + 1)
+            vals.append(1.0)
+            if j > i:
+                rows.append(locb)
+                cols.append((j + 1) * mb + i + 1)
+                vals.append(1.0)
+                dAAt[locb] += 2
+            else:
+                dAAt[locb] += 1
+    A = sp.csr_matrix((vals, (rows, cols)), shape=(lsp, mb * mb + mb + 1))   # :51 (duplicates summed, as sparse() does)
+    c = np.zeros(mb * mb + mb + 1)
+    c[0] = 1.0                                                  # :55-56
+    return A, coe.copy(), c, {"f": mb + 1, "s": mb}, dAAt
+
+
 def snl_polynomial(n, seed=1, radius2=0.5):
     """The quartic of example/Sensor_Network_Localization.m:2-31: ``n`` sensors at random positions in the unit square, the four anchors
     of the example, an edge wherever two sensors (or, for the LAST sensor as in the example's ``for i = n``, sensor and anchor) are

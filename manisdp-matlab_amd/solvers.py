@@ -969,3 +969,151 @@ def _dual_unitdiag_impl(A, b, c, K, options, verbose, rng):
         _say(verbose, "Iteration maximum is reached!")
     _say(verbose, "ManiDSDP: optimum = %0.8f, time = %0.2fs" % (obj, time.time() - t0))
     return X, obj, data
+
+
+# ===================================================================== dual approach, generic
+DEFAULTS["dual"] = dict(p0=1, ADMM_maxiter=1000, gama=2, sigma0=1e-1, sigma_min=1e-2, sigma_max=1e7, tol=1e-8, theta=1e-2,
+                        delta=8, alpha=0.01, tolgradnorm=1e-8, TR_maxinner=20, TR_maxiter=4, tau1=0.1, tau2=1,
+                        line_search=1)       # ManiDSDP.m:10-25
+DATA_FIELDS["dual"] = ("X", "y", "S", "w", "gap", "pinf", "dinf", "gradnorm", "time", "status")   # :125-133
+
+
+def ManiDSDP(A, b, c, K, options=None, verbose=True, rng=None):
+    """``[X, obj, data] = ManiDSDP(A, b, c, K, options)`` (reference src/dual/ManiDSDP.m:7): the dual approach
+    ``sup <C, X> + <cf, w>  s.t.  A(X) + B(w) = b, X psd`` with S = Y Y' on the Euclidean factor Y (n x p).  ``A`` is
+    m x (K['f'] + K['s']^2) -- free columns first -- and ``c`` has K['f'] + K['s']^2 entries; ``options['dAAt']`` as in
+    the reference (default diag(A A') of the PSD part).  The Riemannian subproblem (costgrad / hess :162-177), the line
+    search (:141-160) and the outer step (:66-77) run on the device; the multiplier matrix x never leaves it.
+    Returns (X, obj, data); ``data['Y']`` is the factor of S."""
+    with _host_threads():
+        return _dual_impl(A, b, c, K, options, verbose, rng)
+
+
+def _dual_impl(A, b, c, K, options, verbose, rng):
+    o = dict(options or {})
+    for k, v in DEFAULTS["dual"].items():
+        o.setdefault(k, v)
+    n = int(K["s"]); nf = int(K.get("f", 0))
+    b = _dense_vec(b)
+    call = _dense_vec(c)
+    m = b.size
+    rng = rng or np.random.default_rng(0)
+    _say(verbose, "ManiSDP is starting...")                # :28-29
+    _say(verbose, f"SDP size: n = {n}, m = {m}")
+    normc = 1.0 + np.linalg.norm(call)                     # :31
+    Aall = sp.csc_matrix(A)
+    B = Aall[:, :nf]; Apsd = sp.csr_matrix(Aall[:, nf:])   # :32-33
+    cf = call[:nf]; cpsd = call[nf:]                       # :34-35
+    dAAt = o.get("dAAt", None)
+    if dAAt is None:
+        dAAt = np.asarray(Apsd.multiply(Apsd).sum(axis=1)).ravel()      # :37
+    dAAt = _dense_vec(dAAt)
+    # eig(X) (:76) as in ManiDSDP_unitdiag: the host's dense eig up to n = 600, the device escape with the independent
+    # lambda_min check beyond
+    dense_max = int(o.get("dense_eig_max", 600))
+    eig_mode = o.get("eig", "host" if n <= dense_max else "device")
+    p = int(o["p0"])
+    delta = int(o["delta"])
+    h = _lib.Handle.dual(Apsd, b, cpsd, dAAt, B if nf else None, cf, pcap=max(32, p + 2 * delta))
+    topts = _rtr_opts(o)
+    sigma = float(o["sigma0"]); gama = float(o["gama"])
+    w = np.zeros(nf)
+    Y = o.get("Y0", None)
+    if Y is None:                                          # trustregions.m:390-392 -> euclideanfactory rand = randn(n, p)
+        Y = rng.standard_normal((n, p))
+    Y = np.asfortranarray(Y, dtype=np.float64)
+    U = None
+    data = {"status": 0, "hessvecs": 0, "cost_evals": 0, "rejected": 0, "rtr_seconds": 0.0, "eig_seconds": 0.0, "log": [],
+            "g_identity": h.dual_g_identity(), "p_max": p}
+    t0 = time.time()
+    gap0 = pinf0 = dinf0 = None
+    obj = gap = pinf = dinf = gradnorm = eta = None
+    Y_eval = None
+    certified = True
+    try:
+        for it in range(1, int(o["ADMM_maxiter"]) + 1):    # :59
+            h.dual_set_penalty(sigma, w)
+            h.set_point(Y)
+            if U is not None:
+                _line_search(h, U)                         # :61-63, 150-160 (Y + alpha*U, no normalisation)
+            st = h.rtr(topts)                              # :64
+            data["rtr_seconds"] += st.seconds
+            data["hessvecs"] += st.hessvecs; data["cost_evals"] += st.cost_evals; data["rejected"] += st.rejected
+            gradnorm = st.gradnorm                         # :65
+            Y = h.get_point()
+            Y_eval = Y
+            by, cex, as2, Af, _ = h.dual_outer_step()      # :66-77 (x updated on the device, X = mat(x + bA) kept there)
+            pinf = (math.sqrt(as2) + float(np.linalg.norm(Af))) / normc      # :71
+            w = w - sigma * Af                             # :74
+            obj = cex + float(cf @ w)                      # :77
+            t1 = time.time()
+            certified = True
+            if eig_mode == "host":
+                Xd = h.get_dual_slack()
+                dX, vX = np.linalg.eigh(0.5 * (Xd + Xd.T)) # :76
+                lam_min, lam_max = float(dX[0]), float(dX[-1])
+                nneg = int(np.sum(dX < 0))
+            else:
+                lam, vX, lam_max, _, certified = _device_escape(
+                    h, lambda tol, maxit: h.escape_eigs_dual(delta, tol=tol, maxit=maxit), o, data, 1e-10, 20000)
+                lam_min = float(lam[0])
+                nneg = int(np.sum(lam < 0))
+            dinf = max(0.0, -lam_min) / (1.0 + abs(lam_max))     # :78
+            if eig_mode != "host" and certified and (dinf < o["tol"] or it == int(o["ADMM_maxiter"])):
+                lam_v, v_v, lmax_v, certified = _verify_lambda_min(
+                    h, lambda tol, maxit: h.escape_eigs_dual(1, tol=tol, maxit=maxit), o, data, 1e-10, 20000, dense_n=n)
+                dinf_v = max(0.0, -lam_v) / (1.0 + abs(lmax_v))
+                if dinf_v >= o["tol"] > dinf:
+                    vX = np.hstack([v_v, vX[:, :max(delta - 1, 0)]])
+                    nneg = max(nneg, 1)
+                dinf = dinf_v
+            data["eig_seconds"] += time.time() - t1
+            gap = abs(obj - by) / (1.0 + abs(obj) + abs(by))     # :79
+            if _RANK_CUT_SVD:
+                _, e, Qt = np.linalg.svd(Y, full_matrices=False); Q = Qt.T
+            else:
+                Q, e, _ = _thin_svd_rank(Y, float(o["theta"]))
+            r = int(np.sum(e > float(o["theta"]) * e[0]))  # :80-86 (strict)
+            _say(verbose, "Iter %d, obj:%0.8f, gap:%0.1e, pinf:%0.1e, dinf:%0.1e, gradnorm:%0.1e, r:%d, p:%d, sigma:%0.3f, time:%0.2fs"
+                 % (it, obj, gap, pinf, dinf, gradnorm, r, p, sigma, time.time() - t0))
+            data["log"].append((obj, gap, pinf, dinf, gradnorm, r, p, sigma))
+            eta = max(gap, pinf, dinf)                     # :89
+            data["iters"] = it
+            if eta < o["tol"] and certified:
+                _say(verbose, "Optimality is reached!")
+                break
+            if it % 20 == 0:                               # :94-104
+                if it > 50 and gap > gap0 and pinf > pinf0 and dinf > dinf0:
+                    data["status"] = 2
+                    _say(verbose, "Slow progress!")
+                    break
+                gap0, pinf0, dinf0 = gap, pinf, dinf
+            if r <= p - 1:                                 # :105-108: Y = V(:,1:r)*diag(e(1:r))
+                Y = _rank_cut(Y, Q, e, r)
+                p = r
+            nne = min(nneg, delta)                         # :109 (no lower bound)
+            if o["line_search"] == 1:
+                U = np.hstack([np.zeros((n, p)), vX[:, :nne]])   # :111
+            p = p + nne
+            data["p_max"] = max(data["p_max"], p)
+            if o["line_search"] == 1:
+                Y = np.hstack([Y, np.zeros((n, nne))])     # :115
+            else:
+                Y = np.hstack([Y, o["alpha"] * vX[:, :nne]])     # :117
+            Y = np.asfortranarray(Y)
+            if pinf < o["tau1"] * gradnorm:                # :119-123
+                sigma = max(sigma / gama, float(o["sigma_min"]))
+            elif pinf > o["tau2"] * gradnorm:
+                sigma = min(sigma * gama, float(o["sigma_max"]))
+        X = h.get_dual_slack() if obj is not None else None
+        y = h.dual_get_y() if obj is not None else None
+    finally:
+        h.close()
+    data.update({"X": X, "y": y, "S": (Y_eval @ Y_eval.T if Y_eval is not None and n <= int(o.get("dense_X_max", 4000)) else None),
+                 "w": w, "gap": gap, "pinf": pinf, "dinf": dinf, "gradnorm": gradnorm, "time": time.time() - t0,
+                 "Y": Y_eval, "sigma": sigma})
+    if data["status"] == 0 and (eta is None or eta > o["tol"] or not certified):
+        data["status"] = 1
+        _say(verbose, "Iteration maximum is reached!")
+    _say(verbose, "ManiDSDP: optimum = %0.8f, time = %0.2fs" % (obj, time.time() - t0))   # :139
+    return X, obj, data

@@ -53,6 +53,7 @@ typedef struct msdp_handle_s* msdp_handle;
 #define MSDP_KIND_MULTIBLOCK   5   /* src/primal/ManiSDP_multiblock.m (product manifold) */
 #define MSDP_KIND_DUAL_UNITDIAG 6  /* src/dual/ManiDSDP_unitdiag.m (dual approach, diag(S) = 1) */
 #define MSDP_KIND_DUAL         7   /* src/dual/ManiDSDP.m (dual approach, Euclidean factor of S) */
+#define MSDP_KIND_DUAL_MULTIBLOCK 8 /* src/dual/ManiDSDP_multiblock.m (dual approach, one factor per block) */
 
 /* Options of one Riemannian trust-region solve: the fields ManiSDP sets
  * (ManiSDP_unitdiag.m:44-47) plus Manopt's defaults that are in force
@@ -193,6 +194,20 @@ int msdp_create_dual(int64_t n, int64_t m, const int64_t* at_jc, const int64_t* 
 /* *g_identity = 1 when the setup proved D\A*A' = I (rows of A with pairwise disjoint supports and dAAt equal to their
  * squared norms bit for bit): the Hess-vec then skips the G*a terms of ManiDSDP.m:176.  Dual handles only. */
 int msdp_dual_info(msdp_handle h, int32_t* g_identity);
+/* Multiblock dual approach (src/dual/ManiDSDP_multiblock.m:8-298): nb blocks of orders block_n, S_i = Y_i'Y_i with unit diagonal
+ * on the first nob blocks (oblique rows) and a Euclidean factor on the others.  at_* is the PSD part of A transposed,
+ * (sum n_i^2) x m, its rows the concatenated column-major vecs of the blocks (the layout of msdp_create_multiblock); c is the
+ * PSD cost in that layout; dAAt, b, nf, B (b_*), cf as for msdp_create_dual (nf = 0: no free part).  The factor crosses the
+ * boundary as msdp_create_multiblock's one zero-padded array (row r of the direct sum = column r of its block's Y_i, p values).
+ * The handle takes msdp_dual_set_penalty, msdp_dual_get_y, msdp_rtr, the single-operator and line-search calls,
+ * msdp_get_dual_slack_block and msdp_block_eigs (they read the blocks X_i).  msdp_dual_outer_step performs :86-124: scal[0] =
+ * b'y, scal[1] = <c, x + bA>, scal[2] = |As|^2, Af = B'y - cf, z = the diagonal multipliers of the first nob blocks (their rows
+ * in order; may be NULL when nob = 0), X_i = mat(x + bA)_i - diag(z_i) left on the device.  msdp_get_dual_slack gives
+ * MSDP_EUNSUPPORTED; a factor wider than 128 columns gives MSDP_EUNSUPPORTED. */
+int msdp_create_dual_multiblock(int32_t nb, const int64_t* block_n, int32_t nob, int64_t m, const int64_t* at_jc,
+                                const int64_t* at_ir, const double* at_pr, const double* dAAt, const double* b, const double* c,
+                                int32_t nf, const int64_t* b_jc, const int64_t* b_ir, const double* b_pr, const double* cf,
+                                int32_t pcap, msdp_handle* out);
 
 int msdp_destroy(msdp_handle h);
 /* The library keeps ONE device allocation beyond the life of the handles: the Lanczos workspace of the escape (up to 24 GB for

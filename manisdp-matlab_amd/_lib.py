@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libmanisdp_hip.so")
 
 KIND_ONLYUNITDIAG, KIND_UNITDIAG, KIND_UNITTRACE, KIND_GENERIC, KIND_MULTIBLOCK, KIND_DUAL_UNITDIAG, KIND_DUAL = 1, 2, 3, 4, 5, 6, 7
+KIND_DUAL_MULTIBLOCK = 8
 
 
 class RtrOpts(C.Structure):
@@ -107,6 +108,8 @@ SIGNATURES = {
                                             _dp, C.c_int32, C.POINTER(C.c_void_p)]),
     "msdp_create_dual": (C.c_int, [C.c_int64, C.c_int64, _i64p, _i64p, _dp, _dp, _dp, _dp, C.c_int32, _i64p, _i64p, _dp,
                                    _dp, C.c_int32, C.POINTER(C.c_void_p)]),
+    "msdp_create_dual_multiblock": (C.c_int, [C.c_int32, _i64p, C.c_int32, C.c_int64, _i64p, _i64p, _dp, _dp, _dp, _dp, C.c_int32,
+                                              _i64p, _i64p, _dp, _dp, C.c_int32, C.POINTER(C.c_void_p)]),
     "msdp_dual_info": (C.c_int, [C.c_void_p, _P(C.c_int32)]),
     "msdp_dual_set_penalty": (C.c_int, [C.c_void_p, C.c_double, _dp]),
     "msdp_dual_outer_step": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
@@ -333,6 +336,44 @@ class Handle:
         hd.nf = nf
         return hd
 
+    @classmethod
+    def dual_multiblock(cls, A, b, c, dAAt, block_n, nob, B=None, cf=None, pcap=32):
+        """Multiblock dual approach (ManiDSDP_multiblock.m): ``A`` is the m x sum(n_i^2) PSD part (rows = the concatenated
+        column-major vecs of the blocks), ``c`` its cost, ``B`` / ``cf`` the free part, ``dAAt = diag(A A')``; S_i = Y_i Y_i'
+        with unit diagonal on the first ``nob`` blocks.  The factor is one (N, p) array, N = sum n_i, zero beyond each block's
+        own width (as :meth:`multiblock`)."""
+        import scipy.sparse as sp
+        lib = load()
+        out = C.c_void_p()
+        Atc = sp.csc_matrix(sp.csr_matrix(A).T)
+        Atc.sort_indices()
+        jc = np.ascontiguousarray(Atc.indptr, dtype=np.int64)
+        ir = np.ascontiguousarray(Atc.indices, dtype=np.int64)
+        pr = np.ascontiguousarray(Atc.data, dtype=np.float64)
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        c = np.ascontiguousarray(c, dtype=np.float64)
+        d = np.ascontiguousarray(dAAt, dtype=np.float64)
+        bn = np.ascontiguousarray(block_n, dtype=np.int64)
+        nf = 0 if B is None else int(B.shape[1])
+        if nf:
+            Bc = sp.csc_matrix(B)
+            Bc.sort_indices()
+            bjc = np.ascontiguousarray(Bc.indptr, dtype=np.int64)
+            bir = np.ascontiguousarray(Bc.indices, dtype=np.int64)
+            bpr = np.ascontiguousarray(Bc.data, dtype=np.float64)
+            cfv = np.ascontiguousarray(cf, dtype=np.float64)
+            args = (bjc.ctypes.data_as(_i64p), bir.ctypes.data_as(_i64p), _dptr(bpr), _dptr(cfv))
+        else:
+            args = (None, None, None, None)
+        _check(lib.msdp_create_dual_multiblock(len(bn), bn.ctypes.data_as(_i64p), int(nob), Atc.shape[1], jc.ctypes.data_as(_i64p),
+                                               ir.ctypes.data_as(_i64p), _dptr(pr), _dptr(d), _dptr(b), _dptr(c), nf, *args, pcap,
+                                               C.byref(out)))
+        hd = cls(out.value, KIND_DUAL_MULTIBLOCK, int(bn.sum()))
+        hd.m = Atc.shape[1]
+        hd.nf = nf
+        hd.zrows = int(bn[:int(nob)].sum())
+        return hd
+
     def dual_set_penalty(self, sigma, w=None):
         w = np.ascontiguousarray(w if w is not None else np.zeros(max(self.nf, 1)), dtype=np.float64)
         _check(self._lib.msdp_dual_set_penalty(self._h, float(sigma), _dptr(w)))
@@ -343,7 +384,11 @@ class Handle:
         scal = np.zeros(3)
         Af = np.zeros(max(self.nf, 1))
         z = np.zeros(self.n) if self.kind == KIND_DUAL_UNITDIAG else None
+        if self.kind == KIND_DUAL_MULTIBLOCK:
+            z = np.zeros(max(self.zrows, 1))            # the rows of the first nob blocks (ManiDSDP_multiblock.m:115-118)
         _check(self._lib.msdp_dual_outer_step(self._h, _dptr(scal), _dptr(Af), _dptr(z) if z is not None else None))
+        if self.kind == KIND_DUAL_MULTIBLOCK:
+            z = z[:self.zrows]
         return float(scal[0]), float(scal[1]), float(scal[2]), Af[:self.nf], z
 
     def dual_g_identity(self):

@@ -2361,6 +2361,14 @@ struct DualState {
     double* R = nullptr;            // bA - sigma*As                     (n x nS)
     double* v = nullptr;            // the m-vector of the current adjoint
     double* tB = nullptr;           // B'a of the current Hess-vec        (nf)
+    // multiblock kind (MSDP_KIND_DUAL_MULTIBLOCK): every n x nS operand above is the per-block storage of BlockedDev instead,
+    // G2 / M1 hold one ld x ld Gram matrix per block
+    bool blocked = false;
+    int64_t tot = 0;                // entries of one operand: n * nS, or sum n_i * nS_i
+    int nb = 1;
+    const int* blk_r0 = nullptr;    // nb + 1: first row of every block
+    const int* rowblk = nullptr;    // N: block of every row
+    int64_t zrows = 0;              // rows of the first nob (unit-diagonal) blocks: the z of msdp_dual_outer_step
 };
 static void msdp_dual_release(DualState* ds) { delete ds; }
 #define DUAL_PP_BLOCKS 64
@@ -2559,6 +2567,77 @@ __global__ __launch_bounds__(MSDP_BLOCK) void k_dual_outer(Dev d, int nS, double
     msdp_put_partials3(d.P, P_S2, pc, P_S3, pa, -1, 0.0, sh);
 }
 
+// ------------------------------------------------------------------ dual, multiblock (MSDP_KIND_DUAL_MULTIBLOCK)
+// src/dual/ManiDSDP_multiblock.m: S_i = Y_i'Y_i per block, the first nob blocks unit-diagonal (oblique rows), the others
+// Euclidean (the primal multiblock kind's rowfree flag).  All operands live in the per-block storage of BlockedDev (memory and
+// work ~ sum n_i^2).  nob == nb runs the unit-diagonal dual kind's closures (tt = bA - sigma*As, :257-258; tYU of :282-283),
+// nob < nb the generic kind's (tt with iAB*Af and A'(iA'*As), :259-260; tYU of :284-286) -- on the blocks: S by k_block_gram,
+// the dense products by k_block_contract (affine_gemm), the p_i x p_i Grams of 2*sigma*Y_i(T_i + T_i') per block in one launch
+// (k_bpp_gram / k_bpp_apply).  No launch depends on nb.
+// per-block Gram out_b = Xa_b' * Xb_b (ld x ld) of the rows of block b: grid (nb, chunks of the ld x ld entries)
+__global__ __launch_bounds__(256) void k_bpp_gram(const int* __restrict__ blk_r0, int ld, const double* __restrict__ Xa,
+                                                  const double* __restrict__ Xb, double* __restrict__ out, const int* skip_flag, int skip_when) {
+    if (skip_flag && *skip_flag == skip_when) return;
+    const int b = blockIdx.x;
+    const int r0 = blk_r0[b], r1 = blk_r0[b + 1];
+    double* __restrict__ ob = out + (int64_t)b * ld * ld;
+    for (int e = blockIdx.y * blockDim.x + threadIdx.x; e < ld * ld; e += gridDim.y * blockDim.x) {
+        const int a = e / ld, c = e - a * ld;
+        double acc = 0.0;
+        for (int k = r0; k < r1; ++k) acc = fma(Xa[(int64_t)k * ld + a], Xb[(int64_t)k * ld + c], acc);
+        ob[e] = acc;
+    }
+}
+// out(i,:) = coef * (Y(i,:)*M1_b + U(i,:)*G2_b), b = the block of row i: the 2*sigma*Y_i(T_i + T_i') term, one more slab
+__global__ void k_bpp_apply(int n, int ld, const int* __restrict__ rowblk, const double* __restrict__ Y, const double* __restrict__ U,
+                            const double* __restrict__ M1, const double* __restrict__ G2, double coef, double* __restrict__ out,
+                            const int* skip_flag, int skip_when) {
+    if (skip_flag && *skip_flag == skip_when) return;
+    const int64_t tot = (int64_t)n * ld;
+    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < tot; e += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = e / ld; const int c = (int)(e - i * ld);
+        const int64_t bo = (int64_t)rowblk[i] * ld * ld;
+        double acc = 0.0;
+        for (int a = 0; a < ld; ++a) acc = fma(Y[i * ld + a], M1[bo + a * ld + c], fma(U[i * ld + a], G2[bo + a * ld + c], acc));
+        out[e] = coef * acc;
+    }
+}
+// Outer step :86-124 after the cost state at Y, one wave per row of the direct sum.  Xd holds tt (:257-260) with the multipliers
+// of the solve; Asx = As - x/sigma (generic form: in Sg; unit form: (bA - tt)/sigma); Sf = S.  x <- tt - bA (both forms of
+// :102-106); rows of the unit-diagonal blocks: z_r = sum_j S_rj X_rj, X_rr -= z_r (:115-118); z = 0 on the Euclidean rows.
+// Partial sums of <C, X> -> P_S2 and |As|^2 -> P_S3   (grid d.G)
+__global__ __launch_bounds__(MSDP_BLOCK) void k_dmb_outer(Dev d, BlockedDev bd, double* __restrict__ Xd, const double* __restrict__ Sg,
+                                                          const double* __restrict__ Sf, double* __restrict__ x, const double* __restrict__ bA,
+                                                          const double* __restrict__ C, double sigma, int generic, double* __restrict__ z) {
+    __shared__ double sh[3 * MSDP_WAVES];
+    int lo, hi;
+    msdp_chunk_rows(d.n_loc, d.G, lo, hi);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double pc = 0.0, pa = 0.0;
+    for (int row = lo + wave; row < hi; row += MSDP_WAVES) {
+        const int64_t o = bd.rbase[row];
+        const int len = bd.rhi[row] - bd.rlo[row], dc = row - bd.rlo[row];
+        double zr = 0.0, exd = 0.0;
+        for (int j = lane; j < len; j += 64) {
+            const double X = Xd[o + j], xo = x[o + j], ba = bA[o + j];
+            const double asx = generic ? Sg[o + j] : (ba - X) / sigma;
+            const double as = asx + xo / sigma;
+            x[o + j] = X - ba;
+            zr = fma(Sf[o + j], X, zr);
+            pc = fma(C[o + j], X, pc);
+            pa = fma(as, as, pa);
+            if (j == dc) exd = X;
+        }
+        zr = msdp_wave_sum(zr);
+        const bool ob = !(d.rowfree && d.rowfree[row]);
+        if (lane == (dc & 63)) {
+            if (ob) Xd[o + dc] = exd - zr;
+            z[row] = ob ? zr : 0.0;
+        }
+    }
+    msdp_put_partials3(d.P, P_S2, pc, P_S3, pa, -1, 0.0, sh);
+}
+
 static int dgen_rows_grid(int64_t m) {
     int64_t g = (m + 3) / 4;                               // four waves (rows) per workgroup
     if (g > 4096) g = 4096;
@@ -2566,6 +2645,12 @@ static int dgen_rows_grid(int64_t m) {
 }
 static int dual_pp_gram(msdp_handle h, DualState* ds, const double* Xa, const double* Xb, double* out, const int* flag, int when) {
     const Dev& d = h->d;
+    if (ds->blocked) {                                   // one ld x ld Gram per block, all blocks in one launch
+        const int gy = std::max(1, std::min(64, (d.ld * d.ld + 255) / 256));
+        hipLaunchKernelGGL(k_bpp_gram, dim3(ds->nb, gy), dim3(256), 0, h->stream, ds->blk_r0, d.ld, Xa, Xb, out, flag, when);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
     hipLaunchKernelGGL(k_pp_gram_part, dim3(DUAL_PP_BLOCKS), dim3(256), 0, h->stream, d.n, d.ld, Xa, Xb, ds->pp_part, flag, when);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_pp_gram_sum, dim3((d.ld * d.ld + 255) / 256), dim3(256), 0, h->stream, d.ld, DUAL_PP_BLOCKS,
@@ -2594,12 +2679,16 @@ static int dual_cost_state(msdp_handle h, AffineState* st, const double* Ys, dou
                            (const double*)ds->wf, sigma, ds->Af, flag, when);
         HIPCHK(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_gram_mfma, dim3((a.nS + 63) / 64, (a.n + 63) / 64), dim3(512), 0, h->stream, a.n, a.nS, a.ld, Ys, Ys, ds->Sg, flag, when, 0);
+    if (ds->blocked)
+        hipLaunchKernelGGL(k_block_gram, dim3((st->blk->ntile + 3) / 4), dim3(256), 0, h->stream, *st->blk, Ys, Ys, a.ld, ds->Sg, flag, when);
+    else
+        hipLaunchKernelGGL(k_gram_mfma, dim3((a.nS + 63) / 64, (a.n + 63) / 64), dim3(512), 0, h->stream, a.n, a.nS, a.ld, Ys, Ys, ds->Sg, flag, when, 0);
     HIPCHK(hipGetLastError());
     if (ds->generic) {
         // Q = (C - x/sigma) + A'y; As = Q - S (into Sg), R = bA - sigma*As; v = sigma*D\(A*As + B*Af); X = R + A'v
         if ((rc = launch_adjoint(h, a, (const double*)ds->T, (const double*)a.w, 1.0, Xout, flag, when, false))) return rc;
-        hipLaunchKernelGGL(k_dgen_as, dim3(MSDP_MAX_GRID), dim3(256), 0, h->stream, (int64_t)a.n * a.nS, a.n, a.nS, (const double*)Xout,
+        // (per-block storage: pad columns are zero in every operand, so no column test -- n = nS = 1)
+        hipLaunchKernelGGL(k_dgen_as, dim3(MSDP_MAX_GRID), dim3(256), 0, h->stream, ds->tot, ds->blocked ? 1 : a.n, ds->blocked ? 1 : a.nS, (const double*)Xout,
                            ds->Sg, (const double*)ds->bA, sigma, ds->R, d.P, flag, when);
         HIPCHK(hipGetLastError());
         hipLaunchKernelGGL(k_dgen_rows, dim3(dgen_rows_grid(a.m)), dim3(256), 0, h->stream, a.m, ds->arp, ds->apos, ds->aval,
@@ -2609,7 +2698,7 @@ static int dual_cost_state(msdp_handle h, AffineState* st, const double* Ys, dou
         if ((rc = launch_adjoint(h, a, (const double*)ds->R, (const double*)ds->v, 1.0, Xout, flag, when, false))) return rc;
     } else {
         if ((rc = launch_adjoint(h, a, (const double*)ds->T, (const double*)a.w, -sigma, Xout, flag, when, false))) return rc;
-        hipLaunchKernelGGL(k_dual_finish_X, dim3(MSDP_MAX_GRID), dim3(256), 0, h->stream, (int64_t)a.n * a.nS, Xout, (const double*)ds->Sg,
+        hipLaunchKernelGGL(k_dual_finish_X, dim3(MSDP_MAX_GRID), dim3(256), 0, h->stream, ds->tot, Xout, (const double*)ds->Sg,
                            (const double*)ds->bA, sigma, d.P, flag, when);
         HIPCHK(hipGetLastError());
     }
@@ -2629,11 +2718,12 @@ static int dual_costgrad(msdp_handle h, AffineState* st, int slot) {
     // eG = 2*X*Y -> Gr[slot], row dots YeG
     const double* slab; int64_t stride; int SK;
     const double* M[1] = {d.eS[slot]}; const double* X[1] = {Ys}; const double sc[1] = {1.0};
-    if ((rc = msdp_dense_gemm(h, 1, M, X, sc, nullptr, &slab, &stride, &SK))) return rc;
+    if ((rc = affine_gemm(h, 1, M, X, sc, nullptr, &slab, &stride, &SK))) return rc;
     DISPATCH_LPR_A(k_rowdot_slabs, h, d.G, d, Ys, slab, stride, SK, 2.0, d.Gr[slot], d.eG[slot], P_S2);
     HIPCHK(hipGetLastError());
-    if (ds->generic) {
-        // G = 2*X*Y as is (euclideanfactory: no projection, :170)
+    if (ds->generic && !ds->blocked) {
+        // G = 2*X*Y as is (euclideanfactory: no projection, :170); the multiblock kind projects the rows of its unit-diagonal
+        // blocks only (k_obl_grad_finish with rowfree, :265-269)
         hipLaunchKernelGGL(k_sph_grad_finish, dim3(d.G), dim3(MSDP_BLOCK), 0, h->stream, d, slot, st->sigma, (const double*)ds->scal);
     } else {
         DISPATCH_LPR_A(k_obl_grad_finish, h, d.G, d, slot, st->sigma, (const double*)ds->scal);
@@ -2686,15 +2776,19 @@ static int dual_hess(msdp_handle h, AffineState* st) {
     const double* M[2] = {d.eS[cur], d.AyU};
     const double* X[2] = {d.md, d.Y[cur]};
     const double sc[2] = {2.0, cA};
-    if ((rc = msdp_dense_gemm(h, 2, M, X, sc, act, &slab, &stride, &SK))) return rc;
+    if ((rc = affine_gemm(h, 2, M, X, sc, act, &slab, &stride, &SK))) return rc;
     if ((rc = dual_pp_gram(h, ds, d.md, d.Y[cur], ds->M1, act, 0))) return rc;
     double* extra = const_cast<double*>(slab) + (int64_t)SK * stride;
     { int64_t g = ((int64_t)d.n_loc * d.ld + 255) / 256; if (g > 4096) g = 4096;
-      hipLaunchKernelGGL(k_pp_apply, dim3((int)g), dim3(256), 0, h->stream, d.n_loc, d.ld, (const double*)d.Y[cur], (const double*)d.md,
-                         (const double*)ds->M1, (const double*)ds->G2[cur], 2.0 * sigma, extra, act, 0); }
+      if (ds->blocked)
+          hipLaunchKernelGGL(k_bpp_apply, dim3((int)g), dim3(256), 0, h->stream, d.n_loc, d.ld, ds->rowblk, (const double*)d.Y[cur], (const double*)d.md,
+                             (const double*)ds->M1, (const double*)ds->G2[cur], 2.0 * sigma, extra, act, 0);
+      else
+          hipLaunchKernelGGL(k_pp_apply, dim3((int)g), dim3(256), 0, h->stream, d.n_loc, d.ld, (const double*)d.Y[cur], (const double*)d.md,
+                             (const double*)ds->M1, (const double*)ds->G2[cur], 2.0 * sigma, extra, act, 0); }
     HIPCHK(hipGetLastError());
     ++SK;
-    if (ds->generic) return msdp_sphere_hess_raw(h, slab, stride, SK);      // Euclidean epilogue: H as is
+    if (ds->generic && !ds->blocked) return msdp_sphere_hess_raw(h, slab, stride, SK);      // Euclidean epilogue: H as is
     return msdp_dense_hess_epilogue_obl(h, slab, stride, SK);
 }
 
@@ -2725,7 +2819,19 @@ int msdp_dual_setup(msdp_handle h, const int64_t* at_jc, const int64_t* at_ir, c
     DualState* ds = new DualState();
     st->dual = ds;
     ds->nf = nf;
-    std::vector<double> dinv((size_t)m), Ac((size_t)m, 0.0), bA((size_t)n * nS, 0.0);
+    // stored position of column-major vec index r: (r % n, r / n) of the n x nS array, or of its block in the per-block storage
+    ds->blocked = st->blk != nullptr;
+    ds->tot = ds->blocked ? st->blk->etot : (int64_t)n * nS;
+    const int nbk = ds->blocked ? (int)st->blk_n.size() : 1;
+    std::vector<int64_t> e0((size_t)nbk + 1, 0);
+    for (int i = 0; i < nbk; ++i) e0[(size_t)i + 1] = e0[(size_t)i] + (ds->blocked ? (int64_t)st->blk_n[(size_t)i] * st->blk_n[(size_t)i] : (int64_t)n * n);
+    auto spos = [&](int64_t r) -> int64_t {
+        if (!ds->blocked) return (r % n) * nS + r / n;
+        const int i = (int)(std::upper_bound(e0.begin(), e0.end(), r) - e0.begin()) - 1;
+        const int64_t l = r - e0[(size_t)i], bn = st->blk_n[(size_t)i];
+        return st->blk_off[(size_t)i] + (l % bn) * st->blk_ns[(size_t)i] + l / bn;
+    };
+    std::vector<double> dinv((size_t)m), Ac((size_t)m, 0.0), bA((size_t)ds->tot, 0.0);
     for (int64_t k = 0; k < m; ++k) {
         if (!(dAAt[k] > 0.0)) { msdp_set_error("dual kind: dAAt(%lld) = %g is not positive", (long long)k, dAAt[k]); return MSDP_EINVAL; }
         dinv[(size_t)k] = 1.0 / dAAt[k];
@@ -2733,8 +2839,9 @@ int msdp_dual_setup(msdp_handle h, const int64_t* at_jc, const int64_t* at_ir, c
         const double bk = b[k] * dinv[(size_t)k];
         for (int64_t t = at_jc[k]; t < at_jc[k + 1]; ++t) {
             const int64_t r = at_ir[t];                    // column-major vec index i + j*n -> row-major (i, j)
+            if (r < 0 || r >= e0[(size_t)nbk]) { msdp_set_error("dual kind: row index of At out of range"); return MSDP_EINVAL; }
             acc += at_pr[t] * c[r];
-            bA[(size_t)((r % n) * nS + r / n)] += at_pr[t] * bk;       // bA = iA*b (:39)
+            bA[(size_t)spos(r)] += at_pr[t] * bk;          // bA = iA*b (:39)
         }
         Ac[(size_t)k] = acc;
     }
@@ -2752,7 +2859,7 @@ int msdp_dual_setup(msdp_handle h, const int64_t* at_jc, const int64_t* at_ir, c
     }
     if (bir.empty()) { bir.push_back(0); bpr.push_back(0.0); }
     if ((rc = up(h, bjc, &ds->bjc)) || (rc = up(h, bir, &ds->bir)) || (rc = up(h, bpr, &ds->bpr)) || (rc = up(h, cfv, &ds->cf))) return rc;
-    const size_t msz = (size_t)n * nS * sizeof(double);
+    const size_t msz = (size_t)ds->tot * sizeof(double);
     void* p = nullptr;
     double** mats[4] = {&ds->x, &ds->bA, &ds->T, &ds->Sg};
     for (int q = 0; q < 4; ++q) {
@@ -2761,15 +2868,23 @@ int msdp_dual_setup(msdp_handle h, const int64_t* at_jc, const int64_t* at_ir, c
         HIPCHK(hipMemset(p, 0, msz));
     }
     HIPCHK(msdp_memcpy(ds->bA, bA.data(), msz, hipMemcpyHostToDevice));
-    const size_t ppsz = (size_t)DUAL_PP_MAXLD * DUAL_PP_MAXLD * sizeof(double);
+    const size_t ppsz = (size_t)DUAL_PP_MAXLD * DUAL_PP_MAXLD * sizeof(double) * nbk;      // one per block (multiblock kind)
     double** pps[3] = {&ds->G2[0], &ds->G2[1], &ds->M1};
     for (int q = 0; q < 3; ++q) {
         if ((rc = msdp_dev_alloc_bytes(h, &p, ppsz))) return rc;
         *pps[q] = (double*)p;
         HIPCHK(hipMemset(p, 0, ppsz));
     }
-    if ((rc = msdp_dev_alloc_bytes(h, &p, ppsz * DUAL_PP_BLOCKS))) return rc;
-    ds->pp_part = (double*)p;
+    if (!ds->blocked) {
+        if ((rc = msdp_dev_alloc_bytes(h, &p, ppsz * DUAL_PP_BLOCKS))) return rc;
+        ds->pp_part = (double*)p;
+    } else {
+        ds->nb = nbk;
+        std::vector<int> br0((size_t)nbk + 1), rowblk((size_t)n);
+        for (int i = 0; i <= nbk; ++i) br0[(size_t)i] = (int)st->blk_r0[(size_t)i];
+        for (int i = 0; i < nbk; ++i) for (int r = br0[(size_t)i]; r < br0[(size_t)i + 1]; ++r) rowblk[(size_t)r] = i;
+        if ((rc = up(h, br0, &ds->blk_r0)) || (rc = up(h, rowblk, &ds->rowblk))) return rc;
+    }
     const size_t nfb = (size_t)std::max(nf, 1) * sizeof(double);
     if ((rc = msdp_dev_alloc_bytes(h, &p, nfb))) return rc;
     ds->wf = (double*)p; HIPCHK(hipMemset(p, 0, nfb));
@@ -2783,17 +2898,16 @@ int msdp_dual_setup(msdp_handle h, const int64_t* at_jc, const int64_t* at_ir, c
     // A by rows (the columns of At) with row-major positions; G = I check: disjoint supports, dAAt(k) == sum_t A_kt^2 bit for bit
     std::vector<int64_t> arp((size_t)m + 1, 0), apos;
     std::vector<double> aval;
-    std::vector<unsigned char> used((size_t)n * n, 0);
+    std::vector<unsigned char> used((size_t)e0[(size_t)nbk], 0);
     bool gI = true;
     for (int64_t k = 0; k < m; ++k) {
         double ss = 0.0;
         for (int64_t t = at_jc[k]; t < at_jc[k + 1]; ++t) {
             const int64_t r = at_ir[t];
-            if (r < 0 || r >= (int64_t)n * n) { msdp_set_error("dual kind: row index of At out of range"); return MSDP_EINVAL; }
             if (used[(size_t)r]) gI = false;
             used[(size_t)r] = 1;
             ss += at_pr[t] * at_pr[t];
-            apos.push_back((r % n) * nS + r / n);
+            apos.push_back(spos(r));
             aval.push_back(at_pr[t]);
         }
         if (ss != dAAt[k]) gI = false;
@@ -2825,6 +2939,14 @@ int msdp_dual_setup(msdp_handle h, const int64_t* at_jc, const int64_t* at_ir, c
     return 0;
 }
 
+// the rows of the first nob blocks of a multiblock dual handle (the length of its z)
+int msdp_dual_set_zrows(msdp_handle h, int64_t zrows) {
+    AffineState* st = astate(h);
+    if (!st || !st->dual) { msdp_set_error("dual state missing"); return MSDP_ESTATE; }
+    st->dual->zrows = zrows;
+    return 0;
+}
+
 int msdp_dual_g_identity(msdp_handle h) {
     AffineState* st = astate(h);
     return (st && st->dual && st->dual->g_identity) ? 1 : 0;
@@ -2842,7 +2964,7 @@ int msdp_dual_set_penalty_impl(msdp_handle h, double sigma, const double* wf_hos
     }
     st->sigma = sigma;
     h->h_ctl->sigma = sigma;
-    const int64_t tot = (int64_t)st->a.n * st->a.nS;
+    const int64_t tot = ds->tot;
     if (ds->generic)
         hipLaunchKernelGGL(k_dual_T, dim3(2048), dim3(256), 0, h->stream, tot, ds->T, (const double*)ds->bA, (const double*)ds->x,
                            (const double*)h->d.Cd, 0.0, -1.0 / sigma, 1.0);
@@ -2867,6 +2989,34 @@ int msdp_dual_outer_step_impl(msdp_handle h, double* scal_host, double* Af_host,
     const double sigma = st->sigma;
     const double* Ys = d.Y[h->h_ctl->cur];
     int rc;
+    if (ds->blocked) {
+        // ManiDSDP_multiblock.m:86-124: tt of :257-260 at Y with the multipliers of the solve -> d.Sdual; x = tt - bA; z and
+        // X_i - diag(z_i) on the unit-diagonal blocks (k_dmb_outer)
+        if ((rc = dual_check(h, ds))) return rc;
+        if ((rc = dual_cost_state(h, st, Ys, d.Sdual, (const int*)nullptr, 0))) return rc;
+        if (ds->nf > 0) {                                  // Af = B'y - cf (:97)
+            hipLaunchKernelGGL(k_dual_free, dim3(ds->nf), dim3(256), 0, h->stream, ds->bjc, ds->bir, ds->bpr, (const double*)a.w, ds->cf,
+                               (const double*)nullptr, sigma, ds->Af, (const int*)nullptr, 0, (const double*)nullptr);
+            HIPCHK(hipGetLastError());
+        }
+        const double* Sf = ds->Sg;
+        if (ds->generic) {                                 // Sg holds As - x/sigma there: S again, into the spent R
+            hipLaunchKernelGGL(k_block_gram, dim3((st->blk->ntile + 3) / 4), dim3(256), 0, h->stream, *st->blk, Ys, Ys, d.ld, ds->R,
+                               (const int*)nullptr, 0);
+            HIPCHK(hipGetLastError());
+            Sf = ds->R;
+        }
+        hipLaunchKernelGGL(k_dmb_outer, dim3(d.G), dim3(MSDP_BLOCK), 0, h->stream, d, *st->blk, d.Sdual, (const double*)ds->Sg, Sf, ds->x,
+                           (const double*)ds->bA, (const double*)d.Cd, sigma, ds->generic ? 1 : 0, d.W0);
+        HIPCHK(hipGetLastError());
+        if ((rc = msdp_k_sum_to_fwd(h, P_S2, ds->scal + 2)) || (rc = msdp_k_sum_to_fwd(h, P_S3, ds->scal + 3))) return rc;
+        HIPCHK(msdp_memcpy_async(scal_host, ds->scal + 1, 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        if (ds->nf > 0) HIPCHK(msdp_memcpy_async(Af_host, ds->Af, (size_t)ds->nf * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        if (ds->zrows > 0 && z_host) HIPCHK(msdp_memcpy_async(z_host, d.W0, (size_t)ds->zrows * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        ds->T_valid = false;
+        return 0;
+    }
     if (ds->generic) {
         // :66-77: X of :169 at Y with the multipliers of the solve (x, w/sigma in T and wf) -> d.Sdual; then x = X - bA
         if ((rc = dual_check(h, ds))) return rc;

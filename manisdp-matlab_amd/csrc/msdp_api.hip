@@ -291,7 +291,7 @@ void msdp_host_kits_release() {                               // msdp_release_ca
 }
 
 static bool boundary_colmajor(msdp_handle h) { return h->kind == MSDP_KIND_UNITTRACE || h->kind == MSDP_KIND_GENERIC || h->kind == MSDP_KIND_DUAL; }
-static bool dual_kind(msdp_handle h) { return h->kind == MSDP_KIND_DUAL_UNITDIAG || h->kind == MSDP_KIND_DUAL; }
+static bool dual_kind(msdp_handle h) { return h->kind == MSDP_KIND_DUAL_UNITDIAG || h->kind == MSDP_KIND_DUAL || h->kind == MSDP_KIND_DUAL_MULTIBLOCK; }
 
 static int rows_capacity(msdp_handle h) {
     // equal per-rank row count so the all-gather is one uniform RCCL call
@@ -757,6 +757,46 @@ extern "C" int msdp_create_dual(int64_t n, int64_t m, const int64_t* at_jc, cons
     if (rc) return rc;
     h->kind = MSDP_KIND_DUAL;
     if ((rc = msdp_dual_setup(h, at_jc, at_ir, at_pr, b, c, dAAt, nf, b_jc, b_ir, b_pr, cf, true))) { msdp_destroy(h); return rc; }
+    *out = h;
+    return 0;
+}
+
+// src/dual/ManiDSDP_multiblock.m: the blocks of msdp_create_multiblock (per-block storage only, the first nob blocks unit-diagonal:
+// oblique rows, the others Euclidean through the rowfree flag) with the dual data of msdp_create_dual
+int msdp_dual_set_zrows(msdp_handle h, int64_t zrows);       // msdp_affine.hip
+extern "C" int msdp_create_dual_multiblock(int32_t nb, const int64_t* block_n, int32_t nob, int64_t m, const int64_t* at_jc,
+                                           const int64_t* at_ir, const double* at_pr, const double* dAAt, const double* b,
+                                           const double* c, int32_t nf, const int64_t* b_jc, const int64_t* b_ir, const double* b_pr,
+                                           const double* cf, int32_t pcap, msdp_handle* out) {
+    if (nb < 1 || !block_n || nob < 0 || nob > nb) { msdp_set_error("dual_multiblock: bad block description"); return MSDP_EINVAL; }
+    if (!at_jc || !at_ir || !at_pr || !dAAt || !b || !c || m <= 0 || !out) { msdp_set_error("dual_multiblock: null/empty data"); return MSDP_EINVAL; }
+    if (nf < 0 || (nf > 0 && (!b_jc || !b_ir || !b_pr || !cf))) { msdp_set_error("dual_multiblock: bad free part"); return MSDP_EINVAL; }
+    std::vector<int64_t> r0((size_t)nb + 1, 0);
+    for (int i = 0; i < nb; ++i) {
+        if (block_n[i] < 1) { msdp_set_error("dual_multiblock: block %d has order %lld", i, (long long)block_n[i]); return MSDP_EINVAL; }
+        r0[(size_t)i + 1] = r0[(size_t)i] + block_n[i];
+    }
+    const int64_t N = r0[(size_t)nb];
+    if (N > 0x3fffffff) { msdp_set_error("dual_multiblock: total order too large"); return MSDP_EUNSUPPORTED; }
+    msdp_handle h = nullptr;
+    int rc = new_handle(MSDP_KIND_UNITDIAG, N, &h);
+    if (rc) return rc;
+    h->d.costkind = COST_AFFINE;
+    h->d.m = m;
+    if ((rc = alloc_common(h)) || (rc = msdp_affine_setup_blocked(h, nb, block_n, at_jc, at_ir, at_pr, b, c)) ||
+        (rc = msdp_alloc_vectors(h, pcap > 0 ? pcap : 32))) { msdp_destroy(h); return rc; }
+    h->kind = MSDP_KIND_DUAL_MULTIBLOCK;
+    if (nob < nb) {
+        std::vector<unsigned char> rf((size_t)N, 0);
+        for (int64_t a = r0[(size_t)nob]; a < N; ++a) rf[(size_t)a] = 1;
+        unsigned char* drf = nullptr;
+        if ((rc = dev_alloc<unsigned char>(h, &drf, (size_t)N))) { msdp_destroy(h); return rc; }
+        if (msdp_memcpy(drf, rf.data(), (size_t)N, hipMemcpyHostToDevice) != hipSuccess) { msdp_set_error("dual_multiblock: upload failed"); msdp_destroy(h); return MSDP_EHIP; }
+        h->d.rowfree = drf;
+    }
+    // nob == nb: the unit-diagonal dual kind's closures (tt = bA - sigma*As), otherwise the generic kind's
+    if ((rc = msdp_dual_setup(h, at_jc, at_ir, at_pr, b, c, dAAt, nf, b_jc, b_ir, b_pr, cf, nob < nb)) ||
+        (rc = msdp_dual_set_zrows(h, r0[(size_t)nob]))) { msdp_destroy(h); return rc; }
     *out = h;
     return 0;
 }

@@ -17,6 +17,10 @@
 //       manisdp_mex('dual_set_penalty', h, sigma, w)     before every rtr of a dual handle (w: nf x 1)
 //   h = manisdp_mex('create_dual', At, dAAt, b, c, n, B, cf)   generic dual approach (ManiDSDP.m): the arguments of
 //                                                        create_dual_unitdiag, Euclidean n x p factor
+//   h = manisdp_mex('create_dual_multiblock', At, dAAt, b, c, nset, nob, B, cf)   multiblock dual approach
+//                                                        (ManiDSDP_multiblock.m): At = A(:,K.f+1:end)' (sum(n_i^2) x m), the
+//                                                        factor as create_multiblock's; z of dual_outer_step = the rows of the
+//                                                        first nob blocks
 //   [by, cex, as2, Af, z] = manisdp_mex('dual_outer_step', h)   ManiDSDP_unitdiag.m:70-81 (ManiDSDP.m:66-77, z = 0) on the device
 //   y = manisdp_mex('dual_get_y', h)
 //       manisdp_mex('set_multipliers', h, y, sigma)
@@ -254,6 +258,34 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             nf ? (const int64_t*)mxGetJc(B) : nullptr, nf ? (const int64_t*)mxGetIr(B) : nullptr, nf ? mxGetPr(B) : nullptr, cf.data(), 32, &h);
         if (rc) fail(generic ? "create_dual" : "create_dual_unitdiag", rc);
         plhs[0] = wrap_handle(h, generic ? MSDP_KIND_DUAL : MSDP_KIND_DUAL_UNITDIAG, n, m, nf);
+        return;
+    }
+
+    if (cmd == "create_dual_multiblock") {
+        need(nrhs == 9, "h = manisdp_mex('create_dual_multiblock', At, dAAt, b, c, nset, nob, B, cf)");
+        const mxArray* At = prhs[1];
+        if (!mxIsSparse(At)) mexErrMsgIdAndTxt("ManiSDP:hip:arg", "At must be sparse (sum(n_i^2) x m)");
+        const size_t nb = mxGetNumberOfElements(prhs[5]);
+        if (nb < 1) mexErrMsgIdAndTxt("ManiSDP:hip:arg", "nset must list at least one block");
+        std::vector<int64_t> nset(nb);
+        int64_t N = 0, E = 0;
+        for (size_t i = 0; i < nb; ++i) { nset[i] = (int64_t)mxGetPr(prhs[5])[i]; N += nset[i]; E += nset[i] * nset[i]; }
+        if ((int64_t)mxGetM(At) != E) mexErrMsgIdAndTxt("ManiSDP:hip:arg", "At must have sum(n_i^2) rows");
+        const int64_t m = (int64_t)mxGetN(At);
+        if ((int64_t)mxGetNumberOfElements(prhs[2]) != m) mexErrMsgIdAndTxt("ManiSDP:hip:arg", "dAAt must have m entries");
+        const std::vector<double> dAAt = as_dense(prhs[2], (size_t)m);
+        const std::vector<double> b = as_dense(prhs[3], (size_t)m);
+        const std::vector<double> c = as_dense(prhs[4], (size_t)E);
+        const mxArray* B = prhs[7];
+        const int64_t nf = mxIsEmpty(B) ? 0 : (int64_t)mxGetN(B);
+        if (nf > 0 && (!mxIsSparse(B) || (int64_t)mxGetM(B) != m)) mexErrMsgIdAndTxt("ManiSDP:hip:arg", "B must be sparse m x nf");
+        const std::vector<double> cf = as_dense(prhs[8], (size_t)(nf > 0 ? nf : 1));
+        msdp_handle h = nullptr;
+        const int rc = msdp_create_dual_multiblock((int32_t)nb, nset.data(), (int32_t)mxGetScalar(prhs[6]), m, (const int64_t*)mxGetJc(At),
+            (const int64_t*)mxGetIr(At), mxGetPr(At), dAAt.data(), b.data(), c.data(), (int32_t)nf,
+            nf ? (const int64_t*)mxGetJc(B) : nullptr, nf ? (const int64_t*)mxGetIr(B) : nullptr, nf ? mxGetPr(B) : nullptr, cf.data(), 32, &h);
+        if (rc) fail("create_dual_multiblock", rc);
+        plhs[0] = wrap_handle(h, MSDP_KIND_DUAL_MULTIBLOCK, N, m, nf);
         return;
     }
 

@@ -960,6 +960,140 @@ def qsmom_sparse(n, cliques, coe):
     return At, b, c, {"s": mb, "nob": 0}
 
 
+def _sos_sparse_support(cliques, multilinear):
+    """The sorted ``sp`` of bqpsos_sparse.m:10-24 / qssos_sparse.m:66-76: every monomial of degree <= 4 whose variables lie in
+    one clique (multilinear ones only for the BQP), as sorted variable tuples, in ``sortrows`` order of the exponent vectors
+    ``(a_1, ..., a_n)`` ascending.  Two sorted tuples compare like their exponent vectors when every variable is negated
+    (at the first differing place the tuple with the smaller variable has the larger exponent there; a proper prefix is the
+    smaller vector), so the key is ``tuple(-v)``."""
+    import itertools
+    mons = set()
+    for I in cliques:
+        for d in range(5):
+            mons.update(itertools.combinations(I, d) if multilinear else itertools.combinations_with_replacement(I, d))
+    return sorted(mons, key=lambda mo: tuple(-v for v in mo))
+
+
+def bqpsos_sparse_coe(cliques, coe):
+    """The coefficients of :func:`bqp_sparse_monomials` (the order of :func:`bqpmom_sparse`) as the ``coe`` of
+    :func:`bqpsos_sparse`, indexed like the sorted ``sp`` of bqpsos_sparse.m (zero on the constant and on degrees 3-4)."""
+    spl = _sos_sparse_support(cliques, True)
+    index = {mo: k for k, mo in enumerate(spl)}
+    out = np.zeros(len(spl))
+    for mo, v in zip(bqp_sparse_monomials(cliques), np.asarray(coe, dtype=np.float64).ravel()):
+        out[index[mo]] = v
+    return out
+
+
+def qssos_sparse_coe(cliques, coe):
+    """The coefficients of :func:`quartic_sparse_monomials` (the order of :func:`qsmom_sparse`) as the ``coe`` of
+    :func:`qssos_sparse`, indexed like the sorted ``sp`` of qssos_sparse.m."""
+    spl = _sos_sparse_support(cliques, False)
+    index = {mo: k for k, mo in enumerate(spl)}
+    out = np.zeros(len(spl))
+    for mo, v in zip(quartic_sparse_monomials(cliques), np.asarray(coe, dtype=np.float64).ravel()):
+        out[index[mo]] = v
+    return out
+
+
+def bqpsos_sparse(n, cliques, coe):
+    """Second-order SOS relaxation of a BQP with correlative sparsity (the dual side of :func:`bqpmom_sparse`), what
+    src/basicfunction/bqpsos_sparse.m:7-56 builds, written from the definition: find the largest lambda with
+    ``f(x) - lambda = sum_k m_k(x)' S_k m_k(x)`` modulo ``x_i^2 = 1``, S_k psd, ``m_k`` the multilinear monomials of degree
+    <= 2 in clique k (``[1, x_a, x_a x_b]``, pairs ordered by their larger variable).  Entry (i, j) of block k carries the
+    monomial ``m_i m_j`` reduced by ``x^2 = 1`` (the symmetric difference of the variable sets); the diagonal carries 1.
+
+    ``coe`` holds the coefficients of f indexed like the sorted ``sp`` (:func:`bqpsos_sparse_coe` maps those of
+    :func:`bqp_sparse_monomials`).  Returns ``(A, b, c, K, dAAt)``: A is lsp x (1 + sum mb_k^2), column 0 the free lambda
+    (row 0: the constant monomial), then the concatenated column-major vecs of the blocks; all values 1; ``b = coe``,
+    ``c = e_1``, ``K = {'f': 1, 's': mb}``, ``dAAt`` = diag(A_psd A_psd') accumulated as :29-30, :45."""
+    spl = _sos_sparse_support(cliques, True)
+    lsp = len(spl)
+    index = {mo: k for k, mo in enumerate(spl)}
+    coe = np.asarray(coe, dtype=np.float64).ravel()
+    if coe.size != lsp:
+        raise ValueError("bqpsos_sparse: coe must have lsp = %d entries" % lsp)
+    bases = []
+    for I in cliques:
+        I = sorted(I)
+        bs = [()] + [(a,) for a in I]
+        for jb in range(1, len(I)):
+            for ia in range(jb):
+                bs.append((I[ia], I[jb]))
+        bases.append(bs)
+    mb = [len(bs) for bs in bases]
+    rows, cols = [0], [0]
+    dAAt = np.zeros(lsp)
+    dAAt[0] = sum(mb)
+    ss = 1
+    for k, bs in enumerate(bases):
+        m_ = mb[k]
+        for i in range(m_):                                # the diagonal: constant row
+            rows.append(0); cols.append(ss + i * m_ + i)
+        for i in range(m_):
+            for j in range(i + 1, m_):
+                loc = index[tuple(sorted(set(bs[i]).symmetric_difference(bs[j])))]
+                rows += [loc, loc]
+                cols += [ss + i * m_ + j, ss + j * m_ + i]
+                dAAt[loc] += 2
+        ss += m_ * m_
+    A = sp.csr_matrix((np.ones(len(rows)), (rows, cols)), shape=(lsp, ss))
+    c = np.zeros(ss)
+    c[0] = 1.0
+    return A, coe.copy(), c, {"f": 1, "s": mb}, dAAt
+
+
+def qssos_sparse(n, cliques, coe):
+    """Second-order SOS relaxation of a quartic with correlative sparsity on the clique spheres ``|x_{I_k}| = 1`` (the dual
+    side of :func:`qsmom_sparse`), what src/basicfunction/qssos_sparse.m:7-74 builds, written from the definition: find the
+    largest lambda with ``f(x) - lambda = sum_k [h_k(x) (|x_{I_k}|^2 - 1) + m_k(x)' S_k m_k(x)]``, ``m_k`` all monomials of
+    degree <= 2 in clique k (``[1, x_a, x_a x_b (a <= b, ordered by b)]``), ``h_k`` with the same support, S_k psd.
+
+    ``coe`` is indexed like the sorted ``sp`` (:func:`qssos_sparse_coe`).  Returns ``(A, b, c, K, dAAt)``: columns lambda,
+    the ``sum(mb)`` coefficients of the h_k clique by clique, then the concatenated column-major vecs of the blocks;
+    ``K = {'f': sum(mb) + 1, 's': mb}``, ``b = coe``, ``c = e_1``, ``dAAt`` = diag(A_psd A_psd') accumulated as :112-118."""
+    spl = _sos_sparse_support(cliques, False)
+    lsp = len(spl)
+    index = {mo: k for k, mo in enumerate(spl)}
+    coe = np.asarray(coe, dtype=np.float64).ravel()
+    if coe.size != lsp:
+        raise ValueError("qssos_sparse: coe must have lsp = %d entries" % lsp)
+    bases = []
+    for I in cliques:
+        I = sorted(I)
+        bs = [()] + [(a,) for a in I]
+        for jb in range(len(I)):
+            for ia in range(jb + 1):
+                bs.append((I[ia], I[jb]))
+        bases.append(bs)
+    mb = [len(bs) for bs in bases]
+    rows, cols, vals = [0], [0], [1.0]
+    col = 1
+    for k, I in enumerate(cliques):                        # h_k(x) (|x_{I_k}|^2 - 1)
+        for i in range(mb[k]):
+            for a in sorted(I):
+                rows.append(index[tuple(sorted(bases[k][i] + (a, a)))]); cols.append(col); vals.append(1.0)
+            rows.append(index[bases[k][i]]); cols.append(col); vals.append(-1.0)
+            col += 1
+    dAAt = np.zeros(lsp)
+    for k, bs in enumerate(bases):                         # m_k(x)' S_k m_k(x)
+        m_ = mb[k]
+        for i in range(m_):
+            for j in range(i, m_):
+                loc = index[tuple(sorted(bs[i] + bs[j]))]
+                rows.append(loc); cols.append(col + i * m_ + j); vals.append(1.0)
+                if j > i:
+                    rows.append(loc); cols.append(col + j * m_ + i); vals.append(1.0)
+                    dAAt[loc] += 2
+                else:
+                    dAAt[loc] += 1
+        col += m_ * m_
+    A = sp.csr_matrix((vals, (rows, cols)), shape=(lsp, col))
+    c = np.zeros(col)
+    c[0] = 1.0
+    return A, coe.copy(), c, {"f": sum(mb) + 1, "s": mb}, dAAt
+
+
 def matrix_completion(p, q, k, m=None, seed=3):
     """Nuclear-norm matrix completion as an SDP for the generic ``ManiSDP`` (reference example/example_matrixcompletion.m:8-41):
     ``M = randn(p,k) randn(k,q)``, ``m`` sampled positions (default ``400 (p+q)`` draws with replacement, duplicates removed,

@@ -1117,3 +1117,171 @@ def _dual_impl(A, b, c, K, options, verbose, rng):
         _say(verbose, "Iteration maximum is reached!")
     _say(verbose, "ManiDSDP: optimum = %0.8f, time = %0.2fs" % (obj, time.time() - t0))   # :139
     return X, obj, data
+
+
+# ===================================================================== dual approach, multiblock
+DEFAULTS["dual_multiblock"] = dict(min_facsize=2, ADMM_maxiter=1000, gama=2, sigma0=1e-1, sigma_min=1e-2, sigma_max=1e7, tol=1e-8,
+                                   theta=1e-2, delta=8, alpha=0.2, tolgradnorm=1e-8, TR_maxinner=20, TR_maxiter=4, tau1=1e1,
+                                   tau2=1e1, line_search=1)       # ManiDSDP_multiblock.m:12-28 (+ p0 = ones, :13)
+DATA_FIELDS["dual_multiblock"] = ("X", "y", "S", "w", "gap", "pinf", "dinf", "gradnorm", "time", "status")   # :188-197
+
+
+def ManiDSDP_multiblock(A, b, c, K, options=None, verbose=True, rng=None):
+    """``[X, obj, data] = ManiDSDP_multiblock(A, b, c, K, options)`` (reference src/dual/ManiDSDP_multiblock.m:8): the dual
+    approach ``sup <C, X> + <cf, w>  s.t.  A(X) + B(w) = b, X_i psd`` for block-diagonal X of orders ``K['s']``, the dual
+    slacks S_i = Y_i Y_i' with unit diagonal on the first ``K['nob']`` blocks.  ``A`` is m x (K['f'] + sum n_i^2) -- free
+    columns first, then the concatenated column-major vecs of the blocks -- and ``c`` has as many entries;
+    ``options['dAAt']`` as in the reference.  The costgrad / hess closures (:243-296), the line search and the outer step
+    (:86-124) run on the device on the blocks' own storage; the per-block bookkeeping (eig(X_i), svd(Y_i), escape
+    directions; :121-181) follows :func:`ManiSDP_multiblock` (``block_eig`` option).  Returns (list of X_i, obj, data);
+    ``data['Y']`` is the list of factors (n_i, p_i)."""
+    with _host_threads():
+        return _dual_multiblock_impl(A, b, c, K, options, verbose, rng)
+
+
+def _dual_multiblock_impl(A, b, c, K, options, verbose, rng):
+    o = dict(options or {})
+    for k, v in DEFAULTS["dual_multiblock"].items():
+        o.setdefault(k, v)
+    nset = [int(v) for v in np.atleast_1d(K["s"])]
+    nb = len(nset)
+    nob = int(K.get("nob", 0))
+    nf = int(K.get("f", 0))
+    b = _dense_vec(b)
+    call = _dense_vec(c)
+    m = b.size
+    p0 = [int(v) for v in np.atleast_1d(o.get("p0", np.ones(nb, int)))]
+    rng = rng or np.random.default_rng(0)
+    _say(verbose, "ManiSDP is starting...")                # :30-31
+    _say(verbose, f"SDP size: n = {max(nset)}, m = {m}")
+    normc = 1.0 + np.linalg.norm(call)                     # :33
+    Aall = sp.csc_matrix(A)
+    B = Aall[:, :nf]; Apsd = sp.csr_matrix(Aall[:, nf:])   # :34-42
+    cf = call[:nf]; cpsd = call[nf:]
+    dAAt = o.get("dAAt", None)
+    if dAAt is None:
+        dAAt = np.asarray(Apsd.multiply(Apsd).sum(axis=1)).ravel()      # :44
+    dAAt = _dense_vec(dAAt)
+    r0 = np.concatenate([[0], np.cumsum(nset)]).astype(int)
+    N = int(r0[-1])
+    p = [p0[i] if nset[i] >= o["min_facsize"] else nset[i] for i in range(nb)]        # :50-55
+    delta = int(o["delta"])
+    h = _lib.Handle.dual_multiblock(Apsd, b, cpsd, dAAt, nset, nob, B if nf else None, cf, pcap=max(32, max(p) + 2 * delta))
+    be = o.get("block_eig", "auto")                        # as ManiSDP_multiblock
+    block_eig_device = be == "device" or (be == "auto" and nb >= 16 and max(nset) <= 256)
+    sigma = float(o["sigma0"]); gama = float(o["gama"])
+    w = np.zeros(nf)
+
+    def normalise(Yi, i):
+        return Yi / np.sqrt(np.sum(Yi * Yi, axis=1, keepdims=True)) if i < nob else Yi
+
+    Yb = o.get("Y0", None)
+    if Yb is None:                                         # trustregions.m:390-392 -> M.rand() (randc.cpp)
+        Yb = [normalise(rng.standard_normal((nset[i], p[i])), i) for i in range(nb)]
+    Yb = [np.ascontiguousarray(Yi, dtype=np.float64) for Yi in Yb]
+    Ub = None
+    data = {"status": 0, "hessvecs": 0, "cost_evals": 0, "rejected": 0, "rtr_seconds": 0.0, "eig_seconds": 0.0, "log": []}
+    t0 = time.time()
+    gap0 = pinf0 = dinf0 = None
+    obj = gap = pinf = dinf = gradnorm = eta = None
+    X = y = Y_eval = None
+    try:
+        for it in range(1, int(o["ADMM_maxiter"]) + 1):    # :79
+            pmax = max(p)
+            tdist = math.sqrt(math.pi * sum(nset[:nob]) + sum(pi * ni for pi, ni in zip(p[nob:], nset[nob:])))   # multiblockmanifold.m:11-15
+            topts = _lib.default_opts(maxiter=int(o["TR_maxiter"]), maxinner=int(o["TR_maxinner"]),
+                                      tolgradnorm=float(o["tolgradnorm"]), Delta_bar=tdist)
+            h.dual_set_penalty(sigma, w)
+            h.set_point(_pack_blocks(Yb, r0, N, pmax))
+            if Ub is not None:
+                _line_search(h, _pack_blocks(Ub, r0, N, pmax))   # :81-83, 220-241 (Y_i + alpha*U_i, DESIGN.md section 4)
+            st = h.rtr(topts)                              # :84
+            data["rtr_seconds"] += st.seconds
+            data["hessvecs"] += st.hessvecs; data["cost_evals"] += st.cost_evals; data["rejected"] += st.rejected
+            gradnorm = st.gradnorm                         # :85
+            Yfull = h.get_point()
+            Yb = [np.ascontiguousarray(Yfull[r0[i]:r0[i + 1], :p[i]]) for i in range(nb)]
+            Y_eval = Yb
+            by, cex, as2, Af, z = h.dual_outer_step()      # :86-124 (x, X_i - diag(z_i) on the device)
+            pinf = (math.sqrt(as2) + float(np.linalg.norm(Af))) / normc     # :95-100
+            w = w - sigma * Af                             # :108
+            obj = cex + float(cf @ w) + float(np.sum(z))   # :109, 117 (<c, x + bA>, DESIGN.md section 4)
+            t1 = time.time()
+            vX, dX, dinfs = [], [], []
+            if block_eig_device:
+                try:
+                    wall, Vall = h.block_eigs(r0[:-1], nset, delta)
+                except _lib.MsdpError:
+                    if be == "device":
+                        raise
+                    block_eig_device = False
+            if block_eig_device:
+                for i in range(nb):
+                    wv = wall[r0[i]:r0[i + 1]]
+                    dX.append(wv); vX.append(Vall[r0[i]:r0[i + 1], :])
+                    dinfs.append(max(0.0, -wv[0]) / (1.0 + abs(wv[-1])))   # :122
+            else:
+                for i in range(nb):                        # :121
+                    Xi = h.get_dual_slack_block(r0[i], nset[i])
+                    wv, V = np.linalg.eigh(0.5 * (Xi + Xi.T))
+                    dX.append(wv); vX.append(V)
+                    dinfs.append(max(0.0, -wv[0]) / (1.0 + abs(wv[-1])))   # :122
+            data["eig_seconds"] += time.time() - t1
+            dinf = max(dinfs)                              # :124
+            gap = abs(obj - by) / (1.0 + abs(obj) + abs(by))     # :125
+            _say(verbose, "Iter %d, obj:%0.8f, gap:%0.1e, pinf:%0.1e, dinf:%0.1e, gradnorm:%0.1e, p_max:%d, sigma:%0.3f, time:%0.2fs"
+                 % (it, obj, gap, pinf, dinf, gradnorm, max(p), sigma, time.time() - t0))
+            data["log"].append((it, obj, gap, pinf, dinf, gradnorm, max(p), sigma, time.time() - t0))
+            eta = max(gap, pinf, dinf)                     # :128
+            data["iters"] = it
+            if eta < o["tol"]:
+                _say(verbose, "Optimality is reached!")
+                break
+            if it % 50 == 0:                               # :133-143
+                if it > 100 and gap > gap0 and pinf > pinf0 and dinf > dinf0:
+                    data["status"] = 2
+                    _say(verbose, "Slow progress!")
+                    break
+                gap0, pinf0, dinf0 = gap, pinf, dinf
+            newY, newU = [], []
+            for i, n in enumerate(nset):                   # :144-181
+                Yi = Yb[i]
+                Ui = None
+                if n >= o["min_facsize"]:
+                    if p[i] > 1:
+                        Q, e, r = _thin_svd_rank(Yi, float(o["theta"]))   # :146-155 (r = sum(e > theta*e(1)), at least 1)
+                        r = max(int(np.sum(e > float(o["theta"]) * e[0])), 1)
+                        if r < p[i]:
+                            Yi = _rank_cut(Yi, Q, e, r)    # :156-159
+                            p[i] = r
+                    nneg = int(np.sum(dX[i] < 0))
+                    nne = max(min(nneg, delta), 1) if i < nob else min(nneg, delta)   # :160-164
+                    if p[i] + nne > n:
+                        nne = 0                            # :165-167
+                    if o["line_search"] == 1:
+                        Ui = np.hstack([np.zeros((n, p[i])), vX[i][:, :nne]])    # :169
+                        Yi = np.hstack([Yi, np.zeros((n, nne))])                 # :173
+                    else:
+                        Yi = normalise(np.hstack([Yi, o["alpha"] * vX[i][:, :nne]]), i)   # :175-178
+                    p[i] = p[i] + nne                      # :171
+                newY.append(np.ascontiguousarray(Yi))
+                newU.append(Ui if Ui is not None else np.zeros_like(Yi))
+            Yb = newY
+            Ub = newU if o["line_search"] == 1 else None
+            if pinf < o["tau1"] * gradnorm:                # :182-186
+                sigma = max(sigma / gama, float(o["sigma_min"]))
+            elif pinf > o["tau2"] * gradnorm:
+                sigma = min(sigma * gama, float(o["sigma_max"]))
+        if obj is not None:
+            X = [h.get_dual_slack_block(r0[i], nset[i]) for i in range(nb)]
+            y = h.dual_get_y()
+    finally:
+        h.close()
+    data.update({"X": X, "y": y, "S": ([Yi @ Yi.T for Yi in Y_eval] if Y_eval is not None else None), "w": w, "gap": gap,
+                 "pinf": pinf, "dinf": dinf, "gradnorm": gradnorm, "time": time.time() - t0, "Y": Y_eval, "sigma": sigma,
+                 "p": [Yi.shape[1] for Yi in (Y_eval or [])]})
+    if data["status"] == 0 and (eta is None or eta > o["tol"]):
+        data["status"] = 1
+        _say(verbose, "Iteration maximum is reached!")
+    _say(verbose, "ManiDSDP: optimum = %0.8f, time = %0.2fs" % (obj, time.time() - t0))   # :202
+    return X, obj, data

@@ -411,22 +411,376 @@ def _line_search(h, U):
     h.linesearch_accept()
 
 
-# =================================================================== unitdiag
+# ============================================================ one AL loop for the affine, multiblock and dual kinds
+# The reference's entry points other than ManiSDP_onlyunitdiag are copies of one scheme (as matlab/msdp_al_engine.m says):
+# solve the subproblem, update the multipliers, measure the KKT residues, cut the rank, add escape directions, adapt sigma.
+# _al_loop holds that scheme once.  What sets a kind apart is data: a factor geometry (_OneFactor / _Blocks), a multiplier
+# side (_primal_side / _dual_side) and the numbers and rules of a _Kind record.
 def _dense_vec(v):
     if sp.issparse(v):
         return np.asarray(v.todense()).ravel()
     return np.asarray(v, dtype=np.float64).ravel()
 
 
-def _affine_common(kind, At, b, c, K, options, verbose, rng, defaults):
-    with _host_threads():
-        return _affine_impl(kind, At, b, c, K, options, verbose, rng, defaults)
-
-
-def _affine_impl(kind, At, b, c, K, options, verbose, rng, defaults):
+def _with_defaults(options, defaults):
     o = dict(options or {})
     for k, v in defaults.items():
         o.setdefault(k, v)
+    return o
+
+
+def _rows(Y):                       # oblique factor: unit rows (ManiSDP_unitdiag.m:106)
+    return Y / np.sqrt(np.sum(Y * Y, axis=1, keepdims=True))
+
+
+def _frobenius(Y):                  # sphere factor (spherefactory.m:249-254, ManiSDP_unittrace.m:110)
+    return Y / np.linalg.norm(Y)
+
+
+def _euclidean(Y):                  # euclideanfactory.m:82 (M.rand = randn), ManiSDP.m:107: no normalisation
+    return Y
+
+
+def _dinf_primal(lam_min, lam_max):     # ManiSDP_unitdiag.m:69
+    return max(0.0, -lam_min) / (1.0 + lam_max)
+
+
+def _dinf_abs(lam_min, lam_max):        # ManiDSDP_unitdiag.m:86, ManiSDP_multiblock.m:87
+    return max(0.0, -lam_min) / (1.0 + abs(lam_max))
+
+
+def _gap_primal(obj, by):               # ManiSDP_unitdiag.m:71
+    return abs(obj - by) / (abs(by) + abs(obj) + 1.0)
+
+
+def _gap_dual(obj, by):                 # ManiDSDP_unitdiag.m:87
+    return abs(obj - by) / (1.0 + abs(obj) + abs(by))
+
+
+def _factor_rank(Y, theta, strict):
+    """svd(Y) and the rank estimate: r = sum(e >= theta*e(1)) in the primal kinds, strict ``>`` in the dual ones
+    (ManiDSDP_unitdiag.m:88-90)."""
+    Q, e, r = _thin_svd_rank(Y, theta)
+    if strict:
+        r = int(np.sum(e > theta * e[0]))
+    return Q, e, r
+
+
+def _widen(Y, p, V, nne, o, normalise):
+    """Add nne escape directions V to the (already cut) factor (ManiSDP_unitdiag.m:97-106): with line_search they
+    become the direction U next to p zero columns and Y gets zero columns; otherwise they are appended with weight alpha
+    and the factor is normalised.  Returns (Y, U or None, p + nne)."""
+    U = None
+    if o["line_search"] == 1:
+        U = np.hstack([np.zeros((Y.shape[0], p)), V[:, :nne]])
+        Y = np.hstack([Y, np.zeros((Y.shape[0], nne))])
+    else:
+        Y = normalise(np.hstack([Y, o["alpha"] * V[:, :nne]]))
+    return Y, U, p + nne
+
+
+def _eig_host(h, o, S, data):
+    """eig(S) of the reference on the host: of the S the host built (affine kinds, ManiSDP_unitdiag.m:68), else of the
+    dual slack the device holds (dual kinds, ManiDSDP_unitdiag.m:82).  Returns (lam, V, lam_max, certified)."""
+    if S is None:
+        X = h.get_dual_slack()
+        S = 0.5 * (X + X.T)
+    dS, vS = np.linalg.eigh(S)
+    return dS, vS, dS[-1], True
+
+
+def _eig_device(h, o, S, data):
+    """The few-eigenvector device escape instead of the O(n^3) eig: the `delta` bottom pairs and lambda_max of an
+    explicit S from the host, else of the S resident after al_dual / dual_outer_step."""
+    k = int(o["delta"])
+    if S is None:
+        run = lambda tol, maxit: h.escape_eigs_dual(k, tol=tol, maxit=maxit)
+    else:
+        run = lambda tol, maxit: h.escape_eigs_matrix(S, k, tol=tol, maxit=maxit)
+    lam, vS, lam_max, _, certified = _device_escape(h, run, o, data, 1e-10, 20000)
+    return lam, vS, lam_max, certified
+
+
+class _OneFactor:
+    """Factor geometry of the kinds with one (n, p) factor Y.  ``eig``: _eig_host or _eig_device; ``dinf``: the
+    kind's dinf formula; ``nne_floor``: least number of escape directions; ``miss_nneg(lam, nneg)``: the escape count
+    after the independent check found a lambda_min the regular escape had missed; ``layout``: the memory order Y is
+    kept in; ``comm``: row-sharded handle (the point is all-gathered)."""
+    line = "Iter %d, obj:%0.8f, gap:%0.1e, pinf:%0.1e, dinf:%0.1e, gradnorm:%0.1e, r:%d, p:%d, sigma:%0.3f, time:%0.2fs"
+
+    def __init__(self, h, o, n, normalise, eig, dinf, strict_rank, nne_floor, miss_nneg, layout=np.ascontiguousarray,
+                 comm=None):
+        self.h, self.o, self.n, self.normalise, self.eig, self.dinf = h, o, n, normalise, eig, dinf
+        self.strict_rank, self.nne_floor, self.miss_nneg, self.layout, self.comm = strict_rank, nne_floor, miss_nneg, layout, comm
+        self.rtr_opts = _rtr_opts(o)
+
+    def start(self, rng, p):                               # trustregions.m:390-392 -> M.rand()
+        Y = self.o.get("Y0", None)
+        if Y is None:
+            Y = self.normalise(rng.standard_normal((self.n, p)))
+        return self.layout(Y, dtype=np.float64)
+
+    def pack(self, Y, p):
+        return Y
+
+    def topts(self, p):
+        return self.rtr_opts
+
+    def fetch(self, p):
+        return self.h.get_point_all() if self.comm is not None else self.h.get_point()
+
+    def spectrum(self, S, data):
+        lam, vS, lam_max, certified = self.eig(self.h, self.o, S, data)
+        return self.dinf(lam[0], lam_max), certified, (lam, vS, int(np.sum(lam < 0)))
+
+    def missed(self, esc, lam_v, v_v):
+        lam, vS, nneg = esc
+        return lam, np.hstack([v_v, vS[:, :max(int(self.o["delta"]) - 1, 0)]]), self.miss_nneg(lam, nneg)
+
+    def shape(self, Y, p):                                 # ManiSDP_unitdiag.m:72-74
+        Q, e, r = _factor_rank(Y, float(self.o["theta"]), self.strict_rank)
+        return (r, p), (Q, e, r)
+
+    def reshape(self, Y, p, cut, esc):
+        Q, e, r = cut
+        if r <= p - 1:                                     # ManiSDP_unitdiag.m:93-96
+            Y = _rank_cut(Y, Q, e, r)
+            p = r
+        nne = max(min(esc[2], int(self.o["delta"])), self.nne_floor)    # :97
+        Y, U, p = _widen(Y, p, esc[1], nne, self.o, self.normalise)
+        return self.layout(Y), U, p
+
+
+class _Blocks:
+    """Factor geometry of the multiblock kinds: factors (n_i, p_i), oblique for the first ``nob`` blocks and Euclidean
+    after them, packed into ONE zero-padded (sum n_i, max p_i) factor on the device; the per-block bookkeeping
+    (eig(S_i), svd(Y_i), escape directions; ManiSDP_multiblock.m:78-147) stays on the host -- the blocks are small by
+    construction.  ``block_eig``: "host" = the reference's loop of eig(S_i) on the host, "device" = all blocks in one
+    launch (msdp_block_eigs: one workgroup per block; Householder tridiagonalisation, bisection, inverse iteration for the
+    `delta` <= 8 vectors the loop uses), "auto" (default) = device from 16 blocks of order <= 256 on, host below -- where
+    the oracle-parity tests compare iterate by iterate: the eigenvectors of two eigen-solvers differ by signs / rotations
+    inside eigenspaces."""
+    line = "Iter %d, obj:%0.8f, gap:%0.1e, pinf:%0.1e, dinf:%0.1e, gradnorm:%0.1e, p_max:%d, sigma:%0.3f, time:%0.2fs"
+
+    def __init__(self, h, o, nset, nob, strict_rank):
+        self.h, self.o, self.nset, self.nob, self.strict_rank = h, o, nset, nob, strict_rank
+        self.r0 = np.concatenate([[0], np.cumsum(nset)]).astype(int)
+        self.N = int(self.r0[-1])
+        be = o.get("block_eig", "auto")
+        self.eig_forced = be == "device"
+        self.eig_device = be == "device" or (be == "auto" and len(nset) >= 16 and max(nset) <= 256)
+        self.S = None                                      # the blocks of S the host eig last fetched
+
+    def normalise(self, i):
+        return _rows if i < self.nob else _euclidean
+
+    def start(self, rng, p):                               # trustregions.m:390-392 -> M.rand() (randc.cpp)
+        Yb = self.o.get("Y0", None)
+        if Yb is None:
+            Yb = [self.normalise(i)(rng.standard_normal((self.nset[i], p[i]))) for i in range(len(self.nset))]
+        return [np.ascontiguousarray(Yi, dtype=np.float64) for Yi in Yb]
+
+    def pack(self, Yb, p):
+        return _pack_blocks(Yb, self.r0, self.N, max(p))
+
+    def topts(self, p):                                    # M.typicaldist of multiblockmanifold.m:11-15
+        nset, nob = self.nset, self.nob
+        tdist = math.sqrt(math.pi * sum(nset[:nob]) + sum(pi * ni for pi, ni in zip(p[nob:], nset[nob:])))
+        o = self.o
+        return _lib.default_opts(maxiter=int(o["TR_maxiter"]), maxinner=int(o["TR_maxinner"]),
+                                 tolgradnorm=float(o["tolgradnorm"]), Delta_bar=tdist)
+
+    def fetch(self, p):
+        Yfull = self.h.get_point()
+        return [np.ascontiguousarray(Yfull[self.r0[i]:self.r0[i + 1], :p[i]]) for i in range(len(self.nset))]
+
+    def spectrum(self, S, data):                           # ManiSDP_multiblock.m:78-89
+        h, r0, nset = self.h, self.r0, self.nset
+        if self.eig_device:
+            try:
+                wall, Vall = h.block_eigs(r0[:-1], nset, int(self.o["delta"]))
+            except _lib.MsdpError:
+                if self.eig_forced:
+                    raise
+                self.eig_device = False
+        dS, vS = [], []
+        self.S = []
+        for i in range(len(nset)):
+            if self.eig_device:
+                dS.append(wall[r0[i]:r0[i + 1]]); vS.append(Vall[r0[i]:r0[i + 1], :])
+            else:                                          # only the diagonal blocks come to the host
+                Si = h.get_dual_slack_block(r0[i], nset[i])
+                w, V = np.linalg.eigh(0.5 * (Si + Si.T))   # :86
+                self.S.append(Si); dS.append(w); vS.append(V)
+        return max(_dinf_abs(w[0], w[-1]) for w in dS), True, (dS, vS)   # :87-89
+
+    def shape(self, Yb, p):
+        return (max(p),), None
+
+    def reshape(self, Yb, p, cut, esc):                    # ManiSDP_multiblock.m:109-147
+        dS, vS = esc
+        o, delta, p = self.o, int(self.o["delta"]), list(p)
+        newY, newU = [], []
+        for i, n in enumerate(self.nset):
+            Yi, Ui = Yb[i], None
+            if n >= o["min_facsize"]:
+                if p[i] > 1:
+                    Q, e, r = _factor_rank(Yi, float(o["theta"]), self.strict_rank)   # :112-121
+                    r = max(r, 1)
+                    if r < p[i]:
+                        Yi = _rank_cut(Yi, Q, e, r)        # :125
+                        p[i] = r
+                nneg = int(np.sum(dS[i] < 0))
+                nne = max(min(nneg, delta), 1 if i < self.nob else 0)    # :129-133
+                if p[i] + nne > n:
+                    nne = 0                                # :134-136
+                Yi, Ui, p[i] = _widen(Yi, p[i], vS[i], nne, o, self.normalise(i))   # :137-147
+            newY.append(np.ascontiguousarray(Yi))
+            newU.append(Ui if Ui is not None else np.zeros_like(Yi))
+        return newY, (newU if o["line_search"] == 1 else None), p
+
+
+def _by(b, y, z):                                          # ManiSDP_unitdiag.m:70 (no z term in the generic kind)
+    return float(b @ y) if z is None else float(b @ y) + float(np.sum(z))
+
+
+def _primal_side(h, b):
+    """Multiplier side of the primal kinds on the device: obj and A x (msdp_al_primal), the y update,
+    then S and z (msdp_al_dual; S stays on the device).  Returns (set_penalty, outer_step)."""
+    normb = 1.0 + np.linalg.norm(b)
+
+    def outer_step(Y, y, sigma):
+        obj, Ax = h.al_primal(b.size)                      # ManiSDP_unitdiag.m:59-61
+        Axb = Ax - b                                       # :62
+        pinf = float(np.linalg.norm(Axb)) / normb          # :63
+        y = y - sigma * Axb                                # :64
+        z = h.al_dual(y)                                   # :65-67
+        return obj, _by(b, y, z), pinf, y, z, None
+    return h.set_multipliers, outer_step
+
+
+def _dual_side(h, call, nf):
+    """Multiplier side of the dual kinds (ManiDSDP_unitdiag.m:70-85): x <- x - sigma*As on the device
+    (msdp_dual_outer_step), the w update and obj = <C, eX> + cf'w (+ sum z where the kind has z).
+    Returns (set_penalty, outer_step)."""
+    normc = 1.0 + np.linalg.norm(call)                     # :32
+    cf = call[:nf]
+
+    def outer_step(Y, w, sigma):
+        by, cex, as2, Af, z = h.dual_outer_step()
+        pinf = (math.sqrt(as2) + float(np.linalg.norm(Af))) / normc    # :75
+        w = w - sigma * Af                                 # :78
+        obj = cex + float(cf @ w)                          # :85
+        if z is not None:
+            obj = obj + float(np.sum(z))
+        return obj, by, pinf, w, z, None
+    return (lambda w, sigma: h.dual_set_penalty(sigma, w)), outer_step
+
+
+class _Kind:
+    """What the outer loop needs to know of a kind beyond its geometry and multiplier side.
+    ``gap``: _gap_primal / _gap_dual; ``slow``: (every, after) of the slow-progress watch; ``verify``: the device escape
+    is checked by _verify_lambda_min before dinf may end the solve, once the KKT residues (``verify_on_kkt``) or dinf
+    alone are below tol; ``verify_at_end``: a solve that stopped without that check gets it once more (both need the
+    single-factor geometry: the check is of one n x n S, and its result goes through _OneFactor.dinf / .missed);
+    ``log``: the slice of (it, obj, gap, pinf, dinf, gradnorm, <shape>, sigma, time) that goes to data["log"]."""
+
+    def __init__(self, geo, side, maxiter, gap, slow, message, verify=False, verify_on_kkt=False, verify_at_end=False,
+                 log=slice(None), iter_hook=None):
+        assert not (verify or verify_at_end) or isinstance(geo, _OneFactor), "the lambda_min check needs one factor"
+        self.geo, (self.set_penalty, self.outer_step) = geo, side
+        self.maxiter, self.gap, self.slow, self.message = maxiter, gap, slow, message
+        self.verify, self.verify_on_kkt, self.verify_at_end = verify, verify_on_kkt, verify_at_end
+        self.log, self.iter_hook = log, iter_hook
+
+
+def _al_loop(h, o, t, Y, p, mult, verbose):
+    """The augmented-Lagrangian outer loop (ManiSDP_unitdiag.m:55-113 and its copies in the other entry points):
+    trustregions() on the device, multiplier update, KKT residues, stop and slow-progress tests, rank cut, escape
+    directions, sigma update.  Returns (obj, data, last) with ``last`` = (Y, multipliers, z, S) of the last evaluated
+    point, p at its end and the per-iteration lists fac_size and seta."""
+    geo, tol = t.geo, o["tol"]
+    every, after = t.slow
+    sigma = float(o["sigma0"]); gama = float(o["gama"])
+    data = {"status": 0, "hessvecs": 0, "cost_evals": 0, "rejected": 0, "rtr_seconds": 0.0, "eig_seconds": 0.0, "log": []}
+    fac_size, seta = [], []
+    U = None
+    t0 = time.time()
+    gap0 = pinf0 = dinf0 = None
+    obj = gap = pinf = dinf = gradnorm = eta = None
+    Y_eval = z = S = None
+    certified = last_verified = True
+
+    def verify():
+        # the regular escape call is warm-started (columns of Y and the previous call's vectors in its start block, or
+        # span(Y) deflated): before dinf may end the solve, lambda_min is recomputed by a cold-started, undeflated run
+        return _verify_lambda_min(h, lambda tol, maxit: h.escape_eigs_dual(1, tol=tol, maxit=maxit), o, data, 1e-10, 20000,
+                                  dense_n=geo.n)
+
+    for it in range(1, t.maxiter + 1):
+        fac_size.append(p)
+        t.set_penalty(mult, sigma)
+        h.set_point(geo.pack(Y, p))
+        if U is not None:
+            _line_search(h, geo.pack(U, p))
+        st = h.rtr(geo.topts(p))                           # ManiSDP_unitdiag.m:57
+        data["rtr_seconds"] += st.seconds
+        data["hessvecs"] += st.hessvecs
+        data["cost_evals"] += st.cost_evals
+        data["rejected"] += st.rejected
+        gradnorm = st.gradnorm
+        Y = Y_eval = geo.fetch(p)                          # what the reference returns (:114)
+        obj, by, pinf, mult, z, S = t.outer_step(Y, mult, sigma)
+        t1 = time.time()
+        dinf, certified, esc = geo.spectrum(S, data)       # :68-69
+        data["eig_seconds"] += time.time() - t1
+        gap = t.gap(obj, by)                               # :71
+        last_verified = not t.verify
+        if t.verify and certified and ((max(gap, pinf, dinf) if t.verify_on_kkt else dinf) < tol or it == t.maxiter):
+            last_verified = True
+            lam_v, v_v, lmax_v, certified = verify()
+            dinf_v = geo.dinf(lam_v, lmax_v)
+            if dinf_v >= tol > dinf:                       # the deflated run had missed the bottom of the spectrum
+                esc = geo.missed(esc, lam_v, v_v)
+            dinf = dinf_v
+        shape, cut = geo.shape(Y, p)
+        row = (it, obj, gap, pinf, dinf, gradnorm) + shape + (sigma, time.time() - t0)
+        _say(verbose, geo.line % row)
+        data["log"].append(row[t.log])
+        eta = max(gap, pinf, dinf)                         # :77
+        seta.append(eta)
+        data["iters"] = it
+        if t.iter_hook is not None:                        # diagnostics (tools/): sees the loop's local state
+            t.iter_hook(locals())
+        if eta < tol and certified:                        # an unconverged Lanczos run certifies nothing
+            _say(verbose, "Optimality is reached!")
+            break
+        if it % every == 0:                                # :82-92
+            if it > after and gap > gap0 and pinf > pinf0 and dinf > dinf0:
+                data["status"] = 2
+                _say(verbose, "Slow progress!")
+                break
+            gap0, pinf0, dinf0 = gap, pinf, dinf
+        Y, U, p = geo.reshape(Y, p, cut, esc)              # :93-106
+        if pinf < o["tau1"] * gradnorm:                    # :108-112
+            sigma = max(sigma / gama, float(o["sigma_min"]))
+        elif pinf > o["tau2"] * gradnorm:
+            sigma = min(sigma * gama, float(o["sigma_max"]))
+    if t.verify_at_end and obj is not None and not last_verified and certified:   # stopped on "Slow progress": report the true dinf
+        lam_v, _, lmax_v, certified = verify()
+        dinf = geo.dinf(lam_v, lmax_v)
+    data.update({"Y": Y_eval, "gap": gap, "pinf": pinf, "dinf": dinf, "gradnorm": gradnorm, "time": time.time() - t0,
+                 "sigma": sigma})
+    if data["status"] == 0 and (eta is None or eta > tol or not certified):
+        data["status"] = 1
+        _say(verbose, "Iteration maximum is reached!")
+    _say(verbose, t.message % (obj, time.time() - t0))
+    return obj, data, (Y_eval, mult, z, S, p, fac_size, seta)
+
+
+# =================================================================== affine kinds
+def _affine_impl(kind, At, b, c, K, options, verbose, rng, defaults):
+    o = _with_defaults(options, defaults)
     n = int(K["s"])
     rng = rng or np.random.default_rng(0)
     b = _dense_vec(b)
@@ -439,210 +793,80 @@ def _affine_impl(kind, At, b, c, K, options, verbose, rng, defaults):
     _say(verbose, "ManiSDP is starting...")
     _say(verbose, f"SDP size: n = {n}, m = {b.size}")
     h = _lib.Handle.affine(kind, Atc, b, c, n, pcap=max(32, int(o["p0"]) + 2 * int(o["delta"])))
-    # options['comm'] = (nranks, rank, unique_id): one process per GPU, rows of the factor sharded over the ranks
-    # (msdp_comm_init).  Every rank runs this same host loop on identical data -- the operator state is replicated on
-    # the device, the start point must be the same on all ranks (pass Y0 or seed rng identically) -- and reaches the same
-    # decisions; collectives happen inside the library calls.
-    comm = o.get("comm")
-    if comm is not None:
-        _join_comm(h, comm)
-    if "escape_method" in o:                               # 0 auto (Lanczos on the explicit S of these kinds), 1 Lanczos, 2 block eigen-solver
-        h.set_option("escape_method", int(o["escape_method"]))
-    for name, value in (o.get("device_options") or {}).items():     # run-time switches of the handle (msdp_set_option): A/B runs, tests
-        h.set_option(name, int(value))
-    topts = _rtr_opts(o)
-    p = int(o["p0"])
-    sigma = float(o["sigma0"])
-    gama = float(o["gama"])
-    y = np.zeros(b.size)
-    normb = 1.0 + np.linalg.norm(b)
-    Y = o.get("Y0", None)
-    if Y is None:
-        Y = rng.standard_normal((n, p))
-        if generic:
-            pass                                           # euclideanfactory.m:82 (M.rand = randn)
-        elif sphere:
-            Y /= np.linalg.norm(Y)                         # spherefactory.m:249-254
-        else:
-            Y /= np.sqrt(np.sum(Y * Y, axis=1, keepdims=True))
-    Y = np.ascontiguousarray(Y, dtype=np.float64)
-    U = None
-    fac_size = []
-    data = {"status": 0, "hessvecs": 0, "cost_evals": 0, "rejected": 0, "rtr_seconds": 0.0,
-            "eig_seconds": 0.0, "log": []}
-    t0 = time.time()
-    gap0 = pinf0 = dinf0 = None
-    obj = gap = pinf = dinf = gradnorm = eta_kkt = None
-    S = z = None
-    slow_every, slow_after = (20, 50) if (sphere or generic) else (50, 100)
-    certified = True
-    last_verified = True
     try:
-        for it in range(1, int(o["AL_maxiter"]) + 1):
-            fac_size.append(p)
-            h.set_multipliers(y, sigma)
-            h.set_point(Y)
-            if U is not None:
-                _line_search(h, U)
-            st = h.rtr(topts)
-            data["rtr_seconds"] += st.seconds
-            data["hessvecs"] += st.hessvecs
-            data["cost_evals"] += st.cost_evals
-            data["rejected"] += st.rejected
-            gradnorm = st.gradnorm
-            Y = h.get_point_all() if comm is not None else h.get_point()
-            Y_eval = Y                                     # X of :59 -- what the reference returns (:114)
-            dev_al = (eig_mode == "device") and bool(o.get("device_al", True))
-            certified = True
-            if dev_al:
-                # obj, A x, eS, z and S from the device kernels (no n x n work on the host)
-                obj, Ax = h.al_primal(b.size)              # :59-61
-                Axb = Ax - b                               # :62
-                pinf = float(np.linalg.norm(Axb)) / normb  # :63
-                y = y - sigma * Axb                        # :64
-                t1 = time.time()
-                zz = h.al_dual(y)                          # :65-67 (S stays on the device)
-                if generic:
-                    by = float(b @ y)
-                elif sphere:
-                    z = zz
-                    by = float(b @ y) + z
-                else:
-                    z = zz
-                    by = float(b @ y) + float(np.sum(z))
-                lam, vS, lam_max, _, certified = _device_escape(
-                    h, lambda tol, maxit: h.escape_eigs_dual(int(o["delta"]), tol=tol, maxit=maxit), o, data,
-                    1e-10, 20000)                          # :68
-                dS = np.concatenate([lam, [lam_max]])
-                S = None
-                data["eig_seconds"] += time.time() - t1
-            else:
-                X = Y @ Y.T                                # unitdiag :59 / unittrace :59
-                x = X.ravel(order="F")
-                obj = float(c @ x)                         # :61
-                Axb = A @ x - b                            # :62
-                pinf = float(np.linalg.norm(Axb)) / normb  # :63
-                y = y - sigma * Axb                        # :64
-                eS = (c - Atc @ y).reshape((n, n), order="F")  # :65
-                t1 = time.time()
-            if dev_al:
-                pass
-            elif generic:
-                S = eS                                     # ManiSDP.m:64
-                by = float(b @ y)                          # :67
+        # options['comm'] = (nranks, rank, unique_id): one process per GPU, rows of the factor sharded over the ranks
+        # (msdp_comm_init).  Every rank runs this same host loop on identical data -- the operator state is replicated on
+        # the device, the start point must be the same on all ranks (pass Y0 or seed rng identically) -- and reaches the
+        # same decisions; collectives happen inside the library calls.
+        comm = o.get("comm")
+        if comm is not None:
+            _join_comm(h, comm)
+        if "escape_method" in o:                           # 0 auto (Lanczos on the explicit S of these kinds), 1 Lanczos, 2 block eigen-solver
+            h.set_option("escape_method", int(o["escape_method"]))
+        for name, value in (o.get("device_options") or {}).items():     # run-time switches of the handle (msdp_set_option): A/B runs, tests
+            h.set_option(name, int(value))
+        dev_al = eig_mode == "device" and bool(o.get("device_al", True))
+        normb = 1.0 + np.linalg.norm(b)
+
+        def host_step(Y, y, sigma):                        # the reference's n x n arithmetic on the host
+            X = Y @ Y.T                                    # unitdiag :59 / unittrace :59
+            x = X.ravel(order="F")
+            obj = float(c @ x)                             # :61
+            Axb = A @ x - b                                # :62
+            pinf = float(np.linalg.norm(Axb)) / normb      # :63
+            y = y - sigma * Axb                            # :64
+            eS = (c - Atc @ y).reshape((n, n), order="F")  # :65
+            if generic:
+                z, S = None, eS                            # ManiSDP.m:64
             elif sphere:
                 z = float(np.sum(eS * X))                  # unittrace :66
                 S = eS - z * np.eye(n)                     # :67
-                by = float(b @ y) + z                      # :70
             else:
                 z = np.sum(X * eS, axis=0)                 # unitdiag :66
                 S = eS - np.diag(z)                        # :67
-                by = float(b @ y) + float(np.sum(z))       # :70
-            if dev_al:
-                pass
-            elif eig_mode == "device":
-                # few-eigenvector escape on the device instead of the O(n^3) eig(S) of :68
-                lam, vS, lam_max, _, certified = _device_escape(
-                    h, lambda tol, maxit: h.escape_eigs_matrix(S, int(o["delta"]), tol=tol, maxit=maxit), o, data,
-                    1e-10, 20000)
-                dS = np.concatenate([lam, [lam_max]])      # dS[0] = lambda_min ... dS[-1] = lambda_max
-                data["eig_seconds"] += time.time() - t1
-            else:
-                dS, vS = np.linalg.eigh(S)                 # :68
-                data["eig_seconds"] += time.time() - t1
-            dinf = max(0.0, -dS[0]) / (1.0 + dS[-1])       # :69
-            gap = abs(obj - by) / (abs(by) + abs(obj) + 1.0)   # :71
-            last_verified = not dev_al
-            if dev_al and certified and ((max(gap, pinf, dinf) < o["tol"]) or it == int(o["AL_maxiter"])):
-                last_verified = True
-                lam_v, v_v, lmax_v, certified = _verify_lambda_min(
-                    h, lambda tol, maxit: h.escape_eigs_dual(1, tol=tol, maxit=maxit), o, data, 1e-10, 20000, dense_n=n)
-                dinf_v = max(0.0, -lam_v) / (1.0 + lmax_v)
-                if dinf_v >= o["tol"] > dinf:
-                    vS = np.hstack([v_v, vS[:, :max(int(o["delta"]) - 1, 0)]])
-                    dS = np.concatenate([[lam_v], dS[:-2], [lmax_v]])
-                dinf = dinf_v
-            Q, e, r = _thin_svd_rank(Y, float(o["theta"]))     # :72-74
-            _say(verbose, "Iter %d, obj:%0.8f, gap:%0.1e, pinf:%0.1e, dinf:%0.1e, gradnorm:%0.1e, r:%d, p:%d, sigma:%0.3f, time:%0.2fs"
-                 % (it, obj, gap, pinf, dinf, gradnorm, r, p, sigma, time.time() - t0))
-            data["log"].append((it, obj, gap, pinf, dinf, gradnorm, r, p, sigma, time.time() - t0))
-            eta_kkt = max(gap, pinf, dinf)                 # :77
-            data["iters"] = it
-            if "iter_hook" in o:                           # diagnostics (tools/): sees the loop's local state
-                o["iter_hook"](locals())
-            if eta_kkt < o["tol"] and certified:
-                _say(verbose, "Optimality is reached!")
-                break
-            if it % slow_every == 0:                       # unitdiag :82-92 / unittrace :86-96
-                if it > slow_after and gap > gap0 and pinf > pinf0 and dinf > dinf0:
-                    data["status"] = 2
-                    _say(verbose, "Slow progress!")
-                    break
-                gap0, pinf0, dinf0 = gap, pinf, dinf
-            if r <= p - 1:                                 # :93-96
-                Y = _rank_cut(Y, Q, e, r)
-                p = r
-            nneg = int(np.sum(dS[:-1] < 0)) if eig_mode == "device" else int(np.sum(dS < 0))
-            if sphere or generic:
-                nne = min(nneg, int(o["delta"]))           # unittrace :101 / ManiSDP.m:99
-            else:
-                nne = max(min(nneg, int(o["delta"])), 1)   # unitdiag :97
-            if o["line_search"] == 1:
-                U = np.hstack([np.zeros((n, p)), vS[:, :nne]])
-            p = p + nne
-            if o["line_search"] == 1:
-                Y = np.hstack([Y, np.zeros((n, nne))])
-            else:
-                Y = np.hstack([Y, o["alpha"] * vS[:, :nne]])
-                if generic:
-                    pass                                   # ManiSDP.m:107
-                elif sphere:
-                    Y = Y / np.linalg.norm(Y)              # unittrace :110
-                else:
-                    Y = Y / np.sqrt(np.sum(Y * Y, axis=1, keepdims=True))   # unitdiag :106
-            Y = np.ascontiguousarray(Y)
-            if pinf < o["tau1"] * gradnorm:                # :108-112
-                sigma = max(sigma / gama, o["sigma_min"])
-            elif pinf > o["tau2"] * gradnorm:
-                sigma = min(sigma * gama, o["sigma_max"])
-        if obj is not None and not last_verified and certified:   # stopped on "Slow progress": report the true dinf
-            lam_v, _, lmax_v, certified = _verify_lambda_min(
-                h, lambda tol, maxit: h.escape_eigs_dual(1, tol=tol, maxit=maxit), o, data, 1e-10, 20000, dense_n=n)
-            dinf = max(0.0, -lam_v) / (1.0 + lmax_v)
+            return obj, _by(b, y, z), pinf, y, z, S
+
+        set_penalty, dev_step = _primal_side(h, b)
+        geo = _OneFactor(h, o, n, _euclidean if generic else _frobenius if sphere else _rows,
+                         _eig_device if eig_mode == "device" else _eig_host, _dinf_primal, strict_rank=False,
+                         nne_floor=0 if (sphere or generic) else 1,           # unittrace :101 / ManiSDP.m:99 / unitdiag :97
+                         miss_nneg=lambda lam, nneg: 1 + int(np.sum(lam[:-1] < 0)),   # the missed pair goes in below the others
+                         comm=comm)
+        t = _Kind(geo, (set_penalty, dev_step if dev_al else host_step), int(o["AL_maxiter"]), _gap_primal,
+                  (20, 50) if (sphere or generic) else (50, 100), "ManiSDP: optimum = %0.8f, time = %0.2fs",
+                  verify=dev_al, verify_on_kkt=True, verify_at_end=True, iter_hook=o.get("iter_hook"))
+        p = int(o["p0"])
+        obj, data, (Y, y, z, S, _, fac_size, _) = _al_loop(h, o, t, geo.start(rng, p), p, np.zeros(b.size), verbose)
         if S is None and obj is not None and n <= int(o.get("dense_X_max", 6000)):
             S = h.get_dual_slack()                         # data.S of the reference (:116), from the device
     finally:
         h.close()
-    if obj is not None:
-        Y = Y_eval          # the point the residues belong to (the loop's last pass has already widened its own copy)
-    data.update({"Y": Y, "X": (Y @ Y.T if n <= int(o.get("dense_X_max", 6000)) else None), "y": y, "S": S, "z": z, "gap": gap, "pinf": pinf, "dinf": dinf,
-                 "gradnorm": gradnorm, "time": time.time() - t0, "sigma": sigma})
+    data.update({"X": (Y @ Y.T if n <= int(o.get("dense_X_max", 6000)) else None), "y": y, "S": S, "z": z})
     if not sphere and not generic:
         data["fac_size"] = fac_size
-    if data["status"] == 0 and (eta_kkt > o["tol"] or not certified):
-        data["status"] = 1
-        _say(verbose, "Iteration maximum is reached!")
-    _say(verbose, "ManiSDP: optimum = %0.8f, time = %0.2fs" % (obj, time.time() - t0))
     return Y, obj, data
 
 
 def ManiSDP_unitdiag(At, b, c, K, options=None, verbose=True, rng=None):
     """``[X, obj, data] = ManiSDP_unitdiag(At, b, c, K, options)`` (reference
     src/primal/ManiSDP_unitdiag.m:7; defaults :10-26)."""
-    return _affine_common(_lib.KIND_UNITDIAG, At, b, c, K, options, verbose, rng, DEFAULTS["unitdiag"])
+    with _host_threads():
+        return _affine_impl(_lib.KIND_UNITDIAG, At, b, c, K, options, verbose, rng, DEFAULTS["unitdiag"])
 
 
 def ManiSDP_unittrace(At, b, c, K, options=None, verbose=True, rng=None):
     """``[X, obj, data] = ManiSDP_unittrace(At, b, c, K, options)`` (reference
     src/primal/ManiSDP_unittrace.m:7; defaults :10-25)."""
-    return _affine_common(_lib.KIND_UNITTRACE, At, b, c, K, options, verbose, rng, DEFAULTS["unittrace"])
+    with _host_threads():
+        return _affine_impl(_lib.KIND_UNITTRACE, At, b, c, K, options, verbose, rng, DEFAULTS["unittrace"])
 
 
 def ManiSDP(At, b, c, K, options=None, verbose=True, rng=None):
     """``[X, obj, data] = ManiSDP(At, b, c, K, options)`` -- the generic entry point on the Euclidean manifold
     (reference src/primal/ManiSDP.m:6; defaults :9-25).  Same device kernels as the two structured affine entry
     points with the projection / retraction terms switched off."""
-    return _affine_common(_lib.KIND_GENERIC, At, b, c, K, options, verbose, rng, DEFAULTS["generic"])
+    with _host_threads():
+        return _affine_impl(_lib.KIND_GENERIC, At, b, c, K, options, verbose, rng, DEFAULTS["generic"])
 
 
 # ================================================================= multiblock
@@ -660,6 +884,11 @@ def _pack_blocks(blocks, r0, N, pmax):
     return Y
 
 
+def _block_widths(o, nset):                                # ManiSDP_multiblock.m:34-39
+    p0 = [int(v) for v in np.atleast_1d(o.get("p0", np.ones(len(nset), int)))]
+    return [p0[i] if nset[i] >= o["min_facsize"] else nset[i] for i in range(len(nset))]
+
+
 def ManiSDP_multiblock(At, b, c, K, options=None, verbose=True, rng=None):
     """``[X, obj, data] = ManiSDP_multiblock(At, b, c, K, options)`` (reference src/primal/ManiSDP_multiblock.m:7):
     block-diagonal X with unit diagonal on the first ``K['nob']`` blocks of orders ``K['s']``.  The product manifold
@@ -671,161 +900,47 @@ def ManiSDP_multiblock(At, b, c, K, options=None, verbose=True, rng=None):
 
 
 def _multiblock_impl(At, b, c, K, options, verbose, rng):
-    o = dict(options or {})
-    for k, v in DEFAULTS["multiblock"].items():
-        o.setdefault(k, v)
+    o = _with_defaults(options, DEFAULTS["multiblock"])
     nset = [int(v) for v in np.atleast_1d(K["s"])]
-    nob = int(K.get("nob", 0))
-    nb = len(nset)
-    p0 = [int(v) for v in np.atleast_1d(o.get("p0", np.ones(nb, int)))]
     rng = rng or np.random.default_rng(0)
     b = _dense_vec(b)
     c = _dense_vec(c)
-    Atc = sp.csc_matrix(At)
-    r0 = np.concatenate([[0], np.cumsum(nset)]).astype(int)
-    N = int(r0[-1])
     _say(verbose, "ManiSDP is starting...")
     _say(verbose, f"SDP size: n = {max(nset)}, m = {b.size}")
-    p = [p0[i] if nset[i] >= o["min_facsize"] else nset[i] for i in range(nb)]        # :34-39
-    h = _lib.Handle.multiblock(Atc, b, c, nset, nob, pcap=max(32, max(p) + 2 * int(o["delta"])))
-    # options["block_eig"]: "host" = the reference's loop of eig(S{i}) on the host (LAPACK through NumPy), "device" = all blocks in
-    # one launch on the GPU (msdp_block_eigs: one workgroup per block; Householder tridiagonalisation, bisection, inverse iteration
-    # for the `delta` <= 8 vectors the loop uses), "auto" (default) = device from 16 blocks of order <= 256 on, host below -- where the
-    # oracle-parity tests compare iterate by iterate: the eigenvectors of two eigen-solvers differ by signs / rotations inside
-    # eigenspaces
-    be = o.get("block_eig", "auto")
-    block_eig_device = be == "device" or (be == "auto" and nb >= 16 and max(nset) <= 256)
-    sigma = float(o["sigma0"]); gama = float(o["gama"])
-    y = np.zeros(b.size)
-    normb = 1.0 + np.linalg.norm(b)
-
-    def normalise(Yi, i):
-        return Yi / np.sqrt(np.sum(Yi * Yi, axis=1, keepdims=True)) if i < nob else Yi
-
-    Yb = o.get("Y0", None)
-    if Yb is None:                                          # trustregions.m:390-392 -> M.rand() (randc.cpp)
-        Yb = [normalise(rng.standard_normal((nset[i], p[i])), i) for i in range(nb)]
-    Yb = [np.ascontiguousarray(Yi, dtype=np.float64) for Yi in Yb]
-    Ub = None
-    data = {"status": 0, "hessvecs": 0, "cost_evals": 0, "rejected": 0, "rtr_seconds": 0.0, "eig_seconds": 0.0, "log": []}
-    t0 = time.time()
-    gap0 = pinf0 = dinf0 = None
-    obj = gap = pinf = dinf = gradnorm = eta_kkt = None
-    X = S = Y_eval = None
+    p = _block_widths(o, nset)
+    h = _lib.Handle.multiblock(sp.csc_matrix(At), b, c, nset, int(K.get("nob", 0)), pcap=max(32, max(p) + 2 * int(o["delta"])))
     try:
-        for it in range(1, int(o["AL_maxiter"]) + 1):       # :57
-            pmax = max(p)
-            # M.typicaldist of multiblockmanifold.m:11-15
-            tdist = math.sqrt(math.pi * sum(nset[:nob]) + sum(pi * ni for pi, ni in zip(p[nob:], nset[nob:])))
-            topts = _lib.default_opts(maxiter=int(o["TR_maxiter"]), maxinner=int(o["TR_maxinner"]),
-                                      tolgradnorm=float(o["tolgradnorm"]), Delta_bar=tdist)
-            h.set_multipliers(y, sigma)
-            h.set_point(_pack_blocks(Yb, r0, N, pmax))
-            if Ub is not None:
-                _line_search(h, _pack_blocks(Ub, r0, N, pmax))   # :59-61, 171-193
-            st = h.rtr(topts)                               # :62
-            data["rtr_seconds"] += st.seconds
-            data["hessvecs"] += st.hessvecs
-            data["cost_evals"] += st.cost_evals
-            data["rejected"] += st.rejected
-            gradnorm = st.gradnorm                          # :63
-            Yfull = h.get_point()
-            Yb = [np.ascontiguousarray(Yfull[r0[i]:r0[i + 1], :p[i]]) for i in range(nb)]
-            Y_eval = Yb
-            obj, Ax = h.al_primal(b.size)                   # :65-70
-            Axb = Ax - b                                    # :71
-            pinf = float(np.linalg.norm(Axb)) / normb       # :72
-            y = y - sigma * Axb                             # :73
-            t1 = time.time()
-            z = h.al_dual(y)                                # :74-84 on the device: S = cy blocks - diag(z), z = 0 on free rows
-            by = float(b @ y) + float(np.sum(z))            # :75,82
-            S, vS, dS, dinfs = [], [], [], []
-            if block_eig_device:
-                # eig(S{i}) of every block in one launch (msdp_block_eigs: cyclic Jacobi, one workgroup per block); what the loop
-                # below uses of it -- all eigenvalues, the eigenvectors of the `delta` smallest -- is what comes back
-                try:
-                    wall, Vall = h.block_eigs(r0[:-1], nset, int(o["delta"]))
-                except _lib.MsdpError:
-                    if o.get("block_eig", "auto") == "device":
-                        raise
-                    block_eig_device = False
-            if block_eig_device:
-                for i in range(nb):
-                    w = wall[r0[i]:r0[i + 1]]
-                    dS.append(w); vS.append(Vall[r0[i]:r0[i + 1], :])
-                    dinfs.append(max(0.0, -w[0]) / (1.0 + abs(w[-1])))   # :87
-            else:
-                for i in range(nb):                         # :78-88 (only the diagonal blocks come to the host)
-                    Si = h.get_dual_slack_block(r0[i], nset[i])
-                    w, V = np.linalg.eigh(0.5 * (Si + Si.T))    # :86
-                    S.append(Si); dS.append(w); vS.append(V)
-                    dinfs.append(max(0.0, -w[0]) / (1.0 + abs(w[-1])))   # :87
-            data["eig_seconds"] += time.time() - t1
-            dinf = max(dinfs)                               # :89
-            gap = abs(obj - by) / (abs(by) + abs(obj) + 1.0)   # :90
-            _say(verbose, "Iter %d, obj:%0.8f, gap:%0.1e, pinf:%0.1e, dinf:%0.1e, gradnorm:%0.1e, p_max:%d, sigma:%0.3f, time:%0.2fs"
-                 % (it, obj, gap, pinf, dinf, gradnorm, max(p), sigma, time.time() - t0))
-            data["log"].append((it, obj, gap, pinf, dinf, gradnorm, max(p), sigma, time.time() - t0))
-            eta_kkt = max(gap, pinf, dinf)                  # :93
-            data["iters"] = it
-            if eta_kkt < o["tol"]:
-                _say(verbose, "Optimality is reached!")
-                break
-            if it % 50 == 0:                                # :98-108
-                if it > 100 and gap > gap0 and pinf > pinf0 and dinf > dinf0:
-                    data["status"] = 2
-                    _say(verbose, "Slow progress!")
-                    break
-                gap0, pinf0, dinf0 = gap, pinf, dinf
-            newY, newU = [], []
-            for i, n in enumerate(nset):                    # :109-147
-                Yi = Yb[i]
-                Ui = None
-                if n >= o["min_facsize"]:
-                    if p[i] > 1:
-                        Q, e, r = _thin_svd_rank(Yi, float(o["theta"]))   # :112-121
-                        r = max(r, 1)
-                        if r < p[i]:
-                            Yi = _rank_cut(Yi, Q, e, r)     # :125
-                            p[i] = r
-                    nneg = int(np.sum(dS[i] < 0))
-                    nne = max(min(nneg, int(o["delta"])), 1) if i < nob else min(nneg, int(o["delta"]))   # :129-133
-                    if p[i] + nne > n:
-                        nne = 0                             # :134-136
-                    if o["line_search"] == 1:
-                        Ui = np.hstack([np.zeros((n, p[i])), vS[i][:, :nne]])    # :137-139
-                        Yi = np.hstack([Yi, np.zeros((n, nne))])                 # :141-142
-                    else:
-                        Yi = normalise(np.hstack([Yi, o["alpha"] * vS[i][:, :nne]]), i)   # :143-147
-                    p[i] = p[i] + nne                       # :140
-                newY.append(np.ascontiguousarray(Yi))
-                newU.append(Ui if Ui is not None else np.zeros_like(Yi))
-            Yb = newY
-            Ub = newU if o["line_search"] == 1 else None
-            if pinf < o["tau1"] * gradnorm:                 # :150-154
-                sigma = max(sigma / gama, o["sigma_min"])
-            elif pinf > o["tau2"] * gradnorm:
-                sigma = min(sigma * gama, o["sigma_max"])
-        if block_eig_device and Y_eval is not None:         # data.S (:158): the blocks of the last iterate, fetched once
-            S = [h.get_dual_slack_block(r0[i], nset[i]) for i in range(nb)]
+        geo = _Blocks(h, o, nset, int(K.get("nob", 0)), strict_rank=False)
+        t = _Kind(geo, _primal_side(h, b), int(o["AL_maxiter"]), _gap_primal, (50, 100),
+                  "ManiSDP: optimum = %0.8f, time = %0.2fs")
+        obj, data, (Yb, y, _, _, _, _, _) = _al_loop(h, o, t, geo.start(rng, p), p, np.zeros(b.size), verbose)
+        S = geo.S                                          # data.S (:158): the blocks of the last iterate
+        if geo.eig_device and Yb is not None:
+            S = [h.get_dual_slack_block(geo.r0[i], nset[i]) for i in range(len(nset))]
     finally:
         h.close()
-    if Y_eval is not None:
-        X = [Yi @ Yi.T for Yi in Y_eval]                    # :65-69, 156
-    data.update({"Y": Y_eval, "X": X, "y": y, "S": S, "gap": gap, "pinf": pinf, "dinf": dinf, "gradnorm": gradnorm,
-                 "time": time.time() - t0, "sigma": sigma, "p": [Yi.shape[1] for Yi in (Y_eval or [])]})
-    if data["status"] == 0 and eta_kkt > o["tol"]:
-        data["status"] = 1
-        _say(verbose, "Iteration maximum is reached!")
-    _say(verbose, "ManiSDP: optimum = %0.8f, time = %0.2fs" % (obj, time.time() - t0))
-    return Y_eval, obj, data
+    data.update({"X": ([Yi @ Yi.T for Yi in Yb] if Yb is not None else None), "y": y, "S": S,   # :65-69, 156
+                 "p": [Yi.shape[1] for Yi in (Yb or [])]})
+    return Yb, obj, data
 
 
-# ================================================================= dual approach, unit diagonal
+# ================================================================= dual approach
 DEFAULTS["dual_unitdiag"] = dict(ADMM_maxiter=300, gama=2, sigma0=1e-3, sigma_min=1e-3, sigma_max=1e7, tol=1e-8, theta=1e-3,
                                  delta=8, alpha=0.1, tolgradnorm=1e-8, TR_maxinner=20, TR_maxiter=4, tau1=1e1, tau2=1e2,
                                  line_search=0)      # ManiDSDP_unitdiag.m:10-26 (+ p0 = ceil(log(m)), :11)
 DATA_FIELDS["dual_unitdiag"] = ("X", "y", "S", "w", "gap", "pinf", "dinf", "gradnorm", "time", "fac_size", "seta", "status")   # :132-144
+
+
+def _dual_matrices(A, c, nf, o):
+    """[B A_psd] and c = [cf; c_psd] split at the K['f'] free columns (ManiDSDP_unitdiag.m:32-37); dAAt = options['dAAt'],
+    default diag(A_psd A_psd') (:37), as a flat float64 vector (the bytes the handle reads)."""
+    call = _dense_vec(c)
+    Aall = sp.csc_matrix(A)
+    B = Aall[:, :nf]; Apsd = sp.csr_matrix(Aall[:, nf:])
+    dAAt = o.get("dAAt", None)
+    if dAAt is None:
+        dAAt = np.asarray(Apsd.multiply(Apsd).sum(axis=1)).ravel()
+    return call, (B if nf else None), Apsd, call[nf:], _dense_vec(dAAt)
 
 
 def ManiDSDP_unitdiag(A, b, c, K, options=None, verbose=True, rng=None):
@@ -839,139 +954,35 @@ def ManiDSDP_unitdiag(A, b, c, K, options=None, verbose=True, rng=None):
 
 
 def _dual_unitdiag_impl(A, b, c, K, options, verbose, rng):
-    o = dict(options or {})
-    for k, v in DEFAULTS["dual_unitdiag"].items():
-        o.setdefault(k, v)
+    o = _with_defaults(options, DEFAULTS["dual_unitdiag"])
     n = int(K["s"]); nf = int(K.get("f", 0))
     b = _dense_vec(b)
-    call = _dense_vec(c)
     m = b.size
     o.setdefault("p0", int(math.ceil(math.log(m))))        # :11
     rng = rng or np.random.default_rng(0)
     _say(verbose, "ManiSDP is starting...")
     _say(verbose, f"SDP size: n = {n}, m = {m}")
-    normc = 1.0 + np.linalg.norm(call)                     # :32
-    Aall = sp.csc_matrix(A)
-    B = Aall[:, :nf]; Apsd = sp.csr_matrix(Aall[:, nf:])   # :33-34
-    cf = call[:nf]; cpsd = call[nf:]                       # :35-36
-    dAAt = o.get("dAAt", None)
-    if dAAt is None:
-        dAAt = np.asarray(Apsd.multiply(Apsd).sum(axis=1)).ravel()      # :37
+    call, B, Apsd, cpsd, dAAt = _dual_matrices(A, c, nf, o)
     # eig(X) (:82): the reference's dense eig on the host up to n = 600 (0.5 ms there), beyond that the device escape on
     # the resident X with the independent lambda_min check before the solve may stop (d = 60, n = 1831: 1.6 s instead of 5.0 s)
-    dense_max = int(o.get("dense_eig_max", 600))
-    eig_mode = o.get("eig", "host" if n <= dense_max else "device")
+    eig_mode = o.get("eig", "host" if n <= int(o.get("dense_eig_max", 600)) else "device")
     p = int(o["p0"])
-    delta = int(o["delta"])
-    h = _lib.Handle.dual_unitdiag(Apsd, b, cpsd, dAAt, B if nf else None, cf, pcap=max(32, p + 2 * delta))
-    topts = _rtr_opts(o)
-    sigma = float(o["sigma0"]); gama = float(o["gama"])
-    w = np.zeros(nf)
-    Y = o.get("Y0", None)
-    if Y is None:                                          # trustregions.m:390-392 -> M.rand()
-        Y = rng.standard_normal((n, p))
-        Y /= np.sqrt(np.sum(Y * Y, axis=1, keepdims=True))
-    Y = np.ascontiguousarray(Y, dtype=np.float64)
-    U = None
-    data = {"status": 0, "hessvecs": 0, "cost_evals": 0, "rejected": 0, "rtr_seconds": 0.0, "eig_seconds": 0.0, "log": []}
-    fac_size, seta = [], []
-    t0 = time.time()
-    gap0 = pinf0 = dinf0 = None
-    obj = gap = pinf = dinf = gradnorm = eta = None
-    Y_eval = None
-    certified = True
+    h = _lib.Handle.dual_unitdiag(Apsd, b, cpsd, dAAt, B, call[:nf], pcap=max(32, p + 2 * int(o["delta"])))
     try:
-        for it in range(1, int(o["ADMM_maxiter"]) + 1):    # :62
-            fac_size.append(p)
-            h.dual_set_penalty(sigma, w)
-            h.set_point(Y)
-            if U is not None:
-                _line_search(h, U)                         # :65-67, 164-172
-            st = h.rtr(topts)                              # :68
-            data["rtr_seconds"] += st.seconds
-            data["hessvecs"] += st.hessvecs; data["cost_evals"] += st.cost_evals; data["rejected"] += st.rejected
-            gradnorm = st.gradnorm                         # :69
-            Y = h.get_point()
-            Y_eval = Y
-            by, cex, as2, Af, z = h.dual_outer_step()      # :70-81 (x <- x - sigma*As on the device)
-            pinf = (math.sqrt(as2) + float(np.linalg.norm(Af))) / normc      # :75
-            w = w - sigma * Af                             # :78
-            obj = cex + float(cf @ w) + float(np.sum(z))   # :85
-            t1 = time.time()
-            certified = True
-            if eig_mode == "host":
-                Xd = h.get_dual_slack()
-                dX, vX = np.linalg.eigh(0.5 * (Xd + Xd.T)) # :82
-                lam_min, lam_max = float(dX[0]), float(dX[-1])
-                nneg = int(np.sum(dX < 0))
-            else:
-                lam, vX, lam_max, _, certified = _device_escape(
-                    h, lambda tol, maxit: h.escape_eigs_dual(delta, tol=tol, maxit=maxit), o, data, 1e-10, 20000)
-                lam_min = float(lam[0])
-                nneg = int(np.sum(lam < 0))
-            dinf = max(0.0, -lam_min) / (1.0 + abs(lam_max))     # :86
-            if eig_mode != "host" and certified and (dinf < o["tol"] or it == int(o["ADMM_maxiter"])):
-                lam_v, v_v, lmax_v, certified = _verify_lambda_min(
-                    h, lambda tol, maxit: h.escape_eigs_dual(1, tol=tol, maxit=maxit), o, data, 1e-10, 20000, dense_n=n)
-                dinf_v = max(0.0, -lam_v) / (1.0 + abs(lmax_v))
-                if dinf_v >= o["tol"] > dinf:
-                    vX = np.hstack([v_v, vX[:, :max(delta - 1, 0)]])
-                    nneg = max(nneg, 1)
-                dinf = dinf_v
-            data["eig_seconds"] += time.time() - t1
-            gap = abs(obj - by) / (1.0 + abs(obj) + abs(by))     # :87
-            if _RANK_CUT_SVD:
-                _, e, Qt = np.linalg.svd(Y, full_matrices=False); Q = Qt.T
-            else:
-                Q, e, _ = _thin_svd_rank(Y, float(o["theta"]))
-            r = int(np.sum(e > float(o["theta"]) * e[0]))  # :88-90 (strict, unlike the primal entry points)
-            _say(verbose, "Iter %d, obj:%0.8f, gap:%0.1e, pinf:%0.1e, dinf:%0.1e, gradnorm:%0.1e, r:%d, p:%d, sigma:%0.3f, time:%0.2fs"
-                 % (it, obj, gap, pinf, dinf, gradnorm, r, p, sigma, time.time() - t0))
-            data["log"].append((obj, gap, pinf, dinf, gradnorm, r, p, sigma))
-            eta = max(gap, pinf, dinf)                     # :93
-            seta.append(eta)
-            data["iters"] = it
-            if eta < o["tol"] and certified:
-                _say(verbose, "Optimality is reached!")
-                break
-            if it % 50 == 0:                               # :99-109
-                if it > 100 and gap > gap0 and pinf > pinf0 and dinf > dinf0:
-                    data["status"] = 2
-                    _say(verbose, "Slow progress!")
-                    break
-                gap0, pinf0, dinf0 = gap, pinf, dinf
-            if r <= p - 1:                                 # :110-113
-                Y = _rank_cut(Y, Q, e, r)
-                p = r
-            nne = max(min(nneg, delta), 1)                 # :114
-            if o["line_search"] == 1:
-                U = np.hstack([np.zeros((n, p)), vX[:, :nne]])   # :116
-            p = p + nne
-            if o["line_search"] == 1:
-                Y = np.hstack([Y, np.zeros((n, nne))])     # :120
-            else:
-                Y = np.hstack([Y, o["alpha"] * vX[:, :nne]])     # :122-123
-                Y = Y / np.sqrt(np.sum(Y * Y, axis=1, keepdims=True))
-            Y = np.ascontiguousarray(Y)
-            if pinf < o["tau1"] * gradnorm:                # :125-129
-                sigma = max(sigma / gama, float(o["sigma_min"]))
-            elif pinf > o["tau2"] * gradnorm:
-                sigma = min(sigma * gama, float(o["sigma_max"]))
+        geo = _OneFactor(h, o, n, _rows, _eig_host if eig_mode == "host" else _eig_device, _dinf_abs, strict_rank=True,
+                         nne_floor=1, miss_nneg=lambda lam, nneg: max(nneg, 1))          # :114
+        t = _Kind(geo, _dual_side(h, call, nf), int(o["ADMM_maxiter"]), _gap_dual, (50, 100),   # :99-109
+                  "ManiDSDP: optimum = %0.8f, time = %0.2fs", verify=eig_mode != "host", log=slice(1, -1))
+        obj, data, (Y, w, _, _, _, fac_size, seta) = _al_loop(h, o, t, geo.start(rng, p), p, np.zeros(nf), verbose)
         X = h.get_dual_slack() if obj is not None else None
         y = h.dual_get_y() if obj is not None else None
     finally:
         h.close()
-    data.update({"X": X, "y": y, "S": (Y_eval @ Y_eval.T if Y_eval is not None and n <= int(o.get("dense_X_max", 4000)) else None),
-                 "w": w, "gap": gap, "pinf": pinf, "dinf": dinf, "gradnorm": gradnorm, "time": time.time() - t0,
-                 "fac_size": fac_size, "seta": seta, "Y": Y_eval, "sigma": sigma})
-    if data["status"] == 0 and (eta is None or eta > o["tol"] or not certified):
-        data["status"] = 1
-        _say(verbose, "Iteration maximum is reached!")
-    _say(verbose, "ManiDSDP: optimum = %0.8f, time = %0.2fs" % (obj, time.time() - t0))
+    data.update({"X": X, "y": y, "S": (Y @ Y.T if Y is not None and n <= int(o.get("dense_X_max", 4000)) else None),
+                 "w": w, "fac_size": fac_size, "seta": seta})
     return X, obj, data
 
 
-# ===================================================================== dual approach, generic
 DEFAULTS["dual"] = dict(p0=1, ADMM_maxiter=1000, gama=2, sigma0=1e-1, sigma_min=1e-2, sigma_max=1e7, tol=1e-8, theta=1e-2,
                         delta=8, alpha=0.01, tolgradnorm=1e-8, TR_maxinner=20, TR_maxiter=4, tau1=0.1, tau2=1,
                         line_search=1)       # ManiDSDP.m:10-25
@@ -990,136 +1001,35 @@ def ManiDSDP(A, b, c, K, options=None, verbose=True, rng=None):
 
 
 def _dual_impl(A, b, c, K, options, verbose, rng):
-    o = dict(options or {})
-    for k, v in DEFAULTS["dual"].items():
-        o.setdefault(k, v)
+    o = _with_defaults(options, DEFAULTS["dual"])
     n = int(K["s"]); nf = int(K.get("f", 0))
     b = _dense_vec(b)
-    call = _dense_vec(c)
-    m = b.size
     rng = rng or np.random.default_rng(0)
     _say(verbose, "ManiSDP is starting...")                # :28-29
-    _say(verbose, f"SDP size: n = {n}, m = {m}")
-    normc = 1.0 + np.linalg.norm(call)                     # :31
-    Aall = sp.csc_matrix(A)
-    B = Aall[:, :nf]; Apsd = sp.csr_matrix(Aall[:, nf:])   # :32-33
-    cf = call[:nf]; cpsd = call[nf:]                       # :34-35
-    dAAt = o.get("dAAt", None)
-    if dAAt is None:
-        dAAt = np.asarray(Apsd.multiply(Apsd).sum(axis=1)).ravel()      # :37
-    dAAt = _dense_vec(dAAt)
+    _say(verbose, f"SDP size: n = {n}, m = {b.size}")
+    call, B, Apsd, cpsd, dAAt = _dual_matrices(A, c, nf, o)
     # eig(X) (:76) as in ManiDSDP_unitdiag: the host's dense eig up to n = 600, the device escape with the independent
     # lambda_min check beyond
-    dense_max = int(o.get("dense_eig_max", 600))
-    eig_mode = o.get("eig", "host" if n <= dense_max else "device")
+    eig_mode = o.get("eig", "host" if n <= int(o.get("dense_eig_max", 600)) else "device")
     p = int(o["p0"])
-    delta = int(o["delta"])
-    h = _lib.Handle.dual(Apsd, b, cpsd, dAAt, B if nf else None, cf, pcap=max(32, p + 2 * delta))
-    topts = _rtr_opts(o)
-    sigma = float(o["sigma0"]); gama = float(o["gama"])
-    w = np.zeros(nf)
-    Y = o.get("Y0", None)
-    if Y is None:                                          # trustregions.m:390-392 -> euclideanfactory rand = randn(n, p)
-        Y = rng.standard_normal((n, p))
-    Y = np.asfortranarray(Y, dtype=np.float64)
-    U = None
-    data = {"status": 0, "hessvecs": 0, "cost_evals": 0, "rejected": 0, "rtr_seconds": 0.0, "eig_seconds": 0.0, "log": [],
-            "g_identity": h.dual_g_identity(), "p_max": p}
-    t0 = time.time()
-    gap0 = pinf0 = dinf0 = None
-    obj = gap = pinf = dinf = gradnorm = eta = None
-    Y_eval = None
-    certified = True
+    h = _lib.Handle.dual(Apsd, b, cpsd, dAAt, B, call[:nf], pcap=max(32, p + 2 * int(o["delta"])))
     try:
-        for it in range(1, int(o["ADMM_maxiter"]) + 1):    # :59
-            h.dual_set_penalty(sigma, w)
-            h.set_point(Y)
-            if U is not None:
-                _line_search(h, U)                         # :61-63, 150-160 (Y + alpha*U, no normalisation)
-            st = h.rtr(topts)                              # :64
-            data["rtr_seconds"] += st.seconds
-            data["hessvecs"] += st.hessvecs; data["cost_evals"] += st.cost_evals; data["rejected"] += st.rejected
-            gradnorm = st.gradnorm                         # :65
-            Y = h.get_point()
-            Y_eval = Y
-            by, cex, as2, Af, _ = h.dual_outer_step()      # :66-77 (x updated on the device, X = mat(x + bA) kept there)
-            pinf = (math.sqrt(as2) + float(np.linalg.norm(Af))) / normc      # :71
-            w = w - sigma * Af                             # :74
-            obj = cex + float(cf @ w)                      # :77
-            t1 = time.time()
-            certified = True
-            if eig_mode == "host":
-                Xd = h.get_dual_slack()
-                dX, vX = np.linalg.eigh(0.5 * (Xd + Xd.T)) # :76
-                lam_min, lam_max = float(dX[0]), float(dX[-1])
-                nneg = int(np.sum(dX < 0))
-            else:
-                lam, vX, lam_max, _, certified = _device_escape(
-                    h, lambda tol, maxit: h.escape_eigs_dual(delta, tol=tol, maxit=maxit), o, data, 1e-10, 20000)
-                lam_min = float(lam[0])
-                nneg = int(np.sum(lam < 0))
-            dinf = max(0.0, -lam_min) / (1.0 + abs(lam_max))     # :78
-            if eig_mode != "host" and certified and (dinf < o["tol"] or it == int(o["ADMM_maxiter"])):
-                lam_v, v_v, lmax_v, certified = _verify_lambda_min(
-                    h, lambda tol, maxit: h.escape_eigs_dual(1, tol=tol, maxit=maxit), o, data, 1e-10, 20000, dense_n=n)
-                dinf_v = max(0.0, -lam_v) / (1.0 + abs(lmax_v))
-                if dinf_v >= o["tol"] > dinf:
-                    vX = np.hstack([v_v, vX[:, :max(delta - 1, 0)]])
-                    nneg = max(nneg, 1)
-                dinf = dinf_v
-            data["eig_seconds"] += time.time() - t1
-            gap = abs(obj - by) / (1.0 + abs(obj) + abs(by))     # :79
-            if _RANK_CUT_SVD:
-                _, e, Qt = np.linalg.svd(Y, full_matrices=False); Q = Qt.T
-            else:
-                Q, e, _ = _thin_svd_rank(Y, float(o["theta"]))
-            r = int(np.sum(e > float(o["theta"]) * e[0]))  # :80-86 (strict)
-            _say(verbose, "Iter %d, obj:%0.8f, gap:%0.1e, pinf:%0.1e, dinf:%0.1e, gradnorm:%0.1e, r:%d, p:%d, sigma:%0.3f, time:%0.2fs"
-                 % (it, obj, gap, pinf, dinf, gradnorm, r, p, sigma, time.time() - t0))
-            data["log"].append((obj, gap, pinf, dinf, gradnorm, r, p, sigma))
-            eta = max(gap, pinf, dinf)                     # :89
-            data["iters"] = it
-            if eta < o["tol"] and certified:
-                _say(verbose, "Optimality is reached!")
-                break
-            if it % 20 == 0:                               # :94-104
-                if it > 50 and gap > gap0 and pinf > pinf0 and dinf > dinf0:
-                    data["status"] = 2
-                    _say(verbose, "Slow progress!")
-                    break
-                gap0, pinf0, dinf0 = gap, pinf, dinf
-            if r <= p - 1:                                 # :105-108: Y = V(:,1:r)*diag(e(1:r))
-                Y = _rank_cut(Y, Q, e, r)
-                p = r
-            nne = min(nneg, delta)                         # :109 (no lower bound)
-            if o["line_search"] == 1:
-                U = np.hstack([np.zeros((n, p)), vX[:, :nne]])   # :111
-            p = p + nne
-            data["p_max"] = max(data["p_max"], p)
-            if o["line_search"] == 1:
-                Y = np.hstack([Y, np.zeros((n, nne))])     # :115
-            else:
-                Y = np.hstack([Y, o["alpha"] * vX[:, :nne]])     # :117
-            Y = np.asfortranarray(Y)
-            if pinf < o["tau1"] * gradnorm:                # :119-123
-                sigma = max(sigma / gama, float(o["sigma_min"]))
-            elif pinf > o["tau2"] * gradnorm:
-                sigma = min(sigma * gama, float(o["sigma_max"]))
+        g_identity = h.dual_g_identity()
+        geo = _OneFactor(h, o, n, _euclidean, _eig_host if eig_mode == "host" else _eig_device, _dinf_abs, strict_rank=True,
+                         nne_floor=0, miss_nneg=lambda lam, nneg: max(nneg, 1),     # :109 (no lower bound)
+                         layout=np.asfortranarray)
+        t = _Kind(geo, _dual_side(h, call, nf), int(o["ADMM_maxiter"]), _gap_dual, (20, 50),   # :94-104
+                  "ManiDSDP: optimum = %0.8f, time = %0.2fs", verify=eig_mode != "host", log=slice(1, -1))
+        obj, data, (Y, w, _, _, p, fac_size, _) = _al_loop(h, o, t, geo.start(rng, p), p, np.zeros(nf), verbose)
         X = h.get_dual_slack() if obj is not None else None
         y = h.dual_get_y() if obj is not None else None
     finally:
         h.close()
-    data.update({"X": X, "y": y, "S": (Y_eval @ Y_eval.T if Y_eval is not None and n <= int(o.get("dense_X_max", 4000)) else None),
-                 "w": w, "gap": gap, "pinf": pinf, "dinf": dinf, "gradnorm": gradnorm, "time": time.time() - t0,
-                 "Y": Y_eval, "sigma": sigma})
-    if data["status"] == 0 and (eta is None or eta > o["tol"] or not certified):
-        data["status"] = 1
-        _say(verbose, "Iteration maximum is reached!")
-    _say(verbose, "ManiDSDP: optimum = %0.8f, time = %0.2fs" % (obj, time.time() - t0))   # :139
+    data.update({"X": X, "y": y, "S": (Y @ Y.T if Y is not None and n <= int(o.get("dense_X_max", 4000)) else None),
+                 "w": w, "g_identity": g_identity, "p_max": max(fac_size + [p])})
     return X, obj, data
 
 
-# ===================================================================== dual approach, multiblock
 DEFAULTS["dual_multiblock"] = dict(min_facsize=2, ADMM_maxiter=1000, gama=2, sigma0=1e-1, sigma_min=1e-2, sigma_max=1e7, tol=1e-8,
                                    theta=1e-2, delta=8, alpha=0.2, tolgradnorm=1e-8, TR_maxinner=20, TR_maxiter=4, tau1=1e1,
                                    tau2=1e1, line_search=1)       # ManiDSDP_multiblock.m:12-28 (+ p0 = ones, :13)
@@ -1140,148 +1050,25 @@ def ManiDSDP_multiblock(A, b, c, K, options=None, verbose=True, rng=None):
 
 
 def _dual_multiblock_impl(A, b, c, K, options, verbose, rng):
-    o = dict(options or {})
-    for k, v in DEFAULTS["dual_multiblock"].items():
-        o.setdefault(k, v)
+    o = _with_defaults(options, DEFAULTS["dual_multiblock"])
     nset = [int(v) for v in np.atleast_1d(K["s"])]
-    nb = len(nset)
-    nob = int(K.get("nob", 0))
-    nf = int(K.get("f", 0))
+    nob = int(K.get("nob", 0)); nf = int(K.get("f", 0))
     b = _dense_vec(b)
-    call = _dense_vec(c)
-    m = b.size
-    p0 = [int(v) for v in np.atleast_1d(o.get("p0", np.ones(nb, int)))]
     rng = rng or np.random.default_rng(0)
     _say(verbose, "ManiSDP is starting...")                # :30-31
-    _say(verbose, f"SDP size: n = {max(nset)}, m = {m}")
-    normc = 1.0 + np.linalg.norm(call)                     # :33
-    Aall = sp.csc_matrix(A)
-    B = Aall[:, :nf]; Apsd = sp.csr_matrix(Aall[:, nf:])   # :34-42
-    cf = call[:nf]; cpsd = call[nf:]
-    dAAt = o.get("dAAt", None)
-    if dAAt is None:
-        dAAt = np.asarray(Apsd.multiply(Apsd).sum(axis=1)).ravel()      # :44
-    dAAt = _dense_vec(dAAt)
-    r0 = np.concatenate([[0], np.cumsum(nset)]).astype(int)
-    N = int(r0[-1])
-    p = [p0[i] if nset[i] >= o["min_facsize"] else nset[i] for i in range(nb)]        # :50-55
-    delta = int(o["delta"])
-    h = _lib.Handle.dual_multiblock(Apsd, b, cpsd, dAAt, nset, nob, B if nf else None, cf, pcap=max(32, max(p) + 2 * delta))
-    be = o.get("block_eig", "auto")                        # as ManiSDP_multiblock
-    block_eig_device = be == "device" or (be == "auto" and nb >= 16 and max(nset) <= 256)
-    sigma = float(o["sigma0"]); gama = float(o["gama"])
-    w = np.zeros(nf)
-
-    def normalise(Yi, i):
-        return Yi / np.sqrt(np.sum(Yi * Yi, axis=1, keepdims=True)) if i < nob else Yi
-
-    Yb = o.get("Y0", None)
-    if Yb is None:                                         # trustregions.m:390-392 -> M.rand() (randc.cpp)
-        Yb = [normalise(rng.standard_normal((nset[i], p[i])), i) for i in range(nb)]
-    Yb = [np.ascontiguousarray(Yi, dtype=np.float64) for Yi in Yb]
-    Ub = None
-    data = {"status": 0, "hessvecs": 0, "cost_evals": 0, "rejected": 0, "rtr_seconds": 0.0, "eig_seconds": 0.0, "log": []}
-    t0 = time.time()
-    gap0 = pinf0 = dinf0 = None
-    obj = gap = pinf = dinf = gradnorm = eta = None
-    X = y = Y_eval = None
+    _say(verbose, f"SDP size: n = {max(nset)}, m = {b.size}")
+    call, B, Apsd, cpsd, dAAt = _dual_matrices(A, c, nf, o)    # :33-44
+    p = _block_widths(o, nset)                             # :50-55
+    h = _lib.Handle.dual_multiblock(Apsd, b, cpsd, dAAt, nset, nob, B, call[:nf], pcap=max(32, max(p) + 2 * int(o["delta"])))
     try:
-        for it in range(1, int(o["ADMM_maxiter"]) + 1):    # :79
-            pmax = max(p)
-            tdist = math.sqrt(math.pi * sum(nset[:nob]) + sum(pi * ni for pi, ni in zip(p[nob:], nset[nob:])))   # multiblockmanifold.m:11-15
-            topts = _lib.default_opts(maxiter=int(o["TR_maxiter"]), maxinner=int(o["TR_maxinner"]),
-                                      tolgradnorm=float(o["tolgradnorm"]), Delta_bar=tdist)
-            h.dual_set_penalty(sigma, w)
-            h.set_point(_pack_blocks(Yb, r0, N, pmax))
-            if Ub is not None:
-                _line_search(h, _pack_blocks(Ub, r0, N, pmax))   # :81-83, 220-241 (Y_i + alpha*U_i)
-            st = h.rtr(topts)                              # :84
-            data["rtr_seconds"] += st.seconds
-            data["hessvecs"] += st.hessvecs; data["cost_evals"] += st.cost_evals; data["rejected"] += st.rejected
-            gradnorm = st.gradnorm                         # :85
-            Yfull = h.get_point()
-            Yb = [np.ascontiguousarray(Yfull[r0[i]:r0[i + 1], :p[i]]) for i in range(nb)]
-            Y_eval = Yb
-            by, cex, as2, Af, z = h.dual_outer_step()      # :86-124 (x, X_i - diag(z_i) on the device)
-            pinf = (math.sqrt(as2) + float(np.linalg.norm(Af))) / normc     # :95-100
-            w = w - sigma * Af                             # :108
-            obj = cex + float(cf @ w) + float(np.sum(z))   # :109, 117 (<c, x + bA>)
-            t1 = time.time()
-            vX, dX, dinfs = [], [], []
-            if block_eig_device:
-                try:
-                    wall, Vall = h.block_eigs(r0[:-1], nset, delta)
-                except _lib.MsdpError:
-                    if be == "device":
-                        raise
-                    block_eig_device = False
-            if block_eig_device:
-                for i in range(nb):
-                    wv = wall[r0[i]:r0[i + 1]]
-                    dX.append(wv); vX.append(Vall[r0[i]:r0[i + 1], :])
-                    dinfs.append(max(0.0, -wv[0]) / (1.0 + abs(wv[-1])))   # :122
-            else:
-                for i in range(nb):                        # :121
-                    Xi = h.get_dual_slack_block(r0[i], nset[i])
-                    wv, V = np.linalg.eigh(0.5 * (Xi + Xi.T))
-                    dX.append(wv); vX.append(V)
-                    dinfs.append(max(0.0, -wv[0]) / (1.0 + abs(wv[-1])))   # :122
-            data["eig_seconds"] += time.time() - t1
-            dinf = max(dinfs)                              # :124
-            gap = abs(obj - by) / (1.0 + abs(obj) + abs(by))     # :125
-            _say(verbose, "Iter %d, obj:%0.8f, gap:%0.1e, pinf:%0.1e, dinf:%0.1e, gradnorm:%0.1e, p_max:%d, sigma:%0.3f, time:%0.2fs"
-                 % (it, obj, gap, pinf, dinf, gradnorm, max(p), sigma, time.time() - t0))
-            data["log"].append((it, obj, gap, pinf, dinf, gradnorm, max(p), sigma, time.time() - t0))
-            eta = max(gap, pinf, dinf)                     # :128
-            data["iters"] = it
-            if eta < o["tol"]:
-                _say(verbose, "Optimality is reached!")
-                break
-            if it % 50 == 0:                               # :133-143
-                if it > 100 and gap > gap0 and pinf > pinf0 and dinf > dinf0:
-                    data["status"] = 2
-                    _say(verbose, "Slow progress!")
-                    break
-                gap0, pinf0, dinf0 = gap, pinf, dinf
-            newY, newU = [], []
-            for i, n in enumerate(nset):                   # :144-181
-                Yi = Yb[i]
-                Ui = None
-                if n >= o["min_facsize"]:
-                    if p[i] > 1:
-                        Q, e, r = _thin_svd_rank(Yi, float(o["theta"]))   # :146-155 (r = sum(e > theta*e(1)), at least 1)
-                        r = max(int(np.sum(e > float(o["theta"]) * e[0])), 1)
-                        if r < p[i]:
-                            Yi = _rank_cut(Yi, Q, e, r)    # :156-159
-                            p[i] = r
-                    nneg = int(np.sum(dX[i] < 0))
-                    nne = max(min(nneg, delta), 1) if i < nob else min(nneg, delta)   # :160-164
-                    if p[i] + nne > n:
-                        nne = 0                            # :165-167
-                    if o["line_search"] == 1:
-                        Ui = np.hstack([np.zeros((n, p[i])), vX[i][:, :nne]])    # :169
-                        Yi = np.hstack([Yi, np.zeros((n, nne))])                 # :173
-                    else:
-                        Yi = normalise(np.hstack([Yi, o["alpha"] * vX[i][:, :nne]]), i)   # :175-178
-                    p[i] = p[i] + nne                      # :171
-                newY.append(np.ascontiguousarray(Yi))
-                newU.append(Ui if Ui is not None else np.zeros_like(Yi))
-            Yb = newY
-            Ub = newU if o["line_search"] == 1 else None
-            if pinf < o["tau1"] * gradnorm:                # :182-186
-                sigma = max(sigma / gama, float(o["sigma_min"]))
-            elif pinf > o["tau2"] * gradnorm:
-                sigma = min(sigma * gama, float(o["sigma_max"]))
-        if obj is not None:
-            X = [h.get_dual_slack_block(r0[i], nset[i]) for i in range(nb)]
-            y = h.dual_get_y()
+        geo = _Blocks(h, o, nset, nob, strict_rank=True)  # :146-155 (r = sum(e > theta*e(1)), at least 1)
+        t = _Kind(geo, _dual_side(h, call, nf), int(o["ADMM_maxiter"]), _gap_dual, (50, 100),   # :133-143
+                  "ManiDSDP: optimum = %0.8f, time = %0.2fs")
+        obj, data, (Yb, w, _, _, _, _, _) = _al_loop(h, o, t, geo.start(rng, p), p, np.zeros(nf), verbose)
+        X = [h.get_dual_slack_block(geo.r0[i], nset[i]) for i in range(len(nset))] if obj is not None else None
+        y = h.dual_get_y() if obj is not None else None
     finally:
         h.close()
-    data.update({"X": X, "y": y, "S": ([Yi @ Yi.T for Yi in Y_eval] if Y_eval is not None else None), "w": w, "gap": gap,
-                 "pinf": pinf, "dinf": dinf, "gradnorm": gradnorm, "time": time.time() - t0, "Y": Y_eval, "sigma": sigma,
-                 "p": [Yi.shape[1] for Yi in (Y_eval or [])]})
-    if data["status"] == 0 and (eta is None or eta > o["tol"]):
-        data["status"] = 1
-        _say(verbose, "Iteration maximum is reached!")
-    _say(verbose, "ManiDSDP: optimum = %0.8f, time = %0.2fs" % (obj, time.time() - t0))   # :202
+    data.update({"X": X, "y": y, "S": ([Yi @ Yi.T for Yi in Yb] if Yb is not None else None), "w": w,
+                 "p": [Yi.shape[1] for Yi in (Yb or [])]})
     return X, obj, data

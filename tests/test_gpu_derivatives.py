@@ -99,3 +99,85 @@ def test_fd_generic(lib):
     h, Y, U = _affine(lib, lib.KIND_GENERIC, "mcp100", 5, 0.7, 3)
     _fd_check(h, 0.3 * Y, U)
     h.close()
+
+
+# ---- the dual kinds.  The penalty (sigma, w) is set first, and one outer step at another point moves the device-resident
+# multiplier x away from 0, so every term of the cost is live; the outer step spends the penalty, so it is set again.
+def _dual_penalised(h, Y0, sigma, w):
+    h.dual_set_penalty(sigma, w)
+    h.set_point(Y0)
+    h.dual_outer_step()
+    h.dual_set_penalty(sigma, w)
+
+
+def _split(A, c, nf):
+    Ac = sp.csc_matrix(A)
+    return sp.csr_matrix(Ac[:, nf:]), Ac[:, :nf], c[nf:], c[:nf]
+
+
+@pytest.mark.parametrize("p", [7, 70])
+def test_fd_dual_unitdiag(lib, p):
+    from manisdp_matlab_amd import problems
+    rng = np.random.default_rng(p)
+    d = 8
+    Q = rng.standard_normal((d, d)); Q = (Q + Q.T) / 2
+    A, b, c, K, dAAt, _ = problems.bqpsos_dual_problem(Q, rng.standard_normal(d), d)
+    n, nf = K["s"], K["f"]
+    Apsd, B, cp, cf = _split(A, c, nf)
+    h = lib.Handle.dual_unitdiag(Apsd, b, cp, dAAt, B, cf, pcap=p)
+    def point():
+        Y = rng.standard_normal((n, p)); return Y / np.linalg.norm(Y, axis=1, keepdims=True)
+    _dual_penalised(h, point(), 0.6, 0.2 * rng.standard_normal(nf))
+    _fd_check(h, point(), rng.standard_normal((n, p)))
+    h.close()
+
+
+@pytest.mark.parametrize("p", [5, 70])
+def test_fd_dual_generic(lib, p):
+    from manisdp_matlab_amd import problems
+    d = 6
+    rng = np.random.default_rng(p)
+    A, b, c, K, dAAt = problems.qssos(d, rng.standard_normal(problems.get_basis(d, 4).shape[1]))
+    b = b / np.max(np.abs(b))
+    n, nf = K["s"], K["f"]
+    Apsd, B, cp, cf = _split(A, c, nf)
+    h = lib.Handle.dual(Apsd, b, cp, dAAt, B, cf, pcap=p)
+    _dual_penalised(h, rng.standard_normal((n, p)) / np.sqrt(p), 0.4, 0.1 * rng.standard_normal(nf))
+    _fd_check(h, rng.standard_normal((n, p)) / np.sqrt(p), rng.standard_normal((n, p)))
+    h.close()
+
+
+@pytest.mark.parametrize("widths", [[9, 5, 1, 2], [70, 3, 1, 2]])
+def test_fd_dual_multiblock(lib, widths):
+    """Blocks of order 70 / 6 / 1 / 5, the first two oblique (the generic closures, nob < nb); zero beyond each block's width."""
+    nset, nob, nf, m = [70, 6, 1, 5], 2, 2, 40
+    rng = np.random.default_rng(sum(widths))
+    off = np.concatenate([[0], np.cumsum([k * k for k in nset])])
+    rows = []
+    for _ in range(m):
+        v = np.zeros(off[-1])
+        for blk in rng.choice(len(nset), size=2):
+            k = nset[blk]
+            Mk = np.zeros((k, k))
+            for _ in range(3):
+                i, j = rng.integers(0, k, 2)
+                a = rng.standard_normal()
+                Mk[i, j] += a; Mk[j, i] += a
+            v[off[blk]:off[blk + 1]] += Mk.ravel(order="F")
+        rows.append(v)
+    Apsd = sp.csr_matrix(np.array(rows))
+    B = sp.csr_matrix(rng.standard_normal((m, nf)) * (rng.random((m, nf)) < 0.6))
+    cp = np.concatenate([(lambda C: 0.2 * (C + C.T))(rng.standard_normal((k, k))).ravel(order="F") for k in nset])
+    dAAt = np.asarray(Apsd.multiply(Apsd).sum(axis=1)).ravel()
+    h = lib.Handle.dual_multiblock(Apsd, rng.standard_normal(m), cp, dAAt, nset, nob, B, rng.standard_normal(nf),
+                                   pcap=max(widths))
+    r0 = np.concatenate([[0], np.cumsum(nset)])
+    def packed(unit):
+        Y = np.zeros((r0[-1], max(widths)))
+        for i, (k, w) in enumerate(zip(nset, widths)):
+            Yi = rng.standard_normal((k, w))
+            Y[r0[i]:r0[i + 1], :w] = Yi / np.linalg.norm(Yi, axis=1, keepdims=True) if (unit and i < nob) else Yi
+        return Y
+    _dual_penalised(h, packed(True), 0.5, 0.2 * rng.standard_normal(nf))
+    _fd_check(h, packed(True), packed(False))
+    h.close()

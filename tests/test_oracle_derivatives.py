@@ -59,6 +59,37 @@ def test_fd_unittrace():
     _fd_check(prob, Y, U, prob.M.retr)
 
 
+@pytest.mark.parametrize("p", [3, 9])
+def test_fd_dual_unitdiag(p):
+    """_DualUnitDiagProblem (ManiDSDP_unitdiag.m:174-194), the reference of the GPU dual unit-diagonal tests, against its own
+    cost, with nonzero multipliers x, w.  Its gradient X = bA - sigma*As (:184) leaves out sigma*A'(D\\A As): that term is 0
+    only while A x = 0 (A A' = D here), which the outer step x <- x - sigma*As (:77) keeps, so x comes from one outer step."""
+    import scipy.sparse as sp
+    rng = np.random.default_rng(4 + p)
+    d = 6
+    Q = rng.standard_normal((d, d)); Q = (Q + Q.T) / 2
+    A, b, c, K, dAAt, _ = problems.bqpsos_dual_problem(Q, rng.standard_normal(d), d)
+    nf, n = K["f"], K["s"]
+    Ac = sp.csc_matrix(A)
+    prob = R._DualUnitDiagProblem(Ac[:, nf:], Ac[:, :nf], b, c[nf:], c[:nf], dAAt, n, p)
+    def point():
+        Y = rng.standard_normal((n, p)); return Y / np.linalg.norm(Y, axis=1, keepdims=True)
+    _, sc, y = prob.parts(point())
+    prob.x = -0.4 * (prob.At @ y - sc)
+    prob.w = 0.3 * rng.standard_normal(nf)
+    prob.sigma = 0.7
+    Y = point()
+    U = prob.M.proj(Y, rng.standard_normal((n, p)))
+    _fd_check(prob, Y, U, prob.M.retr)
+    # the Riemannian gradient is tangent, and <V, Hess U> = <U, Hess V> on the tangent space
+    prob.cost(Y)
+    G = prob.grad(Y)
+    assert np.linalg.norm(prob.M.proj(Y, G) - G) <= 1e-12 * max(1.0, np.linalg.norm(G))
+    V = prob.M.proj(Y, rng.standard_normal((n, p)))
+    a, b2 = float(np.sum(V * prob.hess(Y, U))), float(np.sum(U * prob.hess(Y, V)))
+    assert abs(a - b2) <= 1e-10 * max(1.0, abs(a), abs(b2))
+
+
 def test_tcg_stop_codes_and_trust_region():
     """tCG exits: with a tiny radius the first step hits the boundary (stop 2), |eta| = Delta."""
     from oracle import manopt_rtr

@@ -416,7 +416,13 @@ int msdp_get_dual_slack_block(msdp_handle h, int64_t row0, int64_t nb, double* S
  * msdp_get_dual_slack_block remains).  w: the eigenvalues, block after block, ascending inside a block (sum nblk values);
  * V: (sum nblk) x k row-major, row = position in the concatenation of the blocks, column c = eigenvector of the block's c-th
  * smallest eigenvalue (zero columns beyond a block's order).  One workgroup per block (msdp_blockjacobi.hip); method 0 = Householder
- * tridiagonalisation + bisection + inverse iteration when k <= 8 (the way of LAPACK's dsyevx), else 1 = cyclic Jacobi; 2 = the former or an error. */
+ * tridiagonalisation + bisection + inverse iteration when k <= 8 (the way of LAPACK's dsyevx), else 1 = cyclic Jacobi; 2 = the
+ * tridiagonal method, MSDP_EUNSUPPORTED when k > 8.  Limits: 0 <= k <= 64 and method in {0, 1, 2} (MSDP_EINVAL otherwise, as for
+ * nb < 1 and a block outside the matrix); k = 0 returns the eigenvalues only and V may be NULL; a block with fewer than k rows has
+ * zeros in its columns beyond its order.  Vectors of eigenvalues closer than rounding resolves are an orthonormal basis of their
+ * common eigenspace.  MSDP_ESTATE before msdp_al_dual (msdp_dual_outer_step on the dual multiblock kind) has built the blocks, and
+ * when a Jacobi iteration has not converged in 40 sweeps.  Every check is made on the host before anything is launched, and the
+ * handle stays usable after a refusal. */
 int msdp_block_eigs(msdp_handle h, int32_t nb, const int64_t* row0, const int64_t* nblk, int32_t k, int32_t method, double* w, double* V);
 
 /* Run-time switches of one handle (production = the defaults; the tests and the profiling scripts use them):

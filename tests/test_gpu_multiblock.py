@@ -403,9 +403,10 @@ def test_thousand_blocks_of_order_60(lib, storage):
 
 
 def test_block_eigs_match_lapack(lib, storage):
-    """msdp_block_eigs (cyclic Jacobi, one workgroup per block, msdp_blockjacobi.hip) against numpy.linalg.eigh on the blocks of a
-    dual slack: orders 1..97 incl. odd ones, 23 blocks; eigenvalues to 1e-13 |S_i|, eigenvectors as residuals and orthonormality
-    (a Jacobi basis and LAPACK's differ by signs)."""
+    """msdp_block_eigs (one workgroup per block, msdp_blockjacobi.hip), both methods -- tridiagonalisation + bisection + inverse
+    iteration and cyclic Jacobi -- against numpy.linalg.eigh on the blocks of a dual slack: orders 1..97 incl. odd ones, 23 blocks;
+    eigenvalues to 1e-13 |S_i|, eigenvectors as residuals and orthonormality (the device's basis and LAPACK's differ by signs).
+    Clustered, singular and larger blocks: tests/test_gpu_block_eigs.py."""
     rng = np.random.default_rng(11)
     nset = [1, 2, 3, 97, 64, 31] + [int(v) for v in rng.integers(4, 60, size=17)]
     At, b, c = _random_multiblock(nset, 200, seed=8)

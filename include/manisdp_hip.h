@@ -424,6 +424,21 @@ int msdp_get_dual_slack_block(msdp_handle h, int64_t row0, int64_t nb, double* S
  * when a Jacobi iteration has not converged in 40 sweeps.  Every check is made on the host before anything is launched, and the
  * handle stays usable after a refusal. */
 int msdp_block_eigs(msdp_handle h, int32_t nb, const int64_t* row0, const int64_t* nblk, int32_t k, int32_t method, double* w, double* V);
+/* The same call for blocks of order up to 1024 (MSDP_BLOCK_EIGS_LARGE_MAXN): ManiSDP_multiblock.m:78-88 again, the tridiagonal method
+ * only (Householder tridiagonalisation, bisection, inverse iteration, back-transformation), a GROUP of workgroups per block of order
+ * above 256 (msdp_blocktridiag.hip: the group shares the rows of the block and meets at two group barriers per Householder step;
+ * blocks of order <= 256 are legal and take one workgroup).  Same outputs and layout as msdp_block_eigs.  0 <= k <= 8;
+ * MSDP_EUNSUPPORTED for k > 8 and for an order above 1024 (the message names the limit and the block), MSDP_EINVAL for nb < 1, an
+ * order < 1, a block outside the matrix and a range that is not one block of a handle that stores per block, MSDP_ESTATE before
+ * msdp_al_dual / msdp_dual_outer_step; every check is made before anything is launched and the handle stays usable after a refusal.
+ * All workgroups of a launch are resident together (the grid never exceeds what the occupancy query allows; a call with more blocks
+ * runs as consecutive launches); every barrier spins a bounded number of times and a barrier that runs out makes all workgroups leave:
+ * MSDP_ECOMM.  Results are bit-reproducible, and a block's results do not depend on the other blocks of the call nor on the number of
+ * workgroups it was given (option "blk_groups": that number for orders above 256, 0 = by order; tests). */
+#define MSDP_BLOCK_EIGS_LARGE_MAXN 1024
+int msdp_block_eigs_large(msdp_handle h, int32_t nb, const int64_t* row0, const int64_t* nblk, int32_t k, double* w, double* V);
+/* Diagnostic: launches and workgroups of the last msdp_block_eigs_large call on this handle (either pointer may be NULL). */
+int msdp_block_eigs_large_info(msdp_handle h, int32_t* launches, int32_t* workgroups);
 
 /* Run-time switches of one handle (production = the defaults; the tests and the profiling scripts use them):
  *   "persist"      1/0  persistent single-launch tCG / Lanczos kernels where they fit (default 1; env MSDP_NO_PERSIST=1)

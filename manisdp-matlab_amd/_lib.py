@@ -94,6 +94,8 @@ SIGNATURES = {
     "msdp_get_dual_slack": (C.c_int, [C.c_void_p, _dp]),
     "msdp_get_dual_slack_block": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _dp]),
     "msdp_block_eigs": (C.c_int, [C.c_void_p, C.c_int32, _i64p, _i64p, C.c_int32, C.c_int32, _dp, _dp]),
+    "msdp_block_eigs_large": (C.c_int, [C.c_void_p, C.c_int32, _i64p, _i64p, C.c_int32, _dp, _dp]),
+    "msdp_block_eigs_large_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "msdp_release_cache": (C.c_int, []),
     "msdp_debug_pool_stats": (C.c_int, [_P(C.c_int64), _P(C.c_int64), _P(C.c_int64)]),
     "msdp_debug_mem_info": (C.c_int, [_P(C.c_int64), _P(C.c_int64)]),
@@ -613,6 +615,23 @@ class Handle:
         V = np.empty((tot, max(int(k), 1)))
         _check(self._lib.msdp_block_eigs(self._h, len(nb), r0.ctypes.data_as(_i64p), nb.ctypes.data_as(_i64p), int(k), int(method), _dptr(w), _dptr(V)))
         return w, V[:, :int(k)]
+
+    def block_eigs_large(self, row0, nblk, k):
+        """block_eigs for blocks of order up to 1024 (msdp_block_eigs_large: a group of workgroups per block of order > 256, the
+        tridiagonal method, k <= 8): the same (w, V).  A block's results do not depend on the other blocks of the call."""
+        r0 = np.ascontiguousarray(row0, dtype=np.int64)
+        nb = np.ascontiguousarray(nblk, dtype=np.int64)
+        tot = int(nb.sum())
+        w = np.empty(tot)
+        V = np.empty((tot, max(int(k), 1)))
+        _check(self._lib.msdp_block_eigs_large(self._h, len(nb), r0.ctypes.data_as(_i64p), nb.ctypes.data_as(_i64p), int(k), _dptr(w), _dptr(V)))
+        return w, V[:, :int(k)]
+
+    def block_eigs_large_info(self):
+        """(launches, workgroups) of the last block_eigs_large call."""
+        a, b = C.c_int32(), C.c_int32()
+        _check(self._lib.msdp_block_eigs_large_info(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def al_primal(self, m):
         """obj = c'x and A x (length m) at the resident point, without forming X = YY' on the host."""

@@ -1170,6 +1170,7 @@ extern "C" int msdp_set_option(msdp_handle h, const char* name, int32_t value) {
     else if (!strcmp(name, "dense_sym_rt")) { t.dense_sym_rt = (value >= 1 && value <= 4) ? value : 0; h->chunk_len = 0; if (h->have_point && h->d.costkind != COST_SPARSE && !h->blocked) { int rc = msdp_dense_reserve(h, h->d.costkind == COST_AFFINE ? 2 : 1); if (rc) return rc; } }
     else if (!strcmp(name, "dense_sym_db")) { t.dense_sym_db = (value >= 0 && value <= 2) ? value : 0; h->chunk_len = 0; }
     else if (!strcmp(name, "dense_sym_len")) { t.dense_sym_len = value > 0 ? value : 0; h->chunk_len = 0; if (h->have_point && h->d.costkind != COST_SPARSE && !h->blocked) { int rc = msdp_dense_reserve(h, h->d.costkind == COST_AFFINE ? 2 : 1); if (rc) return rc; } }
+    else if (!strcmp(name, "blk_groups")) t.blk_groups = value > 0 ? (value > 16 ? 16 : value) : 0;
     else if (!strcmp(name, "debug_fail_persist")) t.fail_persist = value != 0;
     else if (!strcmp(name, "debug_xr_skip")) t.fail_xr = value != 0;
     else if (!strcmp(name, "debug_fail_block")) t.fail_block = value != 0;

@@ -235,6 +235,7 @@ struct Tuning {
     int be_grid = 0;         // ... workgroups of the filter step (0: by rows)
     int be_lpr = 0;          // ... lanes per row of the filter step (0: by rows per workgroup)
     int grid = 0;          // workgroups of the row-parallel launches (0: choose_grid; A/B switch)
+    int blk_groups = 0;    // msdp_block_eigs_large: workgroups per block of order > 256 (0: by order; tests of the bit-identity across group sizes)
     int fail_block = 0;    // test hook (msdp_set_option "debug_fail_block"): the next block eigen-solver call reports itself unconverged
     int fail_xr = 0;       // test hook ("debug_xr_skip"): this member skips its next cross-rank persistent launch
     int fail_persist = 0;  // test hook (msdp_set_option "debug_fail_persist"): the next persistent launch reports a
@@ -276,7 +277,8 @@ struct msdp_handle_s {
     int xr2_share = 1; bool xr2_multi = false;   // process ranks (msdp_comm_init_ipc): the most members on one device, members on different devices
     bool xr_ok = false; int xr_halo_rows = 0;   // push exchange of the cross-rank kernels: usable (no row needed by more than two members), foreign rows referenced
     struct WinCache* win = nullptr;        // patch plans of the LDS-staged S*U (msdp_window.hip), one per lanes-per-row
-    void* blk_ws = nullptr; size_t blk_ws_cap = 0;   // workspace of msdp_block_eigs (msdp_blockjacobi.hip)
+    void* blk_ws = nullptr; size_t blk_ws_cap = 0;   // workspace of msdp_block_eigs (msdp_blockjacobi.hip) and msdp_block_eigs_large (msdp_blocktridiag.hip)
+    int blk_launches = 0, blk_wgs = 0;               // launches and workgroups of the last msdp_block_eigs_large call
     double* lc_tmp = nullptr; size_t lc_tmp_cap = 0;   // its reduction scratch
     // row-sharded onlyunitdiag (sparse C): the escape runs replicated on full copies of C's CSR arrays and of z
     int* esc_rp = nullptr; int* esc_ci = nullptr; double* esc_cv = nullptr; double* esc_z = nullptr;

@@ -551,15 +551,30 @@ class _OneFactor:
         return self.layout(Y), U, p
 
 
+BLOCK_EIG_SMALL, BLOCK_EIG_LARGE, BLOCK_EIG_LARGE_K = 256, 1024, 8     # msdp_block_eigs / msdp_block_eigs_large: orders, vectors
+
+
+def _block_eig_auto(nset):
+    """Whether block_eig = "auto" takes the device for the block orders `nset`.  All orders <= 256: from 16 blocks on (msdp_block_eigs
+    wins there; below, the host loop keeps the iterates the oracle-parity tests compare).  A set that contains a
+    block of order above 256: the host loop, whatever its size -- msdp_block_eigs_large has not been timed against the host loop
+    (tools/time_block_eigs_large.py makes the comparison), and "auto" moves a set to the device only where the device has won a
+    measurement.  block_eig = "device" takes such sets."""
+    if max(nset) <= BLOCK_EIG_SMALL:
+        return len(nset) >= 16
+    return False
+
+
 class _Blocks:
     """Factor geometry of the multiblock kinds: factors (n_i, p_i), oblique for the first ``nob`` blocks and Euclidean
     after them, packed into ONE zero-padded (sum n_i, max p_i) factor on the device; the per-block bookkeeping
     (eig(S_i), svd(Y_i), escape directions; ManiSDP_multiblock.m:78-147) stays on the host -- the blocks are small by
     construction.  ``block_eig``: "host" = the reference's loop of eig(S_i) on the host, "device" = all blocks in one
     launch (msdp_block_eigs: one workgroup per block; Householder tridiagonalisation, bisection, inverse iteration for the
-    `delta` <= 8 vectors the loop uses), "auto" (default) = device from 16 blocks of order <= 256 on, host below -- where
-    the oracle-parity tests compare iterate by iterate: the eigenvectors of two eigen-solvers differ by signs / rotations
-    inside eigenspaces."""
+    `delta` <= 8 vectors the loop uses) and the blocks of order 257 .. 1024 in one msdp_block_eigs_large call (the same method,
+    a group of workgroups per block; needs delta <= 8; larger orders raise), "auto" (default) = device from 16 blocks of order
+    <= 256 on, host below -- where the oracle-parity tests compare iterate by iterate: the eigenvectors of two eigen-solvers
+    differ by signs / rotations inside eigenspaces; a set that contains a block of order above 256 stays on the host under "auto" (not yet timed)."""
     line = "Iter %d, obj:%0.8f, gap:%0.1e, pinf:%0.1e, dinf:%0.1e, gradnorm:%0.1e, p_max:%d, sigma:%0.3f, time:%0.2fs"
 
     def __init__(self, h, o, nset, nob, strict_rank):
@@ -568,7 +583,7 @@ class _Blocks:
         self.N = int(self.r0[-1])
         be = o.get("block_eig", "auto")
         self.eig_forced = be == "device"
-        self.eig_device = be == "device" or (be == "auto" and len(nset) >= 16 and max(nset) <= 256)
+        self.eig_device = be == "device" or (be == "auto" and _block_eig_auto(nset))
         self.S = None                                      # the blocks of S the host eig last fetched
 
     def normalise(self, i):
@@ -598,7 +613,7 @@ class _Blocks:
         h, r0, nset = self.h, self.r0, self.nset
         if self.eig_device:
             try:
-                wall, Vall = h.block_eigs(r0[:-1], nset, int(self.o["delta"]))
+                wall, Vall = self._device_eigs()
             except _lib.MsdpError:
                 if self.eig_forced:
                     raise
@@ -613,6 +628,28 @@ class _Blocks:
                 w, V = np.linalg.eigh(0.5 * (Si + Si.T))   # :86
                 self.S.append(Si); dS.append(w); vS.append(V)
         return max(_dinf_abs(w[0], w[-1]) for w in dS), True, (dS, vS)   # :87-89
+
+    def _device_eigs(self):
+        """(w, V) of all blocks, rows in block order: the blocks of order <= 256 in one msdp_block_eigs call, the larger ones in one
+        msdp_block_eigs_large call."""
+        h, r0, nset, delta = self.h, self.r0, self.nset, int(self.o["delta"])
+        small = [i for i, n in enumerate(nset) if n <= BLOCK_EIG_SMALL]
+        large = [i for i, n in enumerate(nset) if n > BLOCK_EIG_SMALL]
+        if not large:
+            return h.block_eigs(r0[:-1], nset, delta)
+        if max(nset) > BLOCK_EIG_LARGE or delta > BLOCK_EIG_LARGE_K:
+            raise _lib.MsdpError(f"block_eig = 'device': blocks of order above {BLOCK_EIG_SMALL} need orders <= {BLOCK_EIG_LARGE} and "
+                                 f"delta <= {BLOCK_EIG_LARGE_K} (largest order {max(nset)}, delta {delta})")
+        wall, Vall = np.empty(self.N), np.empty((self.N, delta))
+        for idx, call in ((small, h.block_eigs), (large, h.block_eigs_large)):
+            if not idx:
+                continue
+            w, V = call([r0[i] for i in idx], [nset[i] for i in idx], delta)
+            at = 0
+            for i in idx:
+                wall[r0[i]:r0[i + 1]] = w[at:at + nset[i]]; Vall[r0[i]:r0[i + 1]] = V[at:at + nset[i]]
+                at += nset[i]
+        return wall, Vall
 
     def shape(self, Yb, p):
         return (max(p),), None

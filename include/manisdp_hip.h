@@ -439,6 +439,30 @@ int msdp_block_eigs(msdp_handle h, int32_t nb, const int64_t* row0, const int64_
 int msdp_block_eigs_large(msdp_handle h, int32_t nb, const int64_t* row0, const int64_t* nblk, int32_t k, double* w, double* V);
 /* Diagnostic: launches and workgroups of the last msdp_block_eigs_large call on this handle (either pointer may be NULL). */
 int msdp_block_eigs_large_info(msdp_handle h, int32_t* launches, int32_t* workgroups);
+/* Rank cut and escape widening of ALL blocks of a multiblock factor on the device (ManiSDP_multiblock.m:109-147,
+ * ManiDSDP_multiblock.m:146-181), the resident point rewritten without leaving the device.  nb / row0 / nblk: all blocks of the handle,
+ * in order (MSDP_EINVAL otherwise); p_in[b]: block b's current width (its columns beyond are zero); w, V: eig(S_i) in the layout
+ * msdp_block_eigs returns (sum nblk values ascending per block; (sum nblk) x k row-major).  Block i of order n_i < min_facsize is
+ * left as it is (:110).  Otherwise, when p_i > 1: G = Y_i'Y_i summed over the rows in order, its eigen-decomposition (cyclic Jacobi
+ * in LDS), e = sqrt(max(lambda, 0)) descending, r = #{e >= theta e_1} (strict != 0: #{e > theta e_1}, ManiDSDP_multiblock.m:146-155),
+ * at least 1; r < p_i: Y_i <- Y_i Q(:, 1:r), p_i = r (:112-127).  nne = max(min(#{w_i < 0}, delta), 1 for the first nob blocks of the
+ * handle, else 0), and 0 when p_i + nne > n_i (:129-136).  mode 0 (line_search = 0, :142-146): Y_i <- [Y_i, alpha V_i(:, 1:nne)], the
+ * rows of the first nob blocks scaled to unit norm; mode 1 (:137-141): Y_i <- [Y_i, 0] and U_i = [0, V_i(:, 1:nne)] written to the
+ * host array U in the boundary layout of the new point (N x max p_out, row-major; U may be NULL in mode 0).  Outputs per block:
+ * p_out (new width), r_out (the rank found; p_in where no decomposition was made), nne_out.  Columns beyond a block's new width are
+ * exact zeros; the handle's width becomes max p_out (it may shrink).  One workgroup per block in each of two launches
+ * (msdp_blockreshape.hip: the decisions, then the rows -- the new row stride is known only in between); a block's result does not
+ * depend on the other blocks and is bit-reproducible.  Widths: p_in <= 64 on every block the rule touches; the new width r + nne of a
+ * block may exceed 64 (at most 64 + delta: an uncut block that gains escape columns) and is limited by the handle's allocated width
+ * alone.  MSDP_EINVAL: nb < 1, k < 0 or > 64, delta < 0 or > k, mode not 0 / 1, a null array,
+ * a width outside 1 .. p, a block list that is not the handle's; MSDP_ESTATE: no resident point; MSDP_EUNSUPPORTED: not a
+ * multiblock kind, a row-sharded handle, a block of width above 64 (MSDP_BLOCK_RESHAPE_MAXP) that the rule touches, a new width above
+ * the allocated one (msdp_set_point re-allocates); MSDP_ESTATE also when a Jacobi iteration has not converged in 40 sweeps.  Every refusal leaves the point and the handle as they were. */
+#define MSDP_BLOCK_RESHAPE_MAXP 64
+int msdp_block_reshape(msdp_handle h, int32_t nb, const int64_t* row0, const int64_t* nblk, const int32_t* p_in,
+                       const double* w, const double* V, int32_t k, double theta, int32_t strict, int32_t delta,
+                       double alpha, int32_t min_facsize, int32_t mode,
+                       int32_t* p_out, int32_t* r_out, int32_t* nne_out, double* U);
 
 /* Run-time switches of one handle (production = the defaults; the tests and the profiling scripts use them):
  *   "persist"      1/0  persistent single-launch tCG / Lanczos kernels where they fit (default 1; env MSDP_NO_PERSIST=1)

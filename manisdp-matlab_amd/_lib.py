@@ -37,12 +37,16 @@ class RtrStats(C.Structure):
 
 
 class MsdpError(RuntimeError):
-    pass
+    code = None                     # the library's return code where the error came from a call (MSDP_E* of the header)
+
+
+ESTATE, EUNSUPPORTED = -4, -6
 
 
 _P = C.POINTER
 _dp = _P(C.c_double)
 _i64p = _P(C.c_int64)
+_i32p = _P(C.c_int32)
 
 # name -> (restype, argtypes); this table is also what tests/test_cabi_symbols.py
 # checks against the declarations in include/manisdp_hip.h.
@@ -96,6 +100,8 @@ SIGNATURES = {
     "msdp_block_eigs": (C.c_int, [C.c_void_p, C.c_int32, _i64p, _i64p, C.c_int32, C.c_int32, _dp, _dp]),
     "msdp_block_eigs_large": (C.c_int, [C.c_void_p, C.c_int32, _i64p, _i64p, C.c_int32, _dp, _dp]),
     "msdp_block_eigs_large_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "msdp_block_reshape": (C.c_int, [C.c_void_p, C.c_int32, _i64p, _i64p, _i32p, _dp, _dp, C.c_int32, C.c_double, C.c_int32,
+                                     C.c_int32, C.c_double, C.c_int32, C.c_int32, _i32p, _i32p, _i32p, _dp]),
     "msdp_release_cache": (C.c_int, []),
     "msdp_debug_pool_stats": (C.c_int, [_P(C.c_int64), _P(C.c_int64), _P(C.c_int64)]),
     "msdp_debug_mem_info": (C.c_int, [_P(C.c_int64), _P(C.c_int64)]),
@@ -180,7 +186,9 @@ def mem_info():
 
 def _check(rc):
     if rc != 0:
-        raise MsdpError(f"libmanisdp_hip error {rc}: {load().msdp_last_error().decode()}")
+        err = MsdpError(f"libmanisdp_hip error {rc}: {load().msdp_last_error().decode()}")
+        err.code = rc
+        raise err
 
 
 def _dptr(a):
@@ -626,6 +634,28 @@ class Handle:
         V = np.empty((tot, max(int(k), 1)))
         _check(self._lib.msdp_block_eigs_large(self._h, len(nb), r0.ctypes.data_as(_i64p), nb.ctypes.data_as(_i64p), int(k), _dptr(w), _dptr(V)))
         return w, V[:, :int(k)]
+
+    def block_reshape(self, row0, nblk, p, w, V, theta, strict, delta, alpha, min_facsize, mode):
+        """Rank cut and escape widening of all blocks of the resident multiblock factor on the device (msdp_block_reshape;
+        ManiSDP_multiblock.m:109-147): ``p`` the blocks' widths, ``w`` / ``V`` their eig(S_i) as block_eigs returns them.  Returns
+        (p_out, r_out, nne_out, U) -- U (N, max p_out) in mode 1, else None -- and updates ``self.p``."""
+        r0 = np.ascontiguousarray(row0, dtype=np.int64); nb = np.ascontiguousarray(nblk, dtype=np.int64)
+        pin = np.ascontiguousarray(p, dtype=np.int32)
+        w = np.ascontiguousarray(w, dtype=np.float64); V = np.ascontiguousarray(V, dtype=np.float64)
+        k = int(V.shape[1]) if V.ndim == 2 else 0
+        assert len(r0) == len(nb) == len(pin) and w.shape == (int(nb.sum()),) and (k == 0 or V.shape[0] == w.size)
+        out = [np.zeros(max(len(nb), 1), dtype=np.int32) for _ in range(3)]
+        # mode 1: room for the widest U the call can produce (the library writes N x max p_out of it)
+        U = np.zeros(self.n * (int(pin.max(initial=1)) + int(delta))) if int(mode) == 1 else None
+        _check(self._lib.msdp_block_reshape(self._h, len(nb), r0.ctypes.data_as(_i64p), nb.ctypes.data_as(_i64p), pin.ctypes.data_as(_i32p),
+                                            _dptr(w), _dptr(V) if k else None, k, float(theta), int(bool(strict)), int(delta), float(alpha),
+                                            int(min_facsize), int(mode), *(o.ctypes.data_as(_i32p) for o in out),
+                                            _dptr(U) if U is not None else None))
+        p_out, r_out, nne_out = (o[:len(nb)] for o in out)
+        self.p = int(p_out.max())
+        if U is not None:
+            U = U[:self.n * self.p].reshape(self.n, self.p).copy()
+        return p_out, r_out, nne_out, U
 
     def block_eigs_large_info(self):
         """(launches, workgroups) of the last block_eigs_large call."""

@@ -666,6 +666,7 @@ extern "C" int msdp_create_multiblock(int32_t nb, const int64_t* block_n, int32_
         if ((rcb = alloc_common(hb)) || (rcb = msdp_affine_setup_blocked(hb, nb, block_n, at_jc, at_ir, at_pr, b, c)) ||
             (rcb = msdp_alloc_vectors(hb, pcap > 0 ? pcap : 32))) { msdp_destroy(hb); return rcb; }
         hb->kind = MSDP_KIND_MULTIBLOCK;
+        hb->mb_n.assign(block_n, block_n + nb); hb->mb_nob = nob;
         std::vector<unsigned char> rfb((size_t)N, 0);
         bool anyb = false;
         for (int i = nob; i < nb; ++i)
@@ -700,6 +701,7 @@ extern "C" int msdp_create_multiblock(int32_t nb, const int64_t* block_n, int32_
     int rc = msdp_create_affine(MSDP_KIND_UNITDIAG, N, m, at_jc, ir.data(), at_pr, b, cN.data(), pcap, &h);
     if (rc) return rc;
     h->kind = MSDP_KIND_MULTIBLOCK;
+    h->mb_n.assign(block_n, block_n + nb); h->mb_nob = nob;
     std::vector<unsigned char> rf((size_t)N, 0);
     bool any = false;
     for (int i = nob; i < nb; ++i)
@@ -786,6 +788,7 @@ extern "C" int msdp_create_dual_multiblock(int32_t nb, const int64_t* block_n, i
     if ((rc = alloc_common(h)) || (rc = msdp_affine_setup_blocked(h, nb, block_n, at_jc, at_ir, at_pr, b, c)) ||
         (rc = msdp_alloc_vectors(h, pcap > 0 ? pcap : 32))) { msdp_destroy(h); return rc; }
     h->kind = MSDP_KIND_DUAL_MULTIBLOCK;
+    h->mb_n.assign(block_n, block_n + nb); h->mb_nob = nob;
     if (nob < nb) {
         std::vector<unsigned char> rf((size_t)N, 0);
         for (int64_t a = r0[(size_t)nob]; a < N; ++a) rf[(size_t)a] = 1;
@@ -1036,6 +1039,50 @@ extern "C" int msdp_factor_append(msdp_handle h, int32_t k, const double* V, dou
     (void)hipStreamSynchronize(h->stream);
     (void)hipFree(vd);
     if (rc) return rc;
+    return adopt_point(h, cur ^ 1, pn);
+}
+
+// Rank cut and escape widening of all blocks of a multiblock factor (msdp_blockreshape.hip); every check before any launch.
+int msdp_block_reshape_run(msdp_handle h, int cur, int nb, const int64_t* nblk, const int32_t* p_in, const double* w, const double* V,
+                           int k, double theta, int strict, int delta, double alpha, int min_facsize, int mode, int nob,
+                           int32_t* p_out, int32_t* r_out, int32_t* nne_out, int* p_new);
+int msdp_block_reshape_maxp();
+extern "C" int msdp_block_reshape(msdp_handle h, int32_t nb, const int64_t* row0, const int64_t* nblk, const int32_t* p_in,
+                                  const double* w, const double* V, int32_t k, double theta, int32_t strict, int32_t delta,
+                                  double alpha, int32_t min_facsize, int32_t mode,
+                                  int32_t* p_out, int32_t* r_out, int32_t* nne_out, double* U) {
+    CHECK_H(h);
+    if (nb < 1 || !row0 || !nblk || !p_in || !w || k < 0 || k > 64 || (k > 0 && !V) || delta < 0 || delta > k || (mode != 0 && mode != 1) ||
+        (mode == 1 && !U) || !p_out || !r_out || !nne_out) { msdp_set_error("block_reshape: bad argument"); return MSDP_EINVAL; }
+    if (h->kind != MSDP_KIND_MULTIBLOCK && h->kind != MSDP_KIND_DUAL_MULTIBLOCK) { msdp_set_error("block_reshape: the multiblock kinds only"); return MSDP_EUNSUPPORTED; }
+    if (h->nranks > 1 || h->use_comm) { msdp_set_error("block_reshape: not on a row-sharded handle"); return MSDP_EUNSUPPORTED; }
+    if ((size_t)nb != h->mb_n.size()) { msdp_set_error("block_reshape: %d blocks given, the handle has %zu (all blocks, in order)", nb, h->mb_n.size()); return MSDP_EINVAL; }
+    int64_t at = 0;
+    for (int b = 0; b < nb; ++b) {
+        if (row0[b] != at || nblk[b] != h->mb_n[(size_t)b]) { msdp_set_error("block_reshape: block %d is not block %d of the handle (all blocks, in order)", b, b); return MSDP_EINVAL; }
+        at += nblk[b];
+    }
+    if (!h->have_point) { msdp_set_error("block_reshape: no resident point"); return MSDP_ESTATE; }
+    Dev& d = h->d;
+    const int maxp = msdp_block_reshape_maxp();
+    for (int b = 0; b < nb; ++b) {
+        if (p_in[b] < 1 || p_in[b] > d.p) { msdp_set_error("block_reshape: width %d of block %d outside 1..p = %d", p_in[b], b, d.p); return MSDP_EINVAL; }
+        if (nblk[b] >= min_facsize && p_in[b] > maxp) { msdp_set_error("block_reshape: block widths up to %d (block %d has %d)", maxp, b, p_in[b]); return MSDP_EUNSUPPORTED; }
+    }
+    const int cur = host_cur(h);
+    int pn = 0;
+    int rc = msdp_block_reshape_run(h, cur, nb, nblk, p_in, w, V, k, theta, strict, delta, alpha, min_facsize, mode, h->mb_nob, p_out, r_out, nne_out, &pn);
+    if (rc) return rc;
+    if (mode == 1) {                                       // U_i = [0, V_i(:, 1:nne_i)] in the boundary layout of the new point (:137-141)
+        std::fill(U, U + (size_t)d.n * pn, 0.0);
+        int64_t r = 0;
+        for (int b = 0; b < nb; ++b) {
+            const int c0 = p_out[b] - nne_out[b];
+            for (int64_t i = 0; i < nblk[b]; ++i)
+                for (int c = 0; c < nne_out[b]; ++c) U[(size_t)(r + i) * pn + c0 + c] = V[(size_t)(r + i) * k + c];
+            r += nblk[b];
+        }
+    }
     return adopt_point(h, cur ^ 1, pn);
 }
 

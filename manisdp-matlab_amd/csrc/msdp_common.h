@@ -279,6 +279,7 @@ struct msdp_handle_s {
     struct WinCache* win = nullptr;        // patch plans of the LDS-staged S*U (msdp_window.hip), one per lanes-per-row
     void* blk_ws = nullptr; size_t blk_ws_cap = 0;   // workspace of msdp_block_eigs (msdp_blockjacobi.hip) and msdp_block_eigs_large (msdp_blocktridiag.hip)
     int blk_launches = 0, blk_wgs = 0;               // launches and workgroups of the last msdp_block_eigs_large call
+    std::vector<int64_t> mb_n; int mb_nob = 0;       // multiblock kinds: the block orders and the number of unit-diagonal blocks (msdp_block_reshape)
     double* lc_tmp = nullptr; size_t lc_tmp_cap = 0;   // its reduction scratch
     // row-sharded onlyunitdiag (sparse C): the escape runs replicated on full copies of C's CSR arrays and of z
     int* esc_rp = nullptr; int* esc_ci = nullptr; double* esc_cv = nullptr; double* esc_z = nullptr;

@@ -537,6 +537,9 @@ class _OneFactor:
         lam, vS, nneg = esc
         return lam, np.hstack([v_v, vS[:, :max(int(self.o["delta"]) - 1, 0)]]), self.miss_nneg(lam, nneg)
 
+    def keep(self, Y, p):
+        return Y
+
     def shape(self, Y, p):                                 # ManiSDP_unitdiag.m:72-74
         Q, e, r = _factor_rank(Y, float(self.o["theta"]), self.strict_rank)
         return (r, p), (Q, e, r)
@@ -549,6 +552,17 @@ class _OneFactor:
         nne = max(min(esc[2], int(self.o["delta"])), self.nne_floor)    # :97
         Y, U, p = _widen(Y, p, esc[1], nne, self.o, self.normalise)
         return self.layout(Y), U, p
+
+
+_RESIDENT = object()               # stands for "the factor is the handle's resident point" between _Blocks.fetch / reshape / pack
+
+
+def _block_reshape_option(o):
+    """options["block_reshape"]: "host" (default) = the per-block loop of _Blocks.reshape, "device" = msdp_block_reshape."""
+    br = o.get("block_reshape", "host")
+    if br not in ("host", "device"):
+        raise ValueError(f"options['block_reshape'] must be 'host' or 'device', not {br!r}")
+    return br
 
 
 BLOCK_EIG_SMALL, BLOCK_EIG_LARGE, BLOCK_EIG_LARGE_K = 256, 1024, 8     # msdp_block_eigs / msdp_block_eigs_large: orders, vectors
@@ -574,11 +588,17 @@ class _Blocks:
     `delta` <= 8 vectors the loop uses) and the blocks of order 257 .. 1024 in one msdp_block_eigs_large call (the same method,
     a group of workgroups per block; needs delta <= 8; larger orders raise), "auto" (default) = device from 16 blocks of order
     <= 256 on, host below -- where the oracle-parity tests compare iterate by iterate: the eigenvectors of two eigen-solvers
-    differ by signs / rotations inside eigenspaces; a set that contains a block of order above 256 stays on the host under "auto" (not yet timed)."""
+    differ by signs / rotations inside eigenspaces; a set that contains a block of order above 256 stays on the host under "auto" (not yet timed).
+    ``block_reshape``: "host" (default) = the per-block loop of :meth:`reshape` on the fetched factor, "device" = one
+    msdp_block_reshape call per outer iteration on the resident factor (widths <= 64): `fetch` then hands the loop _RESIDENT
+    instead of the factor, `pack` has nothing to upload, and the factor comes to the host once, at the end (:meth:`final`); an
+    iteration the call refuses as unsupported runs the host loop and re-enters through set_point."""
     line = "Iter %d, obj:%0.8f, gap:%0.1e, pinf:%0.1e, dinf:%0.1e, gradnorm:%0.1e, p_max:%d, sigma:%0.3f, time:%0.2fs"
 
     def __init__(self, h, o, nset, nob, strict_rank):
         self.h, self.o, self.nset, self.nob, self.strict_rank = h, o, nset, nob, strict_rank
+        self.reshape_device = _block_reshape_option(o) == "device"
+        self.wV = None                                     # (w, V) of all blocks as the device eigen route returned them
         self.r0 = np.concatenate([[0], np.cumsum(nset)]).astype(int)
         self.N = int(self.r0[-1])
         be = o.get("block_eig", "auto")
@@ -596,6 +616,10 @@ class _Blocks:
         return [np.ascontiguousarray(Yi, dtype=np.float64) for Yi in Yb]
 
     def pack(self, Yb, p):
+        if Yb is _RESIDENT:
+            return None
+        if isinstance(Yb, np.ndarray):                     # the direction U of the device reshape: already one (N, max p) array
+            return Yb
         return _pack_blocks(Yb, self.r0, self.N, max(p))
 
     def topts(self, p):                                    # M.typicaldist of multiblockmanifold.m:11-15
@@ -606,6 +630,14 @@ class _Blocks:
                                  tolgradnorm=float(o["tolgradnorm"]), Delta_bar=tdist)
 
     def fetch(self, p):
+        # block_reshape = "device": the factor stays where it is (the loop asks for it with keep() / final() when it returns it)
+        return _RESIDENT if self.reshape_device else self.download(p)
+
+    def keep(self, Yb, p):
+        """The iterate itself, on the host: the loop calls this before a reshape whose input it is going to return."""
+        return self.download(p) if Yb is _RESIDENT else Yb
+
+    def download(self, p):
         Yfull = self.h.get_point()
         return [np.ascontiguousarray(Yfull[self.r0[i]:self.r0[i + 1], :p[i]]) for i in range(len(self.nset))]
 
@@ -620,6 +652,7 @@ class _Blocks:
                 self.eig_device = False
         dS, vS = [], []
         self.S = []
+        self.wV = (wall, Vall) if self.eig_device else None
         for i in range(len(nset)):
             if self.eig_device:
                 dS.append(wall[r0[i]:r0[i + 1]]); vS.append(Vall[r0[i]:r0[i + 1], :])
@@ -655,6 +688,14 @@ class _Blocks:
         return (max(p),), None
 
     def reshape(self, Yb, p, cut, esc):                    # ManiSDP_multiblock.m:109-147
+        if self.reshape_device:
+            try:
+                return self._reshape_device(p, esc)
+            except _lib.MsdpError as e:                    # a width beyond the call's or the handle's (or a Jacobi iteration that did
+                if e.code not in (_lib.EUNSUPPORTED, _lib.ESTATE):   # not converge): the point is untouched, this iteration runs on
+                    raise                                  # the host and comes back in through set_point (which re-allocates)
+            if Yb is _RESIDENT:
+                Yb = self.download(p)
         dS, vS = esc
         o, delta, p = self.o, int(self.o["delta"]), list(p)
         newY, newU = [], []
@@ -675,6 +716,28 @@ class _Blocks:
             newY.append(np.ascontiguousarray(Yi))
             newU.append(Ui if Ui is not None else np.zeros_like(Yi))
         return newY, (newU if o["line_search"] == 1 else None), p
+
+
+    def _reshape_device(self, p, esc):
+        """The same lines in one msdp_block_reshape call on the resident factor: (w, V) of the device eigen route as they came, the
+        host route's eigh results repacked into that layout."""
+        o, delta = self.o, int(self.o["delta"])
+        if self.wV is not None:
+            w, V = self.wV
+        else:
+            dS, vS = esc
+            w = np.concatenate(dS)
+            V = np.zeros((self.N, delta))
+            for i, Vi in enumerate(vS):
+                V[self.r0[i]:self.r0[i + 1], :min(delta, Vi.shape[1])] = Vi[:, :delta]
+        mode = 1 if o["line_search"] == 1 else 0
+        p_out, _, _, U = self.h.block_reshape(self.r0[:-1], self.nset, p, w, V, float(o["theta"]), self.strict_rank, delta,
+                                              float(o["alpha"]), int(o["min_facsize"]), mode)
+        return _RESIDENT, U, [int(v) for v in p_out]
+
+    def final(self, Yb, p):
+        """The iterate the loop returned, on the host (block_reshape = "device" leaves it on the device when the loop stops early)."""
+        return self.keep(Yb, p)
 
 
 def _by(b, y, z):                                          # ManiSDP_unitdiag.m:70 (no z term in the generic kind)
@@ -757,7 +820,9 @@ def _al_loop(h, o, t, Y, p, mult, verbose):
     for it in range(1, t.maxiter + 1):
         fac_size.append(p)
         t.set_penalty(mult, sigma)
-        h.set_point(geo.pack(Y, p))
+        Yp = geo.pack(Y, p)
+        if Yp is not None:                                 # None: the geometry reshaped the resident point on the device
+            h.set_point(Yp)
         if U is not None:
             _line_search(h, geo.pack(U, p))
         st = h.rtr(geo.topts(p))                           # ManiSDP_unitdiag.m:57
@@ -798,6 +863,8 @@ def _al_loop(h, o, t, Y, p, mult, verbose):
                 _say(verbose, "Slow progress!")
                 break
             gap0, pinf0, dinf0 = gap, pinf, dinf
+        if it == t.maxiter:                                # the loop ends here and returns Y_eval: a geometry that keeps the factor
+            Y = Y_eval = geo.keep(Y, p)                    # on the device hands it over before the reshape below rewrites it
         Y, U, p = geo.reshape(Y, p, cut, esc)              # :93-106
         if pinf < o["tau1"] * gradnorm:                    # :108-112
             sigma = max(sigma / gama, float(o["sigma_min"]))
@@ -931,7 +998,9 @@ def ManiSDP_multiblock(At, b, c, K, options=None, verbose=True, rng=None):
     block-diagonal X with unit diagonal on the first ``K['nob']`` blocks of orders ``K['s']``.  The product manifold
     of ``multiblockmanifold.m`` lives on the device as ONE factor of N = sum n_i rows whose blocks are zero-padded to a
     common width; the per-block bookkeeping of the outer loop (eig(S{i}), svd(Y{i}), escape directions; :78-147) stays
-    on the host -- the blocks are small by construction.  Returns (list of factors, obj, data)."""
+    on the host -- the blocks are small by construction; ``options['block_reshape'] = "device"`` moves the rank cut and the
+    escape widening (:109-147) of all blocks into one device call per outer iteration (default "host").  Returns (list of
+    factors, obj, data)."""
     with _host_threads():
         return _multiblock_impl(At, b, c, K, options, verbose, rng)
 
@@ -945,12 +1014,14 @@ def _multiblock_impl(At, b, c, K, options, verbose, rng):
     _say(verbose, "ManiSDP is starting...")
     _say(verbose, f"SDP size: n = {max(nset)}, m = {b.size}")
     p = _block_widths(o, nset)
+    _block_reshape_option(o)                               # (a bad value is refused before anything is built)
     h = _lib.Handle.multiblock(sp.csc_matrix(At), b, c, nset, int(K.get("nob", 0)), pcap=max(32, max(p) + 2 * int(o["delta"])))
     try:
         geo = _Blocks(h, o, nset, int(K.get("nob", 0)), strict_rank=False)
         t = _Kind(geo, _primal_side(h, b), int(o["AL_maxiter"]), _gap_primal, (50, 100),
                   "ManiSDP: optimum = %0.8f, time = %0.2fs")
-        obj, data, (Yb, y, _, _, _, _, _) = _al_loop(h, o, t, geo.start(rng, p), p, np.zeros(b.size), verbose)
+        obj, data, (Yb, y, _, _, p, _, _) = _al_loop(h, o, t, geo.start(rng, p), p, np.zeros(b.size), verbose)
+        Yb = data["Y"] = geo.final(Yb, p)
         S = geo.S                                          # data.S (:158): the blocks of the last iterate
         if geo.eig_device and Yb is not None:
             S = [h.get_dual_slack_block(geo.r0[i], nset[i]) for i in range(len(nset))]
@@ -1096,12 +1167,14 @@ def _dual_multiblock_impl(A, b, c, K, options, verbose, rng):
     _say(verbose, f"SDP size: n = {max(nset)}, m = {b.size}")
     call, B, Apsd, cpsd, dAAt = _dual_matrices(A, c, nf, o)    # :33-44
     p = _block_widths(o, nset)                             # :50-55
+    _block_reshape_option(o)
     h = _lib.Handle.dual_multiblock(Apsd, b, cpsd, dAAt, nset, nob, B, call[:nf], pcap=max(32, max(p) + 2 * int(o["delta"])))
     try:
         geo = _Blocks(h, o, nset, nob, strict_rank=True)  # :146-155 (r = sum(e > theta*e(1)), at least 1)
         t = _Kind(geo, _dual_side(h, call, nf), int(o["ADMM_maxiter"]), _gap_dual, (50, 100),   # :133-143
                   "ManiDSDP: optimum = %0.8f, time = %0.2fs")
-        obj, data, (Yb, w, _, _, _, _, _) = _al_loop(h, o, t, geo.start(rng, p), p, np.zeros(nf), verbose)
+        obj, data, (Yb, w, _, _, p, _, _) = _al_loop(h, o, t, geo.start(rng, p), p, np.zeros(nf), verbose)
+        Yb = data["Y"] = geo.final(Yb, p)
         X = [h.get_dual_slack_block(geo.r0[i], nset[i]) for i in range(len(nset))] if obj is not None else None
         y = h.dual_get_y() if obj is not None else None
     finally:

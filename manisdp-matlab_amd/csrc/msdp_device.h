@@ -50,6 +50,18 @@ __device__ __forceinline__ double msdp_dpp(double v) {
     hi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xf, 0xf, false);
     return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
 }
+// The same exchange where EVERY lane of the row is active (workgroup-uniform control flow) and CTRL is a permutation inside the row
+// (quad_perm, row_mirror, row_half_mirror, row_ror): every lane receives a value, so the destination needs no initial contents -- with
+// old = the source, as above, the compiler copies each half into the destination first (two v_mov_b32 per exchange on the dependent
+// chain of a group sum).  Same values; bound_ctrl never applies since no source lane is invalid.
+template <int CTRL>
+__device__ __forceinline__ double msdp_dpp_all(double v) {
+    const long long b = __double_as_longlong(v);
+    int lo = (int)(b & 0xffffffffLL), hi = (int)(b >> 32);
+    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, true);
+    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, true);
+    return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
+}
 #define MSDP_DPP_XOR1 0xB1          // quad_perm [1,0,3,2]
 #define MSDP_DPP_XOR2 0x4E          // quad_perm [2,3,0,1]
 #define MSDP_DPP_HALF_MIRROR 0x141  // lane i <-> 7-i inside each 8 lanes
@@ -92,6 +104,18 @@ __device__ __forceinline__ double msdp_group_sum(double v) {
     // gfx950: v_permlane16_swap / v_permlane32_swap exchange 16- / 32-lane rows in the VALU (a __shfl_xor across
     // rows is a ds_bpermute round trip through the LDS crossbar).  swap(v, v) returns {even-row value everywhere in
     // the pair, odd-row value everywhere in the pair}; both rows add them in the same order.
+    if (LPR >= 32) v = msdp_rowpair_sum<16>(v);
+    if (LPR >= 64) v = msdp_rowpair_sum<32>(v);
+    return v;
+}
+
+// msdp_group_sum for callers in workgroup-uniform control flow (all lanes active): same exchanges, same order of the additions
+template <int LPR>
+__device__ __forceinline__ double msdp_group_sum_all(double v) {
+    if (LPR >= 2) v += msdp_dpp_all<MSDP_DPP_XOR1>(v);
+    if (LPR >= 4) v += msdp_dpp_all<MSDP_DPP_XOR2>(v);
+    if (LPR >= 8) v += msdp_dpp_all<MSDP_DPP_HALF_MIRROR>(v);
+    if (LPR >= 16) v += msdp_dpp_all<MSDP_DPP_MIRROR>(v);
     if (LPR >= 32) v = msdp_rowpair_sum<16>(v);
     if (LPR >= 64) v = msdp_rowpair_sum<32>(v);
     return v;

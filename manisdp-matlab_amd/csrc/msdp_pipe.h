@@ -154,8 +154,8 @@ __device__ __forceinline__ bool psync8_lines(unsigned long long* slots, unsigned
         for (int k = 0; k < 4; ++k) a[k] = msdp_swap_add<32>(v[k], v[4 + k]);
 #pragma unroll
         for (int k = 0; k < 2; ++k) b[k] = msdp_swap_add<16>(a[k], a[2 + k]);
-        x = (h8 ? b[1] : b[0]) + msdp_dpp<0x128>(h8 ? b[0] : b[1]);
-        x += msdp_dpp<MSDP_DPP_XOR1>(x); x += msdp_dpp<MSDP_DPP_XOR2>(x); x += msdp_dpp<MSDP_DPP_HALF_MIRROR>(x);
+        x = (h8 ? b[1] : b[0]) + msdp_dpp_all<0x128>(h8 ? b[0] : b[1]);
+        x += msdp_dpp_all<MSDP_DPP_XOR1>(x); x += msdp_dpp_all<MSDP_DPP_XOR2>(x); x += msdp_dpp_all<MSDP_DPP_HALF_MIRROR>(x);
         if ((lane & 7) == 0) sh8[(lane >> 3) * PWAVES + w] = x;
     }
     if (tr && threadIdx.x == 0) tr[4] = __builtin_readcyclecounter();
@@ -202,8 +202,8 @@ __device__ __forceinline__ bool psync8_lines(unsigned long long* slots, unsigned
     }
     if (tr && threadIdx.x == 0) tr[7] = (__builtin_readcyclecounter() << 4) + (unsigned long long)(spins < 15 ? spins : 15);
     // lanes l, l ^ 4, l ^ 8, l ^ 12 of a row, then the four rows: the sixteen lanes that hold the same value pair
-    t0 += msdp_dpp<0x124>(t0); t1 += msdp_dpp<0x124>(t1);         // row_ror:4
-    t0 += msdp_dpp<0x128>(t0); t1 += msdp_dpp<0x128>(t1);         // row_ror:8
+    t0 += msdp_dpp_all<0x124>(t0); t1 += msdp_dpp_all<0x124>(t1);         // row_ror:4
+    t0 += msdp_dpp_all<0x128>(t0); t1 += msdp_dpp_all<0x128>(t1);         // row_ror:8
     t0 = msdp_rowpair_sum<16>(t0); t1 = msdp_rowpair_sum<16>(t1);
     t0 = msdp_rowpair_sum<32>(t0); t1 = msdp_rowpair_sum<32>(t1);
     if (lane < 4) { shp[w * 8 + 2 * lane] = t0; shp[w * 8 + 2 * lane + 1] = t1; }
@@ -417,6 +417,15 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
     static_assert(R <= 5, "pipelined trip: every vector in registers");
     static_assert(CSR ? (EP == 64 / LPR && !XR && !TRACE) : EP == 1, "CSR rows: one row per wave, one rank");
     static_assert(PSYNC_NV == 8 && PSYNC_REP * PSYNC_NV == 64, "psync8 posts one slot per lane of wave 0");
+    // What each instance takes of the launch-invariant address and mask work.  Decided by the register allocation: an instance takes a
+    // piece only where its scratch does not grow (bytes per lane, parent -> with everything -> as chosen; tools/isa_scratch_map.py,
+    // profiles/r7_trip_instruction_counts.md):
+    // BOFF: cs[] holds the BYTE offset of the referenced row and the trip multiplies nothing -- all but <16, 8, 3> (68 -> 76 -> 36);
+    // ROWB_INV: the row stores' offsets as one lane-invariant register + a uniform term -- all but the two-level cross-rank instances
+    //       (<16, 5, 3, XRM = 2>: 44 -> 56 -> 44);
+    // UMASK: the mask of lanes without columns under ONE workgroup-uniform branch per trip and no select on the rows of Hmd -- all but
+    //       the fused launches at 16 lanes per row (<16, 5, 3, FUSE>: 120 -> 140 -> 108; either half alone costs it 16 bytes).
+    constexpr bool BOFF = !(EW == 8 && LPR == 16), ROWB_INV = !XTWO, UMASK = !(FUSE && LPR == 16);
     extern __shared__ double lds[];
     __shared__ double sh8[8 * PWAVES];
     __shared__ double shp[8 * PWAVES];
@@ -500,10 +509,14 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
 #define ROW(r) (lo + SLOT(r))
 #define ROK(r) (ROW(r) < hi)
 #define OK(r) (ROK(r) && colok)
+    // byte offset of the lane's 16 bytes of row slot r inside a region of the exchange buffer: one lane-invariant register + a uniform term
+    const unsigned rowb0 = ((unsigned)(lo + slot0) * (unsigned)d.ld + 2u * (unsigned)sub) * 8u;
+#define ROWB(r) (ROWB_INV ? (rowb0 + (unsigned)((r) * RSTEP) * (unsigned)d.ld * 8u) : (((unsigned)ROW(r) * gld + 2 * sub) * 8u))
     const int refresh = c->pipe_refresh;
     // (bits 16..23 = this reduction's own figure; the option psync8_backoff fills them where psync_backoff leaves them empty)
     const int backoff = (c->psync_backoff & 0xff00ffff) | ((((c->psync_backoff >> 16) & 0xff) ? ((c->psync_backoff >> 16) & 0xff) : (c->psync8_backoff & 0xff)) << 16);
     const double2 zz = make_double2(0.0, 0.0);
+    const unsigned gld = (unsigned)d.ld;
     constexpr bool LOC = !CSR && R * EW <= 15;                     // (four row slots: the source selection costs registers that spill)
     constexpr bool MULTI = LOC && !(FUSE && LPR >= 16);            // three instances of the trip loop (per-wave local columns), see below
     double2 eta[R], rr[R], md[R], hmd[R], cmd[R], ctr[R];
@@ -513,6 +526,8 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
         const int rc = rok ? ROW(r) : lo;
         const int64_t o = (int64_t)rc * d.ld + (colok ? 2 * sub : 0);
         double2 y = ld2(Yl + o), g = ld2(gl + o);
+        // INVARIANT (the trip's product and Hmd loops rely on it): a lane without a row (row slot past `hi`) or without columns holds
+        // exact zeros of Y and grad -- in LDS and, through r = md = grad, in every resident vector of the tCG
         if (!OK(r)) { y = zz; g = zz; }
         Ys[r * PB + threadIdx.x] = y; Gs[r * PB + threadIdx.x] = g;
         eta[r] = zz; rr[r] = g; md[r] = g; hmd[r] = zz; cmd[r] = zz; ctr[r] = zz;       // tCG.m:102-157
@@ -536,7 +551,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
         int kw[EW > 0 ? EW : 1];
 #pragma unroll
         for (int w = 0; w < EW; ++w) {
-            if (!rok) vw[w] = 0.0;
+            if (!rok) vw[w] = 0.0;                                 // INVARIANT: a row slot past `hi` has no entries -- its products are exact zeros
             kw[w] = vw[w] == 0.0 ? 3 : (cw[w] == rc ? 0 : ((cw[w] >= lo && cw[w] < hi) ? 1 : 2));
         }
 #pragma unroll
@@ -554,10 +569,15 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
                 pds[t * ROWS + SLOT(r)] = rok ? d.xr_paddr[(int64_t)t * d.n_loc + rc] : 0ULL;
         }
         if (sub == 0) {
-            eGs[SLOT(r)] = rok ? egv : 0.0;
+            eGs[SLOT(r)] = rok ? egv : 0.0;                        // INVARIANT: ... and eG = 0
 #pragma unroll
             for (int w = 0; w < EW; ++w) {
-                cs[w * ROWS + SLOT(r)] = cw[w];
+                // the BYTE offset of the referenced row inside a region of the exchange buffer: nothing of it depends on the trip, so the
+                // trip adds the region's base and the lane's column offset and multiplies nothing.  Below 2^32 with room to spare: an
+                // instance holds n_loc <= MSDP_MAX_GRID x ROWS rows of ld <= 2 LPR doubles (persist_plan) -- 6.3 MB per region for
+                // <16, *, 3>, 4.2 MB for <8, *, 2>, seven regions at most; XR: a region is (xr_cap + xr_halo) x ld x 8 bytes and four of
+                // them are the 32-bit num_records of rs_md
+                cs[w * ROWS + SLOT(r)] = BOFF ? (int)((unsigned)cw[w] * gld * 8u) : cw[w];
                 vs[w * ROWS + SLOT(r)] = vw[w];
                 const int li = cw[w] - lo;
                 const int el = (li / RSTEP) * PB + (li % RSTEP) * LPR;          // element of row li's lane 0 in a half of HQs
@@ -626,7 +646,9 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
     // the gradient rows of the current point: where an earlier launch left them (d.Gr) until a step has been accepted in THIS launch
     __amdgpu_buffer_rsrc_t rs_g = __builtin_amdgcn_make_buffer_rsrc(cur ? d.Gr[1] : d.Gr[0], 0, half_bytes, 0x00020000);
     unsigned g_base = 0u;
-    const unsigned gld = (unsigned)d.ld, gcol = colok ? 2 * sub : 0;
+    const unsigned gcol = colok ? 2 * sub : 0, gcol8 = gcol * 8u;
+    // lanes without columns (ld < 2 LPR) exist in this launch at all: workgroup-uniform, decides whether the trip pays for their mask
+    const bool idle_lanes = d.ld < 2 * LPR;
     // CSR rows: C[row, :] * X[:, my columns] with X read through rs at byte offset base -- lane group epi takes the entries s0 + epi,
     // s0 + epi + EP, ..., eight of them in flight per lane; the groups' partial products are added, the owner keeps the sum.
     // The lane's first eight (column, value) pairs of every row slot are static: they stay in registers for the whole launch where there
@@ -725,8 +747,8 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
             _Pragma("unroll") for (int r = 0; r < R; ++r) \
             _Pragma("unroll") for (int w = 0; w < NG; ++w) { \
                 if ((w0) + w < EW) { \
-                    const int cidx = cs[((w0) + w) * ROWS + SLOT(r)]; \
-                    X[r][w] = ld2_cp<XTWO ? 17 : MSDP_CPOL_SC1>((rs), (base) + ((unsigned)cidx * gld + gcol) * 8u); } } } while (0)
+                    const unsigned coff = (unsigned)cs[((w0) + w) * ROWS + SLOT(r)]; \
+                    X[r][w] = ld2_cp<XTWO ? 17 : MSDP_CPOL_SC1>((rs), (base) + (BOFF ? coff + gcol8 : (coff * gld + gcol) * 8u)); } } } while (0)
 #define PIPE_FOLDX(r, acc, w0) do { \
             _Pragma("unroll") for (int w = 0; w < NG; ++w) { \
                 if ((w0) + w < EW) { \
@@ -781,15 +803,21 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
             // the neighbours' rows of last trip's Hmd: requested inside that trip's reduction already (have_x), except behind a refresh
             if (!CSR && !have_x) PIPE_ISSUE(rs_md, (xq ^ 1u) * half_bytes, NL);
             pre_sums();
+            // (a lane without columns gathers column 0 of the rows: its product is masked -- under ONE workgroup-uniform branch per trip, so
+            // that a launch whose lanes all have columns, ld = 2 LPR, pays nothing for it; CSR rows mask inside csr_gather.  A row slot
+            // past `hi` needs no mask: its vs[] are zero, set-up)
+            auto products = [&](auto masked) {
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
-                double2 a = zz;
-                if (CSR) a = csr_gather(r, rs_md, (xq ^ 1u) * half_bytes);
-                else { PIPE_FOLDL(r, a, HQs + (xq ^ 1u) * R * PB); PIPE_FOLDX(r, a, NL); }
-                if (!colok) a = zz;
-                ctr[r].x = fma(-alpha, a.x, ctr[r].x); ctr[r].y = fma(-alpha, a.y, ctr[r].y);      // C tangent(r') = C tangent(r) - alpha C Hmd
-                cmd[r].x = fma(beta, cmd[r].x, ctr[r].x); cmd[r].y = fma(beta, cmd[r].y, ctr[r].y);  // C md' = C tangent(r') + beta C md
-            }
+                for (int r = 0; r < R; ++r) {
+                    double2 a = zz;
+                    if (CSR) a = csr_gather(r, rs_md, (xq ^ 1u) * half_bytes);
+                    else { PIPE_FOLDL(r, a, HQs + (xq ^ 1u) * R * PB); PIPE_FOLDX(r, a, NL); }
+                    if (decltype(masked)::value && !colok) a = zz;
+                    ctr[r].x = fma(-alpha, a.x, ctr[r].x); ctr[r].y = fma(-alpha, a.y, ctr[r].y);      // C tangent(r') = C tangent(r) - alpha C Hmd
+                    cmd[r].x = fma(beta, cmd[r].x, ctr[r].x); cmd[r].y = fma(beta, cmd[r].y, ctr[r].y);  // C md' = C tangent(r') + beta C md
+                }
+            };
+            if (UMASK) { if (!CSR && idle_lanes) products(std::true_type()); else products(std::false_type()); } else products(std::true_type());
         }
         have_x = false;
         // every `refresh`-th trip publishes tangent(r) and md of ITS start next to Hmd (no barrier of its own: the reduction orders them
@@ -800,19 +828,21 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
         for (int r = 0; r < R; ++r) {
             const double2 acc = cmd[r];
             const double2 y = Ys[r * PB + threadIdx.x], mdr = md[r], rv = rr[r];
-            const double dot = msdp_group_sum<LPR>(acc.x * y.x + acc.y * y.y);
+            const double dot = msdp_group_sum_all<LPR>(acc.x * y.x + acc.y * y.y);
             const double eg = eGs[SLOT(r)];
+            // (a lane without a row or without columns: acc, y and mdr are exact zeros -- the invariants of set-up, kept by the masks of
+            // the products -- and eg and dot are finite, so hq is +0 without a select)
             double2 hq = make_double2(acc.x - y.x * dot - mdr.x * eg, acc.y - y.y * dot - mdr.y * eg);
-            if (!OK(r)) hq = zz;
+            if (!UMASK && !OK(r)) hq = zz;
             hmd[r] = hq;
             if (MULTI) HQs[xq * R * PB + r * PB + threadIdx.x] = hq;    // (read by the instances with local columns only)
-            if (OK(r)) st2_sc1(rs_md, xq * half_bytes + ((unsigned)ROW(r) * gld + 2 * sub) * 8u, hq);
+            if (OK(r)) st2_sc1(rs_md, xq * half_bytes + ROWB(r), hq);
             xr_push(r, xq, hq);
             if (pub) {
-                const double dn = msdp_group_sum<LPR>(rv.x * y.x + rv.y * y.y);
+                const double dn = msdp_group_sum_all<LPR>(rv.x * y.x + rv.y * y.y);
                 if (OK(r)) {
-                    st2_sc1(rs_md, 2u * half_bytes + ((unsigned)ROW(r) * gld + 2 * sub) * 8u, mdr);
-                    st2_sc1(rs_md, 3u * half_bytes + ((unsigned)ROW(r) * gld + 2 * sub) * 8u, make_double2(rv.x - y.x * dn, rv.y - y.y * dn));
+                    st2_sc1(rs_md, 2u * half_bytes + ROWB(r), mdr);
+                    st2_sc1(rs_md, 3u * half_bytes + ROWB(r), make_double2(rv.x - y.x * dn, rv.y - y.y * dn));
                 }
                 xr_push(r, 2u, mdr);
                 xr_push(r, 3u, make_double2(rv.x - y.x * dn, rv.y - y.y * dn));
@@ -899,7 +929,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
         for (int r = 0; r < R; ++r) {
             const double2 y = Ys[r * PB + threadIdx.x];
             const double2 vv = make_double2(rr[r].x + beta * md[r].x, rr[r].y + beta * md[r].y);
-            const double dot = msdp_group_sum<LPR>(vv.x * y.x + vv.y * y.y);
+            const double dot = msdp_group_sum_all<LPR>(vv.x * y.x + vv.y * y.y);
             md[r] = make_double2(vv.x - y.x * dot, vv.y - y.y * dot);
         }
         direct = pub;
@@ -923,7 +953,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
     // trips use it from trip `refresh` on, long behind the first trip's gather)
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        if (OK(r)) st2_sc1(rs_md, 2u * half_bytes + ((unsigned)ROW(r) * gld + 2 * sub) * 8u, md[r]);
+        if (OK(r)) st2_sc1(rs_md, 2u * half_bytes + ROWB(r), md[r]);
         xr_push(r, 2u, md[r]);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1002,11 +1032,11 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
         const double2 he = make_double2(rr[r].x - g.x, rr[r].y - g.y);
         tv[2] += e0.x * (g.x + 0.5 * he.x) + e0.y * (g.y + 0.5 * he.y);
         const double2 x = make_double2(y.x + e0.x, y.y + e0.y);
-        double nn = sqrt(msdp_group_sum<LPR>(x.x * x.x + x.y * x.y));
+        double nn = sqrt(msdp_group_sum_all<LPR>(x.x * x.x + x.y * x.y));
         if (!(nn > 0.0)) nn = 1.0;                                  // empty row slot
         const double2 ypr = OK(r) ? make_double2(x.x / nn, x.y / nn) : zz;
         YPs[r * PB + threadIdx.x] = ypr;
-        if (OK(r)) st2_sc1(rs_md, yx_base + ((unsigned)ROW(r) * gld + 2 * sub) * 8u, ypr);
+        if (OK(r)) st2_sc1(rs_md, yx_base + ROWB(r), ypr);
     }
     FSTAMP(3);
     // (my proposal rows are performed before the post: the wait is inside)
@@ -1016,7 +1046,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
     auto prop_finish = [&](int r, double2 acc) {
         if (!colok) acc = zz;
         const double2 ypr = YPs[r * PB + threadIdx.x];
-        const double dot = msdp_group_sum<LPR>(acc.x * ypr.x + acc.y * ypr.y);
+        const double dot = msdp_group_sum_all<LPR>(acc.x * ypr.x + acc.y * ypr.y);
         const double2 gpr = OK(r) ? make_double2(acc.x - ypr.x * dot, acc.y - ypr.y * dot) : zz;
         GPs[r * PB + threadIdx.x] = gpr;
         tv[1] += gpr.x * gpr.x + gpr.y * gpr.y;
@@ -1024,7 +1054,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
             EGPs[SLOT(r)] = ROK(r) ? dot : 0.0;
             if (ROK(r)) tv[0] += 0.5 * dot;
         }
-        if (OK(r)) st2_sc1(rs_md, gx_base + ((unsigned)ROW(r) * gld + 2 * sub) * 8u, gpr);
+        if (OK(r)) st2_sc1(rs_md, gx_base + ROWB(r), gpr);
     };
     if (CSR) {
 #pragma unroll
@@ -1034,7 +1064,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
 #pragma unroll
         for (int r = 0; r < R; ++r)
 #pragma unroll
-            for (int w = 0; w < EW; ++w) XG[r][w] = ld2_sc1(rs_md, yx_base + ((unsigned)cs[w * ROWS + SLOT(r)] * gld + gcol) * 8u);
+            for (int w = 0; w < EW; ++w) XG[r][w] = ld2_sc1(rs_md, yx_base + (BOFF ? (unsigned)cs[w * ROWS + SLOT(r)] + gcol8 : ((unsigned)cs[w * ROWS + SLOT(r)] * gld + gcol) * 8u));
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             double2 acc = zz;
@@ -1047,7 +1077,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
         for (int r = 0; r < R; ++r) {
             double2 xw[EW > 0 ? EW : 1];
 #pragma unroll
-            for (int w = 0; w < EW; ++w) xw[w] = ld2_sc1(rs_md, yx_base + ((unsigned)cs[w * ROWS + SLOT(r)] * gld + gcol) * 8u);
+            for (int w = 0; w < EW; ++w) xw[w] = ld2_sc1(rs_md, yx_base + (BOFF ? (unsigned)cs[w * ROWS + SLOT(r)] + gcol8 : ((unsigned)cs[w * ROWS + SLOT(r)] * gld + gcol) * 8u));
             double2 acc = zz;
 #pragma unroll
             for (int w = 0; w < EW; ++w) { const double vv = vs[w * ROWS + SLOT(r)]; acc.x = fma(vv, xw[w].x, acc.x); acc.y = fma(vv, xw[w].y, acc.y); }
@@ -1125,6 +1155,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
 #undef ROW
 #undef ROK
 #undef OK
+#undef ROWB
 }
 
 template <int LPR, int EW, int R, bool TRACE = false, bool FUSE = false, int XRM = 0, int EP = 1>

@@ -215,7 +215,7 @@ int msdp_destroy(msdp_handle h);
  * frees it (a long-lived host such as MATLAB calls it when it unloads the binding). */
 int msdp_release_cache(void);
 /* The uncached device memory behind the grid synchronisations and row exchanges comes from per-process arenas with a coalescing
- * sub-allocator (msdp_api.hip): bytes the arenas hold, bytes handed out to live handles, number of arenas.  The pool grows to
+ * sub-allocator (msdp_mem.hip): bytes the arenas hold, bytes handed out to live handles, number of arenas.  The pool grows to
  * the high-water mark of what was live together; arenas return to the driver only while no uncached block of the process is
  * live (beyond MSDP_UC_POOL_CAP bytes -- default 1 GiB -- when the last one is freed, all of them in msdp_release_cache). */
 int msdp_debug_pool_stats(int64_t* pool_bytes, int64_t* live_bytes, int64_t* arenas);

@@ -20,15 +20,6 @@
 #include <cstring>
 #include <vector>
 
-int msdp_dev_alloc_bytes(msdp_handle h, void** out, size_t bytes);
-int msdp_dense_nS(int n);
-int msdp_k_sum_to_fwd(msdp_handle h, int which, double* out);
-int msdp_allreduce_partials(msdp_handle h, int first, int count);          // msdp_api.hip
-int msdp_allgather_rows(msdp_handle h, const double* local_rows);
-int msdp_allgather_vec(msdp_handle h, const double* local, double* all, size_t count_per_rank);
-int msdp_dense_gemm(msdp_handle h, int nmat, const double* const* M, const double* const* X, const double* scale,
-                    const int* active_flag, const double** slab_out, int64_t* stride_out, int* SK_out);
-
 // item value = sum over the item's nonzeros (i,j,val) of val * <Ya_i, Yb_j>   (one LPR-lane group per item)
 template <int LPR, int NCH>
 __global__ __launch_bounds__(MSDP_BLOCK) void k_sddmm(AffineDev a, const double* __restrict__ Ya,
@@ -1750,14 +1741,7 @@ int msdp_affine_set_multipliers(msdp_handle h, const double* y, double sigma) {
         }                                                                                            \
     } while (0)
 
-int msdp_dense_hess_epilogue_obl(msdp_handle h, const double* slab, int64_t stride, int SK);   // msdp_dense.hip
-int msdp_dense_gemm_slabs(msdp_handle h, int nmat);
-int msdp_dense_gemm_at(msdp_handle h, hipStream_t stream, int slab_first, int slabs_reserve, int nmat, const double* const* M,
-                       const double* const* X, const double* scale, const int* active_flag, const double** slab_out,
-                       int64_t* stride_out, int* SK_out);
 int msdp_sphere_hess_raw(msdp_handle h, const double* slab, int64_t stride, int SK);           // below
-int msdp_dense_gemm_side(msdp_handle h, const double* M, const double* X, double scale, const int* active_flag, SideJob sj,
-                         int* njobs_out, const double** slab_out, int64_t* stride_out, int* SK_out);   // msdp_dense.hip
 
 // k_sddmm has no reductions, so its grid follows the number of work items, not the number of rows
 static int sddmm_grid(const AffineDev& a, int ld) {
@@ -1897,7 +1881,6 @@ static int launch_support_spmm(msdp_handle h, const AffineDev& a, const double* 
 
 // The dense products of the closures: the MFMA contraction of msdp_dense.hip, or -- multiblock kind with per-block storage -- one
 // wave per 16-row tile of a block, written to slab 0 (SK = 1)
-int msdp_dense_ensure_slab(msdp_handle h, size_t need);
 static int affine_gemm(msdp_handle h, int nmat, const double* const* M, const double* const* X, const double* scale, const int* active_flag,
                        const double** slab_out, int64_t* stride_out, int* SK_out) {
     AffineState* st = astate(h);
@@ -2250,7 +2233,7 @@ int msdp_affine_al_primal(msdp_handle h, double* obj, double* Ax_host) {
     DISPATCH_LPR_A(k_rowdot_slabs, h, d.G, d, Ys, slab, stride, SK, 1.0, (double*)nullptr, (double*)nullptr, P_S1);
     HIPCHK(hipGetLastError());
     if ((rc = msdp_allreduce_partials(h, P_S1, 1))) return rc;
-    if ((rc = msdp_k_sum_to_fwd(h, P_S1, &d.ctl->fx_prop))) return rc;
+    if ((rc = msdp_k_sum_to(h, P_S1, &d.ctl->fx_prop))) return rc;
     double v = 0.0;
     HIPCHK(msdp_memcpy_async(&v, &d.ctl->fx_prop, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(msdp_memcpy_async(Ax_host, a.w, (size_t)a.m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -2296,7 +2279,7 @@ int msdp_affine_al_dual(msdp_handle h, const double* y_host, double* z_host) {
         HIPCHK(msdp_memcpy_async(z_host, zall, (size_t)a.n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     } else {
         if ((rc = msdp_allreduce_partials(h, P_S2, 1))) return rc;
-        if ((rc = msdp_k_sum_to_fwd(h, P_S2, &d.ctl->fx_prop))) return rc;
+        if ((rc = msdp_k_sum_to(h, P_S2, &d.ctl->fx_prop))) return rc;
         hipLaunchKernelGGL(k_sub_diag, dim3((a.n + 255) / 256), dim3(256), 0, h->stream, a.n, a.nS, d.Sdual, (const double*)nullptr, (const double*)&d.ctl->fx_prop);
         HIPCHK(hipGetLastError());
         HIPCHK(msdp_memcpy_async(z_host, &d.ctl->fx_prop, sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -3009,7 +2992,7 @@ int msdp_dual_outer_step_impl(msdp_handle h, double* scal_host, double* Af_host,
         hipLaunchKernelGGL(k_dmb_outer, dim3(d.G), dim3(MSDP_BLOCK), 0, h->stream, d, *st->blk, d.Sdual, (const double*)ds->Sg, Sf, ds->x,
                            (const double*)ds->bA, (const double*)d.Cd, sigma, ds->generic ? 1 : 0, d.W0);
         HIPCHK(hipGetLastError());
-        if ((rc = msdp_k_sum_to_fwd(h, P_S2, ds->scal + 2)) || (rc = msdp_k_sum_to_fwd(h, P_S3, ds->scal + 3))) return rc;
+        if ((rc = msdp_k_sum_to(h, P_S2, ds->scal + 2)) || (rc = msdp_k_sum_to(h, P_S3, ds->scal + 3))) return rc;
         HIPCHK(msdp_memcpy_async(scal_host, ds->scal + 1, 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         if (ds->nf > 0) HIPCHK(msdp_memcpy_async(Af_host, ds->Af, (size_t)ds->nf * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         if (ds->zrows > 0 && z_host) HIPCHK(msdp_memcpy_async(z_host, d.W0, (size_t)ds->zrows * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -3029,7 +3012,7 @@ int msdp_dual_outer_step_impl(msdp_handle h, double* scal_host, double* Af_host,
         hipLaunchKernelGGL(k_dgen_outer, dim3(d.G), dim3(MSDP_BLOCK), 0, h->stream, d, a.nS, (const double*)d.Sdual, (const double*)ds->Sg,
                            ds->x, (const double*)ds->bA, (const double*)d.Cd, sigma);
         HIPCHK(hipGetLastError());
-        if ((rc = msdp_k_sum_to_fwd(h, P_S2, ds->scal + 2)) || (rc = msdp_k_sum_to_fwd(h, P_S3, ds->scal + 3))) return rc;
+        if ((rc = msdp_k_sum_to(h, P_S2, ds->scal + 2)) || (rc = msdp_k_sum_to(h, P_S3, ds->scal + 3))) return rc;
         HIPCHK(msdp_memcpy_async(scal_host, ds->scal + 1, 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         if (ds->nf > 0) HIPCHK(msdp_memcpy_async(Af_host, ds->Af, (size_t)ds->nf * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
@@ -3039,7 +3022,7 @@ int msdp_dual_outer_step_impl(msdp_handle h, double* scal_host, double* Af_host,
     if ((rc = launch_A(h, a, st->nnz, Ys, Ys, (const int*)nullptr, 0, 0, (double*)nullptr, sigma))) return rc;
     hipLaunchKernelGGL(k_dual_y, dim3(d.G), dim3(MSDP_BLOCK), 0, h->stream, a.m, a.w, ds->dinv, ds->Ac, a.b, d.P, (const int*)nullptr, 0);
     HIPCHK(hipGetLastError());
-    if ((rc = msdp_k_sum_to_fwd(h, P_S1, ds->scal + 1))) return rc;
+    if ((rc = msdp_k_sum_to(h, P_S1, ds->scal + 1))) return rc;
     if (ds->nf > 0) {
         hipLaunchKernelGGL(k_dual_free, dim3(ds->nf), dim3(256), 0, h->stream, ds->bjc, ds->bir, ds->bpr, (const double*)a.w, ds->cf,
                            (const double*)nullptr, sigma, ds->Af, (const int*)nullptr, 0);
@@ -3053,7 +3036,7 @@ int msdp_dual_outer_step_impl(msdp_handle h, double* scal_host, double* Af_host,
     hipLaunchKernelGGL(k_dual_outer, dim3(d.G), dim3(MSDP_BLOCK), 0, h->stream, d, a.nS, d.Sdual, (const double*)ds->Sg, ds->x,
                        (const double*)ds->bA, (const double*)d.Cd, sigma, d.W0);
     HIPCHK(hipGetLastError());
-    if ((rc = msdp_k_sum_to_fwd(h, P_S2, ds->scal + 2)) || (rc = msdp_k_sum_to_fwd(h, P_S3, ds->scal + 3))) return rc;
+    if ((rc = msdp_k_sum_to(h, P_S2, ds->scal + 2)) || (rc = msdp_k_sum_to(h, P_S3, ds->scal + 3))) return rc;
     HIPCHK(msdp_memcpy_async(scal_host, ds->scal + 1, 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (ds->nf > 0) HIPCHK(msdp_memcpy_async(Af_host, ds->Af, (size_t)ds->nf * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(msdp_memcpy_async(z_host, d.W0, (size_t)a.n * sizeof(double), hipMemcpyDeviceToHost, h->stream));

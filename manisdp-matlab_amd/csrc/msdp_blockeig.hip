@@ -132,9 +132,6 @@ __global__ __launch_bounds__(256) void k_be_dense_epi(int n, int b, const double
         st2(Xio + o, make_double2(fma(f1, acc.x, fma(g, x.x, -f2 * pv.x)), fma(f1, acc.y, fma(g, x.y, -f2 * pv.y))));
     }
 }
-int msdp_dense_gemm_at(msdp_handle h, hipStream_t stream, int slab_first, int slabs_reserve, int nmat, const double* const* M,
-                       const double* const* X, const double* scale, const int* active_flag, const double** slab_out,
-                       int64_t* stride_out, int* SK_out);          // msdp_dense.hip
 
 // (A persistent form of the filter -- panels of the recurrence in registers, neighbour rows through an exchange buffer with sc1
 // accesses, one grid barrier per step, a whole round per launch -- was built and measured in round 3: 7.2 us per step against

@@ -12,9 +12,6 @@
 #include "msdp_device.h"
 #include <vector>
 
-int msdp_affine_block_source(msdp_handle h, int64_t row0, int64_t n, int64_t* off, int64_t* ld);   // msdp_affine.hip (per-block storage)
-int msdp_dense_nS(int n);
-
 #define JAC_MAXN 256
 #define JAC_THREADS 1024
 

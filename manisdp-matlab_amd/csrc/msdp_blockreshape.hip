@@ -18,8 +18,6 @@
 #include "msdp_device.h"
 #include <vector>
 
-void msdp_block_eigs_release(msdp_handle h);                 // msdp_blockjacobi.hip (the workspace is shared with msdp_block_eigs)
-
 #define BR_MAXP 64                 // G and Q of a block in LDS: 2 * 64 * 64 doubles = 64 KB of the CU's 160 KB (two workgroups per CU)
 #define BR_THREADS 256
 #define BR_WAVES (BR_THREADS / 64)

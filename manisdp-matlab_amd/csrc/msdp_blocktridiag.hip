@@ -32,10 +32,6 @@
 #include <algorithm>
 #include <vector>
 
-int msdp_affine_block_source(msdp_handle h, int64_t row0, int64_t n, int64_t* off, int64_t* ld);   // msdp_affine.hip (per-block storage)
-int msdp_dense_nS(int n);
-void msdp_block_eigs_release(msdp_handle h);                                                     // msdp_blockjacobi.hip
-
 #define BTL_MAXN MSDP_BLOCK_EIGS_LARGE_MAXN
 #define BTL_MAXK 8
 #define BTL_THREADS 1024

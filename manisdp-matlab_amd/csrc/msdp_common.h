@@ -148,7 +148,7 @@ struct Dev {
     // partition with locality.
     double* xr_rows[4];
     int xr_cap, xr_me, xr_halo;
-    // "push" exchange (msdp_api.hip halo_setup): a member's buffer = [its rows (xr_cap)] [one slot per foreign row its rows of C
+    // "push" exchange (msdp_comm.hip halo_setup): a member's buffer = [its rows (xr_cap)] [one slot per foreign row its rows of C
     // reference]; buffer-local column indices of its rows (ELL copy [w][xr_cap] and CSR), and for every local row up to two
     // (member, position there) pairs it has to be stored to as well ([2][n_loc], member -1 = none)
     const int* xr_ellc; const int* xr_colind; const int* xr_pq; const int* xr_pidx;
@@ -267,7 +267,7 @@ struct msdp_handle_s {
     bool presharded = false;       // created per shard (dense synthetic): row0/n_loc fixed at creation
     double* full_buf = nullptr;    // gather buffer (nranks x cap rows) when the rows are sharded
     // halo exchange (sparse C, option "halo_exchange"): instead of all rows of the direction every rank receives only the rows
-    // its rows of C reference (msdp_api.hip, "Halo exchange")
+    // its rows of C reference (msdp_comm.hip, "Halo exchange")
     struct Halo* halo = nullptr;
     struct LocalGroup* lgroup = nullptr;   // in-process stand-in for the RCCL communicator (msdp_comm_init_local)
     unsigned long long* xr_paddr = nullptr; size_t xr_paddr_cap = 0; double* xr_paddr_key[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; int xr_paddr_ld = 0, xr_paddr_n = 0; const int* xr_paddr_pq = nullptr;   // cross-rank push addresses and what they were built from
@@ -338,32 +338,183 @@ struct msdp_handle_s {
     int fused_sig_lpr = 0, fused_sig_ew = 0, fused_sig_G = 0, fused_sig_ok = 0;
 };
 
-// --- launchers implemented in the .hip units (all asynchronous on h->stream) ---
+#define MSDP_CHECK_H(h)                                     \
+    if (!(h)) { msdp_set_error("null handle"); return MSDP_EINVAL; }
+#define MSDP_XS_MAX_RANKS 64
+#define MSDP_TCG_CHUNK 8          // tCG trips per enqueued chunk (one hipGraph of 3 x 8 kernel nodes)
+
+static inline bool msdp_dual_kind(msdp_handle h) { return h->kind == MSDP_KIND_DUAL_UNITDIAG || h->kind == MSDP_KIND_DUAL || h->kind == MSDP_KIND_DUAL_MULTIBLOCK; }
+static inline int msdp_host_cur(msdp_handle h) { return h->h_ctl->cur; }
+// equal per-rank row count so the all-gather is one uniform RCCL call
+static inline int msdp_rows_capacity(msdp_handle h) { return (h->d.n + h->nranks - 1) / h->nranks; }
+
+// --- every function one .hip unit defines and another calls, by defining unit (launchers: asynchronous on h->stream) ---
+struct SideJob;                                               // msdp_affine_dev.h
+// msdp_api.hip
+int msdp_alloc_vectors(msdp_handle h, int pcap);
+int msdp_alloc_common(msdp_handle h);
+int msdp_upload_sparse_rows(msdp_handle h);
+int msdp_ensure_state(msdp_handle h);
+// msdp_mem.hip
+int msdp_dev_alloc_bytes(msdp_handle h, void** out, size_t bytes);            // freed with the handle, or by msdp_dev_free
+int msdp_dev_alloc_uncached_bytes(msdp_handle h, void** out, size_t bytes);   // from the pool of exchange memory (plain memory when that fails)
+void msdp_dev_free(msdp_handle h, void* p);
+void* msdp_uc_alloc(size_t bytes);                            // per-process pool of fine-grained blocks
+bool msdp_uc_free(void* p);
+void msdp_uc_release_pool();
+bool msdp_host_kit_take(msdp_handle h);
+void msdp_host_kit_give(msdp_handle h);
+void msdp_host_kits_release();
+template <typename T> inline int msdp_dev_alloc(msdp_handle h, T** out, size_t count) {
+    void* p = nullptr;
+    int rc = msdp_dev_alloc_bytes(h, &p, (count ? count : 1) * sizeof(T));
+    if (!rc) *out = (T*)p;
+    return rc;
+}
+template <typename T> inline int msdp_dev_alloc_uncached(msdp_handle h, T** out, size_t count) {
+    void* p = nullptr;
+    int rc = msdp_dev_alloc_uncached_bytes(h, &p, (count ? count : 1) * sizeof(T));
+    if (!rc) *out = (T*)p;
+    return rc;
+}
+// msdp_comm.hip
+int msdp_allreduce_partials(msdp_handle h, int first, int count);   // no-op when nranks == 1
+int msdp_allreduce_array(msdp_handle h, double* buf, size_t count);
+int msdp_allgather_rows(msdp_handle h, const double* local_rows);   // local -> d.full
+int msdp_allgather_vec(msdp_handle h, const double* local, double* all, size_t count_per_rank);
+int msdp_exchange_rows(msdp_handle h, const double* local_rows);    // sparse C: halo rows only when option halo_exchange is set, else the all-gather
+int msdp_exchange_rows_sums(msdp_handle h, const double* local_rows);
+void msdp_comm_release(msdp_handle h);
+void msdp_halo_release(msdp_handle h);
+void msdp_local_leave(msdp_handle h);
+int msdp_local_barrier(msdp_handle h);
+int msdp_local_vote_min(msdp_handle h, int v, int* out);
+int msdp_xr_begin(msdp_handle h, bool* use);
+int msdp_xr_launch(msdp_handle h);
+int msdp_xr_tail(msdp_handle h);
+int msdp_xr_check(msdp_handle h);
+// msdp_rtr.hip
+int msdp_push_ctl(msdp_handle h);
+void msdp_fill_ctl(msdp_handle h, const msdp_rtr_opts* o);
+bool msdp_use_graphs(msdp_handle h);
+int msdp_tcg_begin(msdp_handle h);
+int msdp_enqueue_trips(msdp_handle h, int cnt);
+int msdp_ensure_chunk_graph(msdp_handle h, int CH);
+int msdp_launch_chunk(msdp_handle h, int CH, bool graph);
+void msdp_restore_status_ptr(msdp_handle h);
+// msdp_kernels.hip
 int msdp_launch_costgrad(msdp_handle h, int slot);            // Y[slot] -> Gr[slot], eG[slot], P_F, P_GG
 int msdp_launch_hess(msdp_handle h);
 int msdp_launch_tcg_init(msdp_handle h);
 int msdp_launch_upd1(msdp_handle h);
 int msdp_launch_upd2(msdp_handle h);
-#define MSDP_XS_MAX_RANKS 64
-int msdp_exchange_rows_sums(msdp_handle h, const double* local_rows);    // msdp_api.hip
-int msdp_trip1_ok(msdp_handle h);                             // msdp_trip1.hip: sharded trip with one all-reduce applies to this handle
-int msdp_launch_trip1_init(msdp_handle h);
-int msdp_launch_trip1_head(msdp_handle h, bool direct);
-int msdp_launch_trip1_upd(msdp_handle h);
-int msdp_trip2_ok(msdp_handle h);                             // msdp_trip2.hip: two-launch trip applies to this handle
-int msdp_launch_trip2_init(msdp_handle h);
-int msdp_launch_trip2_head(msdp_handle h);
-int msdp_launch_trip2_upd(msdp_handle h);
 int msdp_launch_retract(msdp_handle h);                       // Y[cur]+eta -> Y[1-cur], P_RD
 int msdp_launch_rtr_begin(msdp_handle h);
 int msdp_launch_rtr_decide(msdp_handle h);
-int msdp_alloc_vectors(msdp_handle h, int pcap);
-int msdp_persist_eligible(msdp_handle h);                     // msdp_persist.hip
+int msdp_k_pack(msdp_handle h, const double* src, double* dst, int n, int p, int ld, bool colmajor);
+int msdp_k_unpack(msdp_handle h, const double* src, double* dst, int n, int p, int ld, bool colmajor);
+int msdp_k_proj_obl(msdp_handle h, const double* Y, const double* U, double* V);
+int msdp_k_retr_obl(msdp_handle h, const double* Y, const double* U, double* Z, double alpha);
+int msdp_k_set_active(msdp_handle h, int active);
+int msdp_k_sum_to(msdp_handle h, int which, double* out);
+int msdp_k_fgram(msdp_handle h, const double* Y, double* part, int nblk, double* out);
+int msdp_k_frotate(msdp_handle h, int cap, int r, int ldn, const double* Y, const double* Q, double* Yn);
+int msdp_k_fappend(msdp_handle h, int cap, int k, int ldn, const double* Y, const double* V, double alpha, int normalize, double* Yn);
+// msdp_trip1.hip, msdp_trip2.hip
+int msdp_trip1_ok(msdp_handle h);                             // sharded trip with one all-reduce applies to this handle
+int msdp_launch_trip1_init(msdp_handle h);
+int msdp_launch_trip1_head(msdp_handle h, bool direct);
+int msdp_launch_trip1_upd(msdp_handle h);
+int msdp_trip2_ok(msdp_handle h);                             // two-launch trip applies to this handle
+int msdp_launch_trip2_init(msdp_handle h);
+int msdp_launch_trip2_head(msdp_handle h);
+int msdp_launch_trip2_upd(msdp_handle h);
+// msdp_persist.hip
+int msdp_persist_eligible(msdp_handle h);
 int msdp_launch_tcg_persist(msdp_handle h, int reset_slots = 1);   // whole tCG of the current TR iteration, one launch
-int msdp_launch_tr_tail(msdp_handle h);                       // retract + cost/grad at the proposal + accept/reject, one launch
 int msdp_persist_fused_ok(msdp_handle h);                     // whole trustregions() loop in one launch possible?
 int msdp_launch_rtr_fused(msdp_handle h);
 size_t msdp_psync_bytes();
-int msdp_allreduce_partials(msdp_handle h, int first, int count);   // no-op when nranks == 1
-int msdp_allgather_rows(msdp_handle h, const double* local_rows);   // local -> d.full
-int msdp_exchange_rows(msdp_handle h, const double* local_rows);    // sparse C: halo rows only when option halo_exchange is set, else the all-gather
+int msdp_tr_tail_grid(msdp_handle h);                         // (persist_grid)
+int msdp_persist_trace_dims(msdp_handle h, int* G, int* nj, int* j0);
+int msdp_xpersist_eligible(msdp_handle h, int nranks);
+size_t msdp_xpersist_slot_bytes();
+int msdp_xpersist_reset(hipStream_t stream, unsigned long long* slots, int* err);
+int msdp_xpersist_member(msdp_handle h, int nranks, int rank, double* const* rows, int halo_rows, Dev* out, int* plan3);
+int msdp_launch_tcg_xpersist_all(hipStream_t stream, int nranks, const Dev* devs, const int* plans, unsigned long long* slots, int* err);
+int msdp_launch_tcg_xpersist_one(hipStream_t stream, const Dev& dv, const int* plan, unsigned long long* slots, int* err);
+size_t msdp_xr2_block_bytes();
+size_t msdp_xr2_err_offset();
+int msdp_xr2_reset(hipStream_t stream, unsigned long long* blk);
+// msdp_trtail.hip
+int msdp_launch_tr_tail(msdp_handle h);                       // retract + cost/grad at the proposal + accept/reject, one launch
+int msdp_launch_tr_tail_xr(hipStream_t stream, const Dev& dv, unsigned long long* slots, int* err);
+// msdp_sphere.hip
+int msdp_sphere_proj(msdp_handle h, const double* Y, const double* U, double* V);
+int msdp_sphere_retr(msdp_handle h, const double* Y, const double* U, double* Z, double alpha);
+int msdp_sphere_upd2(msdp_handle h);
+int msdp_sphere_retract(msdp_handle h);
+// msdp_window.hip
+int msdp_window_eligible(msdp_handle h);
+int msdp_window_hess(msdp_handle h);
+void msdp_window_release(msdp_handle h);
+// msdp_dense.hip
+int msdp_dense_nS(int n);
+int msdp_dense_setup(msdp_handle h, const double* C);
+int msdp_dense_setup_synthetic(msdp_handle h, uint64_t seed);
+int msdp_dense_reserve(msdp_handle h, int nmat);
+int msdp_dense_ensure_slab(msdp_handle h, size_t need);
+int msdp_dense_costgrad(msdp_handle h, int slot);
+int msdp_dense_hess(msdp_handle h);
+int msdp_dense_hess_epilogue_obl(msdp_handle h, const double* slab, int64_t stride, int SK);
+int msdp_dense_gemm_slabs(msdp_handle h, int nmat);
+int msdp_dense_gemm(msdp_handle h, int nmat, const double* const* M, const double* const* X, const double* scale,
+                    const int* active_flag, const double** slab_out, int64_t* stride_out, int* SK_out);
+int msdp_dense_gemm_at(msdp_handle h, hipStream_t stream, int slab_first, int slabs_reserve, int nmat, const double* const* M,
+                       const double* const* X, const double* scale, const int* active_flag, const double** slab_out, int64_t* stride_out, int* SK_out);
+int msdp_dense_gemm_side(msdp_handle h, const double* M, const double* X, double scale, const int* active_flag, SideJob sj,
+                         int* njobs_out, const double** slab_out, int64_t* stride_out, int* SK_out);
+// msdp_densesym.hip
+int msdp_densesym_eligible(msdp_handle h, int nmat);
+int msdp_densesym_reserve(msdp_handle h, int nmat, size_t* slabs_out);
+int msdp_densesym_gemm(msdp_handle h, hipStream_t stream, int nmat, const double* const* M, const double* const* X, const double* scale, const int* active_flag);
+void msdp_densesym_release(msdp_handle h);
+// msdp_affine.hip
+int msdp_affine_setup(msdp_handle h, const int64_t* jc, const int64_t* ir, const double* pr, const double* b, const double* c);
+int msdp_affine_setup_blocked(msdp_handle h, int nb, const int64_t* block_n, const int64_t* jc, const int64_t* ir, const double* pr,
+                              const double* b, const double* c);   // multiblock kind, per-block storage
+void msdp_affine_release(msdp_handle h);
+int msdp_affine_set_multipliers(msdp_handle h, const double* y, double sigma);
+int msdp_affine_costgrad(msdp_handle h, int slot);
+int msdp_affine_hess(msdp_handle h);
+int msdp_affine_linesearch_cost(msdp_handle h, const double* Yt, double* val);
+int msdp_affine_al_primal(msdp_handle h, double* obj, double* Ax_host);
+int msdp_affine_al_dual(msdp_handle h, const double* y_host, double* z_host);
+int msdp_affine_get_block(msdp_handle h, int64_t row0, int64_t nbk, double* S);
+int msdp_affine_block_source(msdp_handle h, int64_t row0, int64_t n, int64_t* off, int64_t* ld);   // per-block storage
+void msdp_affine_algo_cost(msdp_handle h, double* bytes, double* flops);
+int msdp_dual_setup(msdp_handle h, const int64_t* at_jc, const int64_t* at_ir, const double* at_pr, const double* b, const double* c,
+                    const double* dAAt, int32_t nf, const int64_t* b_jc, const int64_t* b_ir, const double* b_pr, const double* cf, bool generic);
+int msdp_dual_set_zrows(msdp_handle h, int64_t zrows);
+int msdp_dual_g_identity(msdp_handle h);
+int msdp_dual_set_penalty_impl(msdp_handle h, double sigma, const double* wf_host);
+int msdp_dual_outer_step_impl(msdp_handle h, double* scal_host, double* Af_host, double* z_host);
+int msdp_dual_get_y_impl(msdp_handle h, double* y_host);
+// msdp_escape.hip, msdp_lanczos.hip, msdp_blockeig.hip
+int msdp_escape_impl(msdp_handle h, int k, double tol, int maxit, double* lam, double* V, double* lmax, int* iters, const double* Mdev);
+void msdp_escape_workspace_park(double* ptr, size_t cap_doubles);
+size_t msdp_lanczos_slot_bytes();
+int msdp_lanczos_persist_ok(msdp_handle h, int nq, const int* full_csr);
+int msdp_lanczos_persist_run(msdp_handle h, const double* z, const double* Q, int nq, double* V, double* X, double* dalpha,
+                             double* dbeta, unsigned long long* slots, int* err, int m0, int m1, const int* rp, const int* ci, const double* cv);
+int msdp_blockeig_eligible(msdp_handle h, const double* Mdev, bool w_loc);
+int msdp_blockeig_run(msdp_handle h, int n, const int* rp, const int* ci, const double* cv, const double* z, bool own_rows,
+                      const double* Ypt, int ld, int p, int k, double tol, int maxdeg, double lmax, double lmax_res, double lmin_est,
+                      bool cold, bool use_y, double* lam, double* V_dev, int* degree_out, bool* conv_out, double* err_out, double* lower_out, const double* Mdense);
+void msdp_blockeig_release(msdp_handle h);
+// msdp_blockjacobi.hip, msdp_blockreshape.hip
+void msdp_block_eigs_release(msdp_handle h);                  // (the workspace is shared with msdp_block_reshape)
+int msdp_block_reshape_run(msdp_handle h, int cur, int nb, const int64_t* nblk, const int32_t* p_in, const double* w, const double* V,
+                           int k, double theta, int strict, int delta, double alpha, int min_facsize, int mode, int nob,
+                           int32_t* p_out, int32_t* r_out, int32_t* nne_out, int* p_new);
+int msdp_block_reshape_maxp();

@@ -349,8 +349,6 @@ __global__ __launch_bounds__(MSDP_BLOCK) void k_dense_costgrad_epi_obl(Dev d, in
 }
 
 // ---------------------------------------------------------------- host side
-int msdp_dev_alloc_bytes(msdp_handle h, void** out, size_t bytes);
-
 static int ensure_slab(msdp_handle h, size_t need) {
     if (h->slab_cap >= need) return 0;
     if (h->slab) {
@@ -369,10 +367,6 @@ static int ensure_slab(msdp_handle h, size_t need) {
 }
 
 int msdp_dense_ensure_slab(msdp_handle h, size_t need) { return ensure_slab(h, need); }
-int msdp_densesym_eligible(msdp_handle h, int nmat);                   // msdp_densesym.hip
-int msdp_densesym_reserve(msdp_handle h, int nmat, size_t* slabs_out);
-int msdp_densesym_gemm(msdp_handle h, hipStream_t stream, int nmat, const double* const* M, const double* const* X,
-                       const double* scale, const int* active_flag);
 
 int msdp_dense_nS(int n) { return ((n + 15) / 16) * 16; }
 
@@ -493,9 +487,6 @@ int msdp_dense_gemm_slabs(msdp_handle h, int nmat) {
     dense_plan(h, nmat, &row_blocks, &SK, &kslice);
     return SK;
 }
-int msdp_dense_gemm_at(msdp_handle h, hipStream_t stream, int slab_first, int slabs_reserve, int nmat, const double* const* M,
-                       const double* const* X, const double* scale, const int* active_flag, const double** slab_out,
-                       int64_t* stride_out, int* SK_out);
 int msdp_dense_gemm(msdp_handle h, int nmat, const double* const* M, const double* const* X, const double* scale,
                     const int* active_flag, const double** slab_out, int64_t* stride_out, int* SK_out) {
     return msdp_dense_gemm_at(h, h->stream, 0, 0, nmat, M, X, scale, active_flag, slab_out, stride_out, SK_out);

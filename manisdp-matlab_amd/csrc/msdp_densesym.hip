@@ -23,10 +23,6 @@
 
 typedef double sym_d4 __attribute__((ext_vector_type(4)));
 
-int msdp_dev_alloc_bytes(msdp_handle h, void** out, size_t bytes);
-int msdp_dense_ensure_slab(msdp_handle h, size_t need);       // msdp_dense.hip
-int msdp_dense_nS(int n);
-
 struct SymItem { int m, rb, k0, k1, dslot, pad0, pad1, pad2; };
 
 struct SymOp {

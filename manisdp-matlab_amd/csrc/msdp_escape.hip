@@ -25,26 +25,6 @@
 #include <cstring>
 #include <vector>
 
-int msdp_dense_nS(int n);
-void* msdp_uc_alloc(size_t bytes);                                           // msdp_api.hip: per-process pool of uncached blocks
-void msdp_uc_release_pool();
-void msdp_host_kits_release();
-int msdp_allgather_rows(msdp_handle h, const double* local_rows);          // msdp_api.hip
-int msdp_allgather_vec(msdp_handle h, const double* local, double* all, size_t count_per_rank);
-// msdp_lanczos.hip: persistent kernel for the recurrence (sparse C, single rank)
-size_t msdp_lanczos_slot_bytes();
-int msdp_lanczos_persist_ok(msdp_handle h, int nq, const int* full_csr);
-int msdp_lanczos_persist_run(msdp_handle h, const double* z, const double* Q, int nq, double* V, double* X, double* dalpha,
-                             double* dbeta, unsigned long long* slots, int* err, int m0, int m1,
-                             const int* rp, const int* ci, const double* cv);
-
-// msdp_blockeig.hip: Chebyshev-filtered subspace iteration on a b-wide panel (sparse C)
-int msdp_blockeig_eligible(msdp_handle h, const double* Mdev, bool w_loc);
-int msdp_blockeig_run(msdp_handle h, int n, const int* rp, const int* ci, const double* cv, const double* z, bool own_rows,
-                      const double* Ypt, int ld, int p, int k, double tol, int maxdeg, double lmax, double lmax_res, double lmin_est,
-                      bool cold, bool use_y, double* lam, double* V_dev, int* degree_out, bool* conv_out, double* err_out,
-                      double* lower_out, const double* Mdense);
-
 // ---------------------------------------------------------------- kernels
 // w = S*v for S = C - diag(z), sparse C (one thread per row; rows are short)
 __global__ void k_sv_sparse(int n, const int* __restrict__ rp, const int* __restrict__ ci, const double* __restrict__ cv,
@@ -794,7 +774,7 @@ void msdp_escape_workspace_park(double* ptr, size_t cap_doubles) {
 extern "C" int msdp_release_cache(void) {
     msdp_uc_release_pool();
     msdp_xfer_release();                                      // the pinned staging buffer of msdp_xfer.hip
-    msdp_host_kits_release();                                 // cached streams + pinned control blocks (msdp_api.hip)
+    msdp_host_kits_release();                                 // cached streams + pinned control blocks (msdp_mem.hip)
     std::lock_guard<std::mutex> lock(g_ws_mutex);
     if (g_ws_ptr) (void)hipFree(g_ws_ptr);
     g_ws_ptr = nullptr; g_ws_cap = 0; g_ws_dev = -1;
@@ -932,7 +912,7 @@ static int escape_impl_once(msdp_handle h, int k, double tol, int maxit, double*
     // the slots proper live in uncached device memory (sc1 accesses skip the L2 look-up: -0.75 us per grid reduction,
     // tools/microbench_sync.hip); the workspace copy above is the fallback
     if (!h->lz_slots) {
-        h->lz_slots = (unsigned long long*)msdp_uc_alloc(msdp_lanczos_slot_bytes());       // per-process pool (msdp_api.hip)
+        h->lz_slots = (unsigned long long*)msdp_uc_alloc(msdp_lanczos_slot_bytes());       // per-process pool (msdp_mem.hip)
     }
     if (h->lz_slots) c.slots = h->lz_slots;
     c.err = reinterpret_cast<int*>(reinterpret_cast<unsigned long long*>(c.X + 4 * (size_t)n) + slot_doubles);   // always in the workspace

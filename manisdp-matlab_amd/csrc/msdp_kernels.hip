@@ -620,15 +620,6 @@ static inline void lpr_rebalance(msdp_handle h, int& lpr, int& nch) {
         }                                                                                            \
     } while (0)
 
-int msdp_window_eligible(msdp_handle h);            // msdp_window.hip
-int msdp_window_hess(msdp_handle h);
-int msdp_dense_costgrad(msdp_handle h, int slot);   // msdp_dense.hip
-int msdp_dense_hess(msdp_handle h);
-int msdp_affine_costgrad(msdp_handle h, int slot);  // msdp_affine.hip
-int msdp_affine_hess(msdp_handle h);
-int msdp_sphere_upd2(msdp_handle h);
-int msdp_sphere_retract(msdp_handle h);
-
 int msdp_launch_costgrad(msdp_handle h, int slot) {
     // gather source: all rows of Y[slot] (slot >= 2: resolved on the device, single rank, sparse C only)
     int rc = 0;
@@ -811,5 +802,3 @@ int msdp_k_sum_to(msdp_handle h, int which, double* out) {
     HIPCHK(hipGetLastError());
     return 0;
 }
-
-int msdp_k_sum_to_fwd(msdp_handle h, int which, double* out) { return msdp_k_sum_to(h, which, out); }

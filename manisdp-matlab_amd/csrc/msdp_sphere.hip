@@ -8,8 +8,6 @@
 #include "msdp_device.h"
 #include <math.h>
 
-void msdp_frame_store_fwd();
-
 __device__ __forceinline__ void sph_frame_store(Frame* o, double z_r, double d_Pd, double e_Pd, double e_Pe,
                                                 double model_value, double norm_r0, double alpha, double beta,
                                                 int active, int j, int stop, int eta_idx) {

@@ -240,7 +240,6 @@ static int tail_lpr(const Dev& d) {
 }
 
 // Same grid as the persistent tCG kernel (one workgroup per CU, all co-resident); LDS = one proposal row set.
-int msdp_tr_tail_grid(msdp_handle h);           // msdp_persist.hip (persist_grid)
 int msdp_launch_tr_tail(msdp_handle h) {
     const int G = msdp_tr_tail_grid(h);
     const int lpr = tail_lpr(h->d);

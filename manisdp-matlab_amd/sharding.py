@@ -5,7 +5,7 @@ The n points (rows of the n x p factor = MATLAB columns of the p x n Y) are spli
 direction can be exchanged with ONE uniform all-gather (every rank contributes ``cap * p``
 doubles; the last block is zero-padded).  Rank r owns rows ``[r*cap, min(n, (r+1)*cap))`` of
 Y, U, H, eG and the same rows of C.  This file is the host-side statement of that layout; the
-library applies the identical partition in ``msdp_comm_init`` (csrc/msdp_api.hip).
+library applies the identical partition in ``msdp_comm_init`` (csrc/msdp_comm.hip).
 """
 from __future__ import annotations
 
@@ -50,7 +50,7 @@ def unpad_gathered(slabs, n):
 
 def halo_lists(C, nranks, rank):
     """Send / receive lists of the halo exchange for sparse C (option ``halo_exchange``; the host-side statement of
-    ``halo_setup`` in csrc/msdp_api.hip).  Every rank holds the whole sparsity structure, so both ends of a pair compute
+    ``halo_setup`` in csrc/msdp_comm.hip).  Every rank holds the whole sparsity structure, so both ends of a pair compute
     the same lists: ``need[q]`` = the sorted global rows outside q's range that q's rows of C reference.
 
     Returns ``(send, recv)``: ``send[q]`` = local row indices this rank packs for peer q (in the order q unpacks them),

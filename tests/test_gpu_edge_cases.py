@@ -421,7 +421,7 @@ def test_wide_factors_up_to_1024(p):
 def test_handle_churn_keeps_results_and_pool_bounded(lib):
     """VERDICT round 3, item 8.  The words that workgroups exchange inside a launch (grid-sync slots, direction rows) live in
     uncached device memory; round 3 found that uncached blocks allocated and hipFree'd per handle corrupt LATER handles of the
-    process.  The fence: uncached memory comes from per-process arenas with a coalescing sub-allocator (msdp_api.hip) that
+    process.  The fence: uncached memory comes from per-process arenas with a coalescing sub-allocator (msdp_mem.hip) that
     never hand pages back to the driver while any block of them is live.  Here 200 handles of mixed kinds and sizes are created
     and destroyed with overlapping lifetimes; every one must reproduce the oracle's cost, eG / z and gradient and a short
     trustregions() call through the persistent kernels (the users of the uncached blocks), the pool must stay below

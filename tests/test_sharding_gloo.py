@@ -212,7 +212,7 @@ def _halo_matrix(kind):
 
 @pytest.mark.parametrize("kind,world", [("grid", 2), ("grid", 3), ("random", 3)])
 def test_halo_exchange_protocol(tmp_path, kind, world):
-    """sharding.halo_lists (the host-side statement of halo_setup in msdp_api.hip): the lists of the two ends of every pair
+    """sharding.halo_lists (the host-side statement of halo_setup in msdp_comm.hip): the lists of the two ends of every pair
     agree, the exchanged rows are exactly the referenced ones, and the local products equal the rows of C*U; on the grid a
     rank receives two grid rows from each neighbour, not the whole direction."""
     out = str(tmp_path / "halo.npy")

@@ -301,7 +301,15 @@ int msdp_linesearch_accept(msdp_handle h);
  * ManiSDP_unitdiag.m:68, ManiSDP_unittrace.m:68 for large n): the k smallest
  * eigenpairs and the largest eigenvalue of the dual slack S at the resident point,
  * by block Lanczos / LOBPCG on the device re-using the S*U kernel.
- * lam_min[k] ascending, V is n x k column-major, *lam_max the top eigenvalue. */
+ * lam_min[k] ascending, V is n x k column-major, *lam_max the top eigenvalue.
+ * The Lanczos path returns the negative eigenvalues it finds (at most k) and at most
+ * one non-negative one, which is an upper estimate that only certifies its sign.  Further
+ * copies of a multiple eigenvalue come from the deflated re-runs alone, and pairs taken
+ * from one Krylov space may come before them: the k values need not be the k smallest
+ * counted with multiplicity.  The sequential deflation ends when the
+ * complement of what was found is non-negative or empty (n <= k, or every eigenvalue
+ * negative and none left).  Values that do not exist are +inf with a zero vector, and
+ * msdp_escape_info reports how many are real: never more than n. */
 int msdp_escape_eigs(msdp_handle h, int32_t k, double tol, int32_t maxit,
                      double* lam_min, double* V, double* lam_max, int32_t* iters);
 

@@ -252,6 +252,17 @@ static void tri_eigvec(const std::vector<double>& a, const std::vector<double>& 
     }
 }
 
+// Order of the leading unreduced block of T_m (diagonal a[0..m-1], couplings b[1..m]): the smallest i in [1, m] with
+// b[i] <= 1e-14 * |T|, else m.  After a breakdown the step kernels go on -- with a zero vector when the remainder is exactly
+// zero (alpha = beta = 0 from there on), with normalised rounding noise otherwise -- and what follows the first vanished
+// coupling is no Krylov space of the start vector: zeros on the diagonal are no Ritz values of S.
+static int leading_block(const std::vector<double>& a, const std::vector<double>& b, int m) {
+    double tscale = 0.0;
+    for (int i = 0; i < m; ++i) tscale = std::max(tscale, std::max(fabs(a[i]), fabs(b[i + 1])));
+    for (int i = 1; i < m; ++i) if (b[i] <= 1e-14 * tscale) return i;
+    return m;
+}
+
 // ---- device-side Lanczos step kernels (scalars stay on the device; the host syncs only at checkpoints)
 __global__ __launch_bounds__(MSDP_BLOCK) void k_dot1(int n, const double* __restrict__ x, const double* __restrict__ y,
                                                     double* __restrict__ out, int take_sqrt) {
@@ -526,6 +537,9 @@ static int lanczos_top(EscCtx& c, double* V, double* w, double* dalpha, double* 
             HIPCHK(msdp_memcpy(&perr, c.err, sizeof(int), hipMemcpyDeviceToHost));
             if (perr) { msdp_set_error("persistent Lanczos: grid synchronisation timed out"); return MSDP_EHIP; }
         }
+        const int mb = leading_block(a, b, m);
+        const bool cut = mb < m;                         // broke down before this checkpoint: the leading block is exact
+        if (cut) { m = mb; a.resize(m); b.resize(m + 1); }
         off.assign(m, 0.0);
         for (int i = 0; i + 1 < m; ++i) off[i] = b[i + 1];
         double glo = 1e300, ghi = -1e300;
@@ -538,7 +552,7 @@ static int lanczos_top(EscCtx& c, double* V, double* w, double* dalpha, double* 
         tri_eigvec(a, off, m, lmax, s);
         res = fabs(b[m] * s[m - 1]);
         const double scale = std::max(fabs(lmax), fabs(lmin)) + 1e-300;
-        if (res <= tol * scale || b[m] <= 1e-14 * scale) break;
+        if (cut || res <= tol * scale || b[m] <= 1e-14 * scale) break;
         next_check = std::min(maxit, 2 * m);
     }
     // top Ritz vector (warm start of the next call)
@@ -591,12 +605,24 @@ static int lanczos_smallest(EscCtx& c, const double* Q, int nq, double* V /* max
         else
             hipLaunchKernelGGL(k_fill_hash, gr, bl, 0, h->stream, n, seed, w);
         if ((rc = deflate(c, Q, nq, w, 2))) return rc;
+        if (nq > 0) {
+            // Q spans everything the start vector has (the complement is exhausted): no run, nothing for the caller to append
+            double nw = 0.0;
+            if ((rc = dev_norm(c, w, &nw))) return rc;
+            if (!(nw > 1e-10)) {
+                if (nacc_out) *nacc_out = 0;
+                if (conv_out) *conv_out = true;
+                *theta_out = INFINITY; *res_out = 0.0; *lmax_out = -1e300; *m_out = 0;
+                return 0;
+            }
+        }
     }
     hipLaunchKernelGGL(k_dot1, dim3(1), dim3(MSDP_BLOCK), 0, h->stream, n, w, w, dbeta, 1);
     hipLaunchKernelGGL(k_normalize_to, gr, bl, 0, h->stream, n, w, dbeta, V);
     HIPCHK(hipGetLastError());
     std::vector<double> a, b, s;
-    int m = 0, next_check = 32;
+    // the complement of Q has dimension n - nq: the recurrence ends there at the latest, and the first look at T_m is due
+    int m = 0, next_check = std::max(1, std::min(32, n - nq));
     double theta = 0.0, res = 1e300, lmax = 0.0;
     bool converged = false;          // one of the three stop tests passed (else the run ended at maxit: theta is only an upper bound)
     const LzMode md = lanczos_mode(c, nq);
@@ -615,6 +641,14 @@ static int lanczos_smallest(EscCtx& c, const double* Q, int nq, double* V /* max
             }
             const auto t_an0 = std::chrono::steady_clock::now();
             struct AnTimer { std::chrono::steady_clock::time_point t0; double* acc; ~AnTimer() { *acc += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); } } an_timer{t_an0, &c.host_analysis_s};
+            // broke down before this checkpoint: the leading block holds the whole Krylov space of the start vector, its Ritz
+            // pairs are exact eigenpairs, and m is what the assembly below may use.  theta is the minimum over THAT space: the
+            // minimum of the complement for a hashed start vector (a component along every eigenvector), not necessarily for
+            // a warm start that lies in an invariant subspace (the sum of the vectors a previous call found, S unchanged) --
+            // no lower estimate is reported for warm calls (esc_lower below)
+            const int mb = leading_block(a, b, m);
+            const bool cut = mb < m;
+            if (cut) { m = mb; a.resize(m); b.resize(m + 1); }
             // T_m: diagonal a[0..m-1], couplings b[1..m-1]; b[m] closes the residual
             std::vector<double> off(m);
             for (int i = 0; i + 1 < m; ++i) off[i] = b[i + 1];
@@ -632,7 +666,7 @@ static int lanczos_smallest(EscCtx& c, const double* Q, int nq, double* V /* max
             tri_eigvec(a, off, m, theta, s);
             res = fabs(b[m] * s[m - 1]);
             const double scale = std::max(fabs(theta), fabs(lmax)) + 1e-300;
-            const bool breakdown = b[m] <= 1e-14 * scale;
+            const bool breakdown = cut || b[m] <= 1e-14 * scale;
             if (res <= tol * scale || theta - res > -tol * scale || breakdown) {
                 if (m > 1024) lmax = tri_eig_kth(a, off, m, m - 1, glo, ghi);
                 converged = true;
@@ -1007,8 +1041,12 @@ static int escape_impl_once(msdp_handle h, int k, double tol, int maxit, double*
             double thetas[64];
             double* x = Q + (size_t)r * n;
             bool conv = false;
+            // every eigenvalue found so far was negative and Q already spans the space (n <= k, or a negative definite S of
+            // order below p + k): the complement is empty, which is as good as non-negative
+            if (r >= n) { complement_nonneg = h->esc_converged != 0; last_theta = INFINITY; last_res = 0.0; break; }
             ESC_CHECK(lanczos_smallest(c, Q, r, V, w, dalpha, dbeta, maxit, tol, 12345u + 7919u * t, &theta, &res, &lmx, x, &m,
                                        std::min(k - t, 64), &nacc, thetas, Z, &have_xstart, &conv));
+            if (nacc == 0) { complement_nonneg = h->esc_converged != 0; last_theta = INFINITY; last_res = 0.0; break; }   // same, found numerically
             total_steps += m;
             if (!conv) {
                 h->esc_converged = 0;

@@ -130,6 +130,15 @@ int msdp_debug_get_tcg_step(msdp_handle h, double* eta, double* Heta);
  * row-major, column j = coefficients of Ritz vector j, W'GW = I on the first *rank columns) of the block eigen-solver. */
 int msdp_debug_sym_eig(int32_t n, const double* A, double* w, double* Z);
 int msdp_debug_ritz(int32_t b, const double* G, const double* H, double* theta, double* W, int32_t* rank);
+/* Test-only GPU twin of msdp_debug_ritz: uploads G and H and runs the kernel of the device Rayleigh-Ritz stage (option
+ * "escape_rr" = 1; k_be_ritz, msdp_beritz.hip) alone on the current device -- no handle, no fallback to the host stage.  b = 32
+ * or 64 (else MSDP_EUNSUPPORTED: the three b x b matrices of a 128-wide panel do not fit the LDS).  *status: 0 = ok (theta
+ * ascending, W'GW = I, *rank = b), 1 = the kernel asks for the host stage (dependent columns: a Cholesky pivot <= 1e-11 max diag G;
+ * or Jacobi not converged in 40 sweeps), 2 = breakdown (non-finite entry, max diag G <= 0); theta, W and *rank are zero then. */
+int msdp_debug_ritz_device(int32_t b, const double* G, const double* H, double* theta, double* W, int32_t* rank, int32_t* status);
+/* Rayleigh-Ritz stages of the block eigen-solver since the handle was created, by where their dense algebra ran: on the
+ * device, on the host, and on the host after the device kernel handed the stage back (status 1 or 2 above). */
+int msdp_debug_ritz_stages(msdp_handle h, int64_t* device, int64_t* host, int64_t* fallback);
 /* Test-only: make a sparse-C handle rank `rank` of `nranks` WITHOUT a communicator (same row split, local CSR/ELL
  * rows with global column indices and gather buffer as msdp_comm_init sets up), so that one GPU can check every
  * shard's kernels against the unsharded result.  Call right after create, before any point is set. */
@@ -504,6 +513,12 @@ int msdp_block_reshape(msdp_handle h, int32_t nb, const int64_t* row0, const int
  *                       2 = always (tests); 0 = never
  *   "escape_method" 0 = block eigen-solver where it applies (sparse C, n >= 512), Lanczos otherwise (default); 1 = Lanczos
  *                       always; 2 = block also for small n (tests)
+ *   "escape_rr"    0/1  block eigen-solver, dense algebra of a Rayleigh-Ritz stage (b x b problem H c = theta G c, residual
+ *                       sums): 0 = on the host (default: Cholesky + tred2 / tql2 on one thread between two copies and two
+ *                       synchronisations), 1 = on the device for panels of 32 / 64 columns (one workgroup, Cholesky + cyclic
+ *                       Jacobi in LDS; the stage reads one record of 2b + 2 doubles behind one synchronisation).  128-wide
+ *                       panels keep the host stage, and so does a stage whose kernel reports dependent columns or a breakdown
+ *                       (msdp_debug_ritz_stages counts them).  Any other value: MSDP_EINVAL
  *   "be_width" 0/32/64/128, "be_degree", "be_grid", "be_lpr"  block eigen-solver: panel width, filter degree per round,
  *                       workgroups and lanes per row of the filter step (0 = automatic; measurement and tests)
  *   "escape_start_y" 1/0  undeflated cold-start escape runs start from a random combination of the columns of Y plus 5 %

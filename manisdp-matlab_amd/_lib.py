@@ -95,6 +95,8 @@ SIGNATURES = {
     "msdp_debug_get_tcg_step": (C.c_int, [C.c_void_p, _dp, _dp]),
     "msdp_debug_sym_eig": (C.c_int, [C.c_int32, _dp, _dp, _dp]),
     "msdp_debug_ritz": (C.c_int, [C.c_int32, _dp, _dp, _dp, _dp, _P(C.c_int32)]),
+    "msdp_debug_ritz_device": (C.c_int, [C.c_int32, _dp, _dp, _dp, _dp, _P(C.c_int32), _P(C.c_int32)]),
+    "msdp_debug_ritz_stages": (C.c_int, [C.c_void_p, _P(C.c_int64), _P(C.c_int64), _P(C.c_int64)]),
     "msdp_get_dual_slack": (C.c_int, [C.c_void_p, _dp]),
     "msdp_get_dual_slack_block": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _dp]),
     "msdp_block_eigs": (C.c_int, [C.c_void_p, C.c_int32, _i64p, _i64p, C.c_int32, C.c_int32, _dp, _dp]),
@@ -203,6 +205,21 @@ def device_count():
     n = C.c_int32()
     _check(load().msdp_device_count(C.byref(n)))
     return n.value
+
+
+def ritz_device(G, H):
+    """The kernel of the device Rayleigh-Ritz stage alone (msdp_debug_ritz_device; b = 32 or 64): H c = theta G c for the b x b
+    matrices G, H.  Returns (theta, W, rank, status): status 0 = ok (theta ascending, W'GW = I, rank = b), 1 = the kernel asks
+    for the host stage (dependent columns or Jacobi not converged), 2 = breakdown; theta and W are zero unless status is 0."""
+    G = np.ascontiguousarray(G, dtype=np.float64)
+    H = np.ascontiguousarray(H, dtype=np.float64)
+    b = G.shape[0]
+    if G.shape != (b, b) or H.shape != (b, b):
+        raise ValueError("ritz_device: G and H must be square and of the same order")
+    theta, W = np.zeros(b), np.zeros((b, b))
+    rank, status = C.c_int32(), C.c_int32()
+    _check(load().msdp_debug_ritz_device(b, _dptr(G), _dptr(H), _dptr(theta), _dptr(W), C.byref(rank), C.byref(status)))
+    return theta, W, rank.value, status.value
 
 
 def default_opts(**kw):
@@ -585,6 +602,13 @@ class Handle:
         v = C.c_int32()
         _check(self._lib.msdp_escape_method(self._h, C.byref(v)))
         return v.value
+
+    def ritz_stages(self):
+        """(device, host, fallback): Rayleigh-Ritz stages of the block eigen-solver on this handle so far whose dense algebra ran
+        on the device (option escape_rr = 1), on the host, and on the host after the device kernel handed the stage back."""
+        d, hst, f = C.c_int64(), C.c_int64(), C.c_int64()
+        _check(self._lib.msdp_debug_ritz_stages(self._h, C.byref(d), C.byref(hst), C.byref(f)))
+        return int(d.value), int(hst.value), int(f.value)
 
     def escape_lower_bound(self):
         """Lower estimate of lambda_min(S) from the last escape call; -inf unless that call was cold-started and

@@ -902,6 +902,7 @@ extern "C" int msdp_set_option(msdp_handle h, const char* name, int32_t value) {
     else if (!strcmp(name, "sweep")) { t.sweep = value < 0 ? 0 : (value > 3 ? 3 : value); choose_grid(h); h->chunk_len = 0; }
     else if (!strcmp(name, "trip2")) { t.trip2 = value < 0 ? 0 : (value > 2 ? 2 : value); h->chunk_len = 0; }
     else if (!strcmp(name, "escape_method")) { if (value < 0 || value > 2) { msdp_set_error("escape_method: 0 auto, 1 lanczos, 2 block"); return MSDP_EINVAL; } t.escape_method = value; }
+    else if (!strcmp(name, "escape_rr")) { if (value != 0 && value != 1) { msdp_set_error("escape_rr: 0 host, 1 device"); return MSDP_EINVAL; } t.escape_rr = value; }
     else if (!strcmp(name, "be_width")) { if (value != 0 && value != 32 && value != 64 && value != 128) { msdp_set_error("be_width: 0, 32, 64 or 128"); return MSDP_EINVAL; } t.be_width = value; }
     else if (!strcmp(name, "be_degree")) t.be_degree = value > 0 ? value : 0;
     else if (!strcmp(name, "be_grid")) t.be_grid = value > 0 ? (value > MSDP_MAX_GRID ? MSDP_MAX_GRID : value) : 0;

@@ -12,7 +12,10 @@
 //     (a, b_up, a0, step) only and are computed by the host ahead of the launches;
 //   * Rayleigh-Ritz every d steps: G = X'X and H = X'SX (two b x b Gram matrices, deterministic two-stage reduction),
 //     the b x b generalised eigenproblem on the host (Cholesky + Householder/QL), X <- X W and SX <- SX W on the device,
-//     residual norms |S x_i - theta_i x_i| from the same pass;
+//     residual norms |S x_i - theta_i x_i| from the same pass; with option escape_rr = 1 and b = 32 / 64 the eigenproblem
+//     (k_be_ritz, msdp_beritz.hip) and the residual sums (k_be_res_sum) stay on the device and the stage reads one record of
+//     2b + 2 doubles behind one synchronisation -- b = 128 keeps the host stage (its three matrices do not fit the LDS), and so
+//     does a stage whose kernel reports dependent columns or a breakdown;
 //   * the lower edge a of the damped interval follows the largest Ritz value of the block (Zhou & Saad), so the filter
 //     sharpens round by round; convergence of the wanted pairs is governed by the gap to the eigenvalues OUTSIDE the
 //     block (lambda_{b+1} - lambda_i), not by the gaps inside the cluster.
@@ -249,6 +252,15 @@ __global__ __launch_bounds__(256) void k_be_rotate(int n, const double* __restri
     }
 }
 
+// res[j] = sqrt(max(sum of the nblk partials of column j, 0)), the partials added in index order (the order of the host loop)
+__global__ void k_be_res_sum(int b, int nblk, const double* __restrict__ rpart, double* __restrict__ res) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= b) return;
+    double s = 0.0;
+    for (int q = 0; q < nblk; ++q) s += rpart[(int64_t)q * b + j];
+    res[j] = sqrt(s > 0.0 ? s : 0.0);
+}
+
 __device__ __forceinline__ double be_hash(unsigned row, unsigned col, unsigned seed) {
     unsigned x = row * 2654435761u ^ (col + 1u) * 2246822519u ^ seed;
     x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
@@ -481,6 +493,8 @@ struct BeMem {                                          // device workspace of o
     double* hpin = nullptr; size_t hpin_cap = 0;        // pinned host staging (Gram matrices, residual partials, W, theta)
     double* prevV = nullptr; int prev_n = 0, prev_k = 0;   // bottom vectors of the previous call (n x prev_k column-major), own allocation
     double prev_a = 0.0;                                // lower filter edge the previous call ended with
+    int64_t rr_device = 0, rr_host = 0, rr_fallback = 0;   // Rayleigh-Ritz stages since the handle was created, by where their algebra
+                                                        //   ran: device (k_be_ritz), host, host after the device kernel handed the stage back
 };
 
 void msdp_blockeig_release(msdp_handle h) {
@@ -550,6 +564,16 @@ struct BeRR {                                           // outcome of one Raylei
     int rank = 0;
 };
 
+// Xn = X*W and the residual partials; theta sits right behind W on the device (Wd + b*b)
+static int be_rotate(msdp_handle h, int b, int n, const double* X, const double* SX, const double* Wd, double* Xn, double* rpart) {
+    const size_t lds = ((size_t)b * b + (size_t)(256 / (b / 4)) * b) * sizeof(double);
+    if (b == 32) hipLaunchKernelGGL((k_be_rotate<32>), dim3(BE_ROT_BLOCKS), dim3(256), lds, h->stream, n, X, SX, Wd, Wd + (size_t)b * b, Xn, rpart);
+    else if (b == 64) hipLaunchKernelGGL((k_be_rotate<64>), dim3(BE_ROT_BLOCKS), dim3(256), lds, h->stream, n, X, SX, Wd, Wd + (size_t)b * b, Xn, rpart);
+    else hipLaunchKernelGGL((k_be_rotate<128>), dim3(BE_ROT_BLOCKS), dim3(256), lds, h->stream, n, X, SX, Wd, Wd + (size_t)b * b, Xn, rpart);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // Rayleigh-Ritz on the panel X (SX = scratch, receives S*X; Xn receives the Ritz vectors, columns >= rank refilled with
 // noise).  X, SX and Xn are three different panels.
 static int be_rayleigh_ritz(msdp_handle h, const BeOp& a, BeMem& m, const double* X, double* SX, double* Xn,
@@ -564,6 +588,27 @@ static int be_rayleigh_ritz(msdp_handle h, const BeOp& a, BeMem& m, const double
     hipLaunchKernelGGL(k_be_gram_sum, dim3((2 * b * b + 255) / 256), dim3(256), 0, h->stream, 2 * b * b, BE_GRAM_BLOCKS, (const double*)gpart, gout);
     HIPCHK(hipGetLastError());
     double* hp = m.hpin;
+    if (h->tune.escape_rr == 1 && msdp_beritz_supported(b)) {
+        // The whole stage enqueued back to back; ONE copy (theta[b], res[b], rank, status) and ONE synchronisation.  k_be_rotate
+        // writes Xn and rpart only, never X or SX, and k_be_ritz leaves gout as it found it: a stage the kernel hands back
+        // (dependent columns, Jacobi not converged, breakdown) is redone by the host stage below from the same Gram matrices --
+        // eigen-basis route, noise refill and the breakdown message included -- as if the device had not been tried.
+        double* rec = rpart + (size_t)BE_ROT_BLOCKS * b;
+        if ((rc = msdp_beritz_launch(h->stream, b, gout, Wd, rec))) return rc;
+        if ((rc = be_rotate(h, b, n, X, SX, Wd, Xn, rpart))) return rc;
+        hipLaunchKernelGGL(k_be_res_sum, dim3(1), dim3(64), 0, h->stream, b, BE_ROT_BLOCKS, (const double*)rpart, rec + b);
+        HIPCHK(hipGetLastError());
+        HIPCHK(msdp_memcpy_async(hp, rec, ((size_t)2 * b + 2) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if ((int)hp[2 * b + 1] == MSDP_RITZ_OK) {
+            out.theta.assign(hp, hp + b);
+            out.res.assign(hp + b, hp + 2 * b);
+            out.rank = (int)hp[2 * b];
+            ++m.rr_device;
+            return 0;
+        }
+        ++m.rr_fallback;
+    } else ++m.rr_host;
     HIPCHK(msdp_memcpy_async(hp, gout, (size_t)2 * b * b * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     const auto t0 = std::chrono::steady_clock::now();
@@ -576,12 +621,7 @@ static int be_rayleigh_ritz(msdp_handle h, const BeOp& a, BeMem& m, const double
     memcpy(hw, W.data(), (size_t)b * b * sizeof(double));
     for (int j = 0; j < b; ++j) hw[(size_t)b * b + j] = j < r ? out.theta[j] : 0.0;
     HIPCHK(msdp_memcpy_async(Wd, hw, ((size_t)b * b + b) * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    // theta sits right behind W on the device (Wd + b*b)
-    const size_t lds = ((size_t)b * b + (size_t)(256 / (b / 4)) * b) * sizeof(double);
-    if (b == 32) hipLaunchKernelGGL((k_be_rotate<32>), dim3(BE_ROT_BLOCKS), dim3(256), lds, h->stream, n, X, (const double*)SX, (const double*)Wd, (const double*)(Wd + (size_t)b * b), Xn, rpart);
-    else if (b == 64) hipLaunchKernelGGL((k_be_rotate<64>), dim3(BE_ROT_BLOCKS), dim3(256), lds, h->stream, n, X, (const double*)SX, (const double*)Wd, (const double*)(Wd + (size_t)b * b), Xn, rpart);
-    else hipLaunchKernelGGL((k_be_rotate<128>), dim3(BE_ROT_BLOCKS), dim3(256), lds, h->stream, n, X, (const double*)SX, (const double*)Wd, (const double*)(Wd + (size_t)b * b), Xn, rpart);
-    HIPCHK(hipGetLastError());
+    if ((rc = be_rotate(h, b, n, X, SX, Wd, Xn, rpart))) return rc;
     if (r < b) {
         hipLaunchKernelGGL(k_be_init, dim3(1024), dim3(256), 0, h->stream, n, b, (const double*)nullptr, 0, 0, (const double*)nullptr, 0, seed, r, Xn);
         HIPCHK(hipGetLastError());
@@ -651,9 +691,9 @@ int msdp_blockeig_run(msdp_handle h, int n, const int* rp, const int* ci, const 
     if (k > 64) { msdp_set_error("block eigen-solver: at most 64 eigenpairs per call"); return MSDP_EINVAL; }
     if (ny > b - 8 - std::min(nprev, 8)) ny = b - 8 - std::min(nprev, 8);     // leave room for noise columns (and some warm ones)
     if (ny + nprev > b - 8) nprev = b - 8 - ny;
-    // ---- workspace: three panels, Gram partials, Gram sums, [W | theta], residual partials
+    // ---- workspace: three panels, Gram partials, Gram sums, [W | theta], residual partials, the result record of the device stage
     const size_t panel = (size_t)n * b;
-    const size_t need = 3 * panel + (size_t)BE_GRAM_BLOCKS * 2 * b * b + (size_t)2 * b * b + (size_t)b * b + b + (size_t)BE_ROT_BLOCKS * b + 64;
+    const size_t need = 3 * panel + (size_t)BE_GRAM_BLOCKS * 2 * b * b + (size_t)2 * b * b + (size_t)b * b + b + (size_t)BE_ROT_BLOCKS * b + 2 * b + 2 + 64;
     if (m.cap < need) {
         (void)hipStreamSynchronize(h->stream);
         if (m.base) (void)hipFree(m.base);
@@ -827,9 +867,9 @@ int msdp_blockeig_run(msdp_handle h, int n, const int* rp, const int* ci, const 
     if (conv_out) *conv_out = converged;
     if (err_out) *err_out = worst;
     if (lower_out) *lower_out = rr.theta[0] - worst * scale_top;
-    if (dbg) fprintf(stderr, "[blockeig] b=%d ny=%d nprev=%d cold=%d: %d rounds, degree %d, %.2f ms (host algebra %.2f ms), theta0=%.9e, %s\n", b, ny, nprev,
+    if (dbg) fprintf(stderr, "[blockeig] b=%d ny=%d nprev=%d cold=%d: %d rounds, degree %d, %.2f ms (host algebra %.2f ms; Ritz stages of the handle: %lld device, %lld host, %lld host after fallback), theta0=%.9e, %s\n", b, ny, nprev,
                      (int)cold, rounds, degree, 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(), 1e3 * host_s,
-                     rr.theta[0], converged ? "converged" : "NOT converged");
+                     (long long)m.rr_device, (long long)m.rr_host, (long long)m.rr_fallback, rr.theta[0], converged ? "converged" : "NOT converged");
     return 0;
 }
 
@@ -850,5 +890,12 @@ extern "C" int msdp_debug_ritz(int32_t b, const double* G, const double* H, doub
     memcpy(theta, th.data(), (size_t)b * sizeof(double));
     memcpy(W, w.data(), (size_t)b * b * sizeof(double));
     *rank = r;
+    return 0;
+}
+extern "C" int msdp_debug_ritz_stages(msdp_handle h, int64_t* device, int64_t* host, int64_t* fallback) {
+    if (!h) { msdp_set_error("null handle"); return MSDP_EINVAL; }
+    if (!device || !host || !fallback) { msdp_set_error("debug_ritz_stages: bad argument"); return MSDP_EINVAL; }
+    const BeMem* m = (const BeMem*)h->be;
+    *device = m ? m->rr_device : 0; *host = m ? m->rr_host : 0; *fallback = m ? m->rr_fallback : 0;
     return 0;
 }

@@ -230,6 +230,9 @@ struct Tuning {
     int trip2 = 1;           // chunked path, sparse C / oblique / one rank: two launches per tCG trip (msdp_trip2.hip) instead of three
     int escape_method = 0;   // 0: block Chebyshev-filtered subspace iteration where it applies (msdp_blockeig.hip), else Lanczos;
                              //   1: Lanczos always (msdp_escape.hip); 2: block also below its size threshold (tests)
+    int escape_rr = 0;       // block eigen-solver, dense algebra of a Rayleigh-Ritz stage: 0 = on the host (be_ritz), 1 = on the device
+                             //   (k_be_ritz, msdp_beritz.hip) for panels of 32 / 64 columns; 128-wide panels and stages the kernel hands
+                             //   back (dependent columns, breakdown) run on the host either way
     int be_width = 0;        // block eigen-solver: panel width 32 / 64 / 128 (0: 64, or 128 when the start block needs it)
     int be_degree = 0;       // ... filter degree per round (0: 200 warm, 400 cold)
     int be_grid = 0;         // ... workgroups of the filter step (0: by rows)
@@ -512,6 +515,12 @@ int msdp_blockeig_run(msdp_handle h, int n, const int* rp, const int* ci, const 
                       const double* Ypt, int ld, int p, int k, double tol, int maxdeg, double lmax, double lmax_res, double lmin_est,
                       bool cold, bool use_y, double* lam, double* V_dev, int* degree_out, bool* conv_out, double* err_out, double* lower_out, const double* Mdense);
 void msdp_blockeig_release(msdp_handle h);
+// msdp_beritz.hip: H c = theta G c of a Rayleigh-Ritz stage in one workgroup; the status it leaves in its result record
+#define MSDP_RITZ_OK 0
+#define MSDP_RITZ_FALLBACK 1          // dependent columns (failed Cholesky pivot) or Jacobi not converged: the host stage decides
+#define MSDP_RITZ_BREAKDOWN 2         // non-finite entry or max diag G <= 0
+int msdp_beritz_supported(int b);
+int msdp_beritz_launch(hipStream_t stream, int b, const double* gout, double* Wd, double* rec);
 // msdp_blockjacobi.hip, msdp_blockreshape.hip
 void msdp_block_eigs_release(msdp_handle h);                  // (the workspace is shared with msdp_block_reshape)
 int msdp_block_reshape_run(msdp_handle h, int cur, int nb, const int64_t* nblk, const int32_t* p_in, const double* w, const double* V,

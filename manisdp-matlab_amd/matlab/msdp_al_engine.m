@@ -19,7 +19,8 @@ function [X, obj, data] = msdp_al_engine(kind, prob, options, defaults)
 %                                                on the GPU between two trustregions() calls
 %   Option names, defaults, the printed protocol and the fields of DATA are the reference's (README.md:19-111 of
 %   the reference; SURVEY.md appendix A).  Extra optional fields: options.Y0 (start point, any kind),
-%   options.eig_tol / options.eig_maxit (Lanczos controls), options.dense_output (return dense X and S; default
+%   options.eig_tol / options.eig_maxit (Lanczos controls), options.escape_rr ('host' | 'device': Rayleigh-Ritz stages of the
+%   block eigen-solver), options.dense_output (return dense X and S; default
 %   n <= 8192 -- beyond that X is returned as the factor and data.S is left empty).
 %
 %   kind      'onlyunitdiag' | 'unitdiag' | 'unittrace' | 'generic'
@@ -29,6 +30,15 @@ function [X, obj, data] = msdp_al_engine(kind, prob, options, defaults)
 opt = options;
 for q = 1:size(defaults, 1)
     if ~isfield(opt, defaults{q, 1}), opt.(defaults{q, 1}) = defaults{q, 2}; end
+end
+% options.escape_rr: 'host' (default) | 'device' -- where the dense algebra of the block eigen-solver's Rayleigh-Ritz stages runs
+% (msdp_set_option "escape_rr"); a bad value is refused before the handle is built
+escape_rr = 0;
+if isfield(opt, 'escape_rr')
+    if ~(ischar(opt.escape_rr) && any(strcmp(opt.escape_rr, {'host', 'device'})))
+        error('manisdp:option', 'options.escape_rr must be ''host'' or ''device''');
+    end
+    escape_rr = double(strcmp(opt.escape_rr, 'device'));
 end
 T = kind_traits(kind);
 n = prob.n;
@@ -48,6 +58,7 @@ else
     h = manisdp_mex('create_onlyunitdiag', prob.C);
 end
 release = onCleanup(@() manisdp_mex('destroy', h)); %#ok<NASGU>
+if escape_rr, manisdp_mex('set_option', h, 'escape_rr', escape_rr); end
 
 % ---- start point (the reference lets trustregions draw it with M.rand())
 p = opt.p0;

@@ -192,6 +192,16 @@ def _verify_lambda_min(h, run1, o, data, default_tol, default_maxit, dense_n=0):
     return float(lam[0]), vS[:, :1], float(lam_max), conv
 
 
+def _escape_rr_option(o):
+    """options["escape_rr"]: where the dense algebra of the block eigen-solver's Rayleigh-Ritz stages runs -- "host" (default) or
+    "device" (msdp_set_option "escape_rr" = 1: panels of 32 / 64 columns; wider panels and stages the kernel hands back stay on
+    the host).  Returns the value of the device option."""
+    rr = o.get("escape_rr", "host")
+    if rr not in ("host", "device"):
+        raise ValueError(f"options['escape_rr'] must be 'host' or 'device', not {rr!r}")
+    return 1 if rr == "device" else 0
+
+
 # =============================================================== onlyunitdiag
 def ManiSDP_onlyunitdiag(C, options=None, verbose=True, rng=None):
     with _host_threads():
@@ -207,6 +217,7 @@ def _onlyunitdiag_impl(C, options=None, verbose=True, rng=None):
     o = dict(options or {})
     for k, v in DEFAULTS["onlyunitdiag"].items():
         o.setdefault(k, v)
+    escape_rr = _escape_rr_option(o)                       # (a bad value is refused before anything is built)
     dense_max = int(o.get("dense_eig_max", 3000))          # the host eig(S) is allowed up to this order (options['eig'] = 'host') ...
     dense_default = int(o.get("dense_eig_default", 600))   # ... and the default up to this one (round 6: G1, n = 800, 0.124 s with it, 0.047 s
                                                            # with the device escape + its independent check; the affine kinds switch at 400 / 600)
@@ -243,6 +254,8 @@ def _onlyunitdiag_impl(C, options=None, verbose=True, rng=None):
             h.set_option("halo_exchange", 1)
     if "escape_method" in o:                               # 0 auto, 1 Lanczos, 2 block eigen-solver also below its size threshold
         h.set_option("escape_method", int(o["escape_method"]))
+    if escape_rr:
+        h.set_option("escape_rr", escape_rr)
     for name, value in (o.get("device_options") or {}).items():     # run-time switches of the handle (msdp_set_option): A/B runs, tests
         h.set_option(name, int(value))
     topts = _rtr_opts(o)
@@ -380,6 +393,8 @@ def _onlyunitdiag_impl(C, options=None, verbose=True, rng=None):
             lam_v, _, lmax_v, certified = _verify_lambda_min(
                 h, lambda tol, maxit: h.escape_eigs(1, tol=tol, maxit=maxit), o, data, 1e-9, 60000)
             dinf = max(0.0, -lam_v) / (1.0 + lmax_v)
+        if eig_mode == "device":
+            data["escape_rr_stages"] = h.ritz_stages()         # Rayleigh-Ritz stages: (device, host, host after fallback)
     finally:
         h.close()
     if obj is not None:
@@ -885,6 +900,7 @@ def _al_loop(h, o, t, Y, p, mult, verbose):
 # =================================================================== affine kinds
 def _affine_impl(kind, At, b, c, K, options, verbose, rng, defaults):
     o = _with_defaults(options, defaults)
+    escape_rr = _escape_rr_option(o)                       # (a bad value is refused before anything is built)
     n = int(K["s"])
     rng = rng or np.random.default_rng(0)
     b = _dense_vec(b)
@@ -907,6 +923,8 @@ def _affine_impl(kind, At, b, c, K, options, verbose, rng, defaults):
             _join_comm(h, comm)
         if "escape_method" in o:                           # 0 auto (Lanczos on the explicit S of these kinds), 1 Lanczos, 2 block eigen-solver
             h.set_option("escape_method", int(o["escape_method"]))
+        if escape_rr:
+            h.set_option("escape_rr", escape_rr)
         for name, value in (o.get("device_options") or {}).items():     # run-time switches of the handle (msdp_set_option): A/B runs, tests
             h.set_option(name, int(value))
         dev_al = eig_mode == "device" and bool(o.get("device_al", True))
@@ -943,6 +961,8 @@ def _affine_impl(kind, At, b, c, K, options, verbose, rng, defaults):
         obj, data, (Y, y, z, S, _, fac_size, _) = _al_loop(h, o, t, geo.start(rng, p), p, np.zeros(b.size), verbose)
         if S is None and obj is not None and n <= int(o.get("dense_X_max", 6000)):
             S = h.get_dual_slack()                         # data.S of the reference (:116), from the device
+        if eig_mode == "device":
+            data["escape_rr_stages"] = h.ritz_stages()     # Rayleigh-Ritz stages: (device, host, host after fallback)
     finally:
         h.close()
     data.update({"X": (Y @ Y.T if n <= int(o.get("dense_X_max", 6000)) else None), "y": y, "S": S, "z": z})

@@ -304,6 +304,29 @@ int msdp_linesearch_cost(msdp_handle h, const double* U, double alpha, double* v
  * as the resident point. */
 int msdp_linesearch_accept(msdp_handle h);
 
+/* ---------------------------------------------------------------- rounding */
+
+/* Goemans-Williamson hyperplane rounding of the resident point of a single-rank MSDP_KIND_ONLYUNITDIAG handle to +1/-1
+ * vectors, with optional 1-opt local search, on the device (not in the reference, which returns the bound and the factor).
+ *   x_t = sign(Y r_t) for the `trials` rows r_t of R (trials x p row-major, p the current width; sign(0) = +1),
+ *   val_t = x_t' C x_t (diagonal included), from the rows of C the handle holds.
+ *   sweeps > 0: up to `sweeps` Gauss-Seidel sweeps of 1-opt per trial -- rows i = 0 .. n-1 in order, s_i = sum_{j != i}
+ *     C_ij x_j, x_i flipped where x_i s_i > 0 (strict: a tie stays).  The 64 trials of a word sweep together; a word stops
+ *     after a sweep of its own without a flip, the call when every word has stopped.  All values are then recomputed from
+ *     the final vectors (never updated incrementally); the sums are deterministic (no floating-point atomics).
+ * trials: a multiple of 64, at most MSDP_ROUND_MAX_TRIALS.  Sign bits are packed 64 trials per word: bit t of
+ * masks[w * n + i] is set when x_i = -1 in trial 64 w + t.
+ *   values0 (trials, may be NULL): the values right after the rounding;   values (trials): the final ones (== values0 when
+ *   sweeps == 0);   info (2 x trials/64, may be NULL): per word the sweeps run, then per word the flips of its last sweep;
+ *   masks (trials/64 x n, may be NULL): the final vectors;   *best: the trial of the smallest value (the lowest index wins a
+ *   tie);   x (n entries +1 / -1, may be NULL): the vector of trial *best.
+ * The point, the cost state and every other state of the handle stay as they are; the device memory of the call is
+ * released before it returns.  MSDP_EINVAL: trials <= 0, not a multiple of 64 or above the cap, sweeps < 0, R / values / best
+ * NULL.  MSDP_EUNSUPPORTED: any other kind, a handle that has joined a communicator.  MSDP_ESTATE: no resident point. */
+#define MSDP_ROUND_MAX_TRIALS 4096
+int msdp_round_hyperplane(msdp_handle h, int32_t trials, const double* R, int32_t sweeps, double* values0, double* values,
+                          int32_t* info, uint64_t* masks, int32_t* best, int8_t* x);
+
 /* ----------------------------------------------------------------- escape */
 
 /* Few-eigenvector saddle escape (replaces eig(S) of ManiSDP_onlyunitdiag.m:50,

@@ -41,6 +41,8 @@ class MsdpError(RuntimeError):
 
 
 ESTATE, EUNSUPPORTED = -4, -6
+EINVAL = -1
+ROUND_MAX_TRIALS = 4096             # MSDP_ROUND_MAX_TRIALS
 
 
 _P = C.POINTER
@@ -82,6 +84,8 @@ SIGNATURES = {
     "msdp_get_z": (C.c_int, [C.c_void_p, _dp]),
     "msdp_linesearch_cost": (C.c_int, [C.c_void_p, _dp, C.c_double, _dp]),
     "msdp_linesearch_accept": (C.c_int, [C.c_void_p]),
+    "msdp_round_hyperplane": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.c_int32, _dp, _dp, _i32p, _P(C.c_uint64), _i32p,
+                                        _P(C.c_int8)]),
     "msdp_escape_eigs": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int32, _dp, _dp, _dp, _P(C.c_int32)]),
     "msdp_escape_eigs_matrix": (C.c_int, [C.c_void_p, _dp, C.c_int32, C.c_double, C.c_int32, _dp, _dp, _dp,
                                          _P(C.c_int32)]),
@@ -526,6 +530,27 @@ class Handle:
 
     def retr(self, U):
         return self._vec_op(self._lib.msdp_retr, U)
+
+    def round_hyperplane(self, R, sweeps=0, masks=False):
+        """Hyperplane rounding of the resident point on the device (msdp_round_hyperplane): x_t = sign(Y r_t) for the rows r_t
+        of R (trials x p, trials a multiple of 64), the values x_t' C x_t, then up to `sweeps` sweeps of 1-opt local search.
+        Returns a dict: values0 (after the rounding), values (final), info (2 x trials/64: sweeps run and flips of the last
+        sweep, per word of 64 trials), best (trial of the smallest value), x (its +1/-1 vector, int8) and masks (trials/64 x n
+        uint64 sign bits, bit t of masks[w, i] set when x_i = -1 in trial 64 w + t; None unless asked for)."""
+        R = np.ascontiguousarray(R, dtype=np.float64)
+        if R.ndim != 2 or (self.p and R.shape[1] != self.p):        # (no point yet: the library refuses the call)
+            raise ValueError(f"round_hyperplane: R must be trials x p = {self.p}, not {R.shape}")
+        T = R.shape[0]
+        W = max(T // 64, 1)
+        values0, values = np.zeros(T), np.zeros(T)
+        info = np.zeros((2, W), dtype=np.int32)
+        M = np.zeros((W, self.n), dtype=np.uint64) if masks else None
+        x = np.zeros(self.n, dtype=np.int8)
+        best = C.c_int32()
+        _check(self._lib.msdp_round_hyperplane(self._h, T, _dptr(R), int(sweeps), _dptr(values0), _dptr(values),
+                                               info.ctypes.data_as(_i32p), M.ctypes.data_as(_P(C.c_uint64)) if masks else None,
+                                               C.byref(best), x.ctypes.data_as(_P(C.c_int8))))
+        return {"values0": values0, "values": values, "info": info, "best": best.value, "x": x, "masks": M}
 
     def debug_get_tcg_step(self):
         """(eta, Heta) of the last tCG solve (test hook, see msdp_debug_get_tcg_step)."""

@@ -54,7 +54,7 @@ def _host_threads():
     return threadpool_limits(limits=max(1, min(ncpu, 16)))
 
 __all__ = ["ManiSDP_onlyunitdiag", "ManiSDP_unitdiag", "ManiSDP_unittrace", "ManiSDP", "ManiSDP_multiblock",
-           "ManiDSDP_unitdiag", "DEFAULTS", "DATA_FIELDS"]
+           "ManiDSDP_unitdiag", "round_unitdiag", "DEFAULTS", "DATA_FIELDS"]
 
 # Option defaults of the reference's entry points: ManiSDP_onlyunitdiag.m:8-17,
 # ManiSDP_unitdiag.m:10-26, ManiSDP_unittrace.m:10-25, ManiSDP.m:9-25.
@@ -202,6 +202,48 @@ def _escape_rr_option(o):
     return 1 if rr == "device" else 0
 
 
+def _round_option(o):
+    """options["round"] = {"trials", "sweeps", "seed"}: round the solution to +1/-1 vectors on the device after the solve
+    (msdp_round_hyperplane; not in the reference, so no DEFAULTS entry).  Returns None when the option is absent, else
+    (trials, sweeps, seed) -- trials a multiple of 64 up to _lib.ROUND_MAX_TRIALS, sweeps >= 0 (0: no local search)."""
+    r = o.get("round")
+    if r is None:
+        return None
+    if not isinstance(r, dict):
+        raise ValueError(f"options['round'] must be a dict with 'trials', 'sweeps' and 'seed', not {r!r}")
+    unknown = sorted(set(r) - {"trials", "sweeps", "seed"})
+    if unknown:
+        raise ValueError(f"options['round'] has unknown fields {unknown} (known: 'trials', 'sweeps', 'seed')")
+    trials, sweeps, seed = r.get("trials", 256), r.get("sweeps", 50), r.get("seed", 0)
+    for name, v in (("trials", trials), ("sweeps", sweeps), ("seed", seed)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"options['round'][{name!r}] must be an integer, not {v!r}")
+    if trials <= 0 or trials % 64 or trials > _lib.ROUND_MAX_TRIALS:
+        raise ValueError(f"options['round']['trials'] must be a multiple of 64 in 64..{_lib.ROUND_MAX_TRIALS}, not {trials}")
+    if sweeps < 0 or seed < 0:
+        raise ValueError(f"options['round']['sweeps'] and ['seed'] must be >= 0, not {sweeps} and {seed}")
+    if o.get("comm") is not None:
+        raise ValueError("options['round'] needs a single-rank solve (no options['comm'])")
+    return int(trials), int(sweeps), int(seed)
+
+
+def round_unitdiag(C, Y, trials=256, sweeps=50, rng=None, R=None):
+    """Round the factor Y (n x p, unit rows) of a unit-diagonal SDP with cost C to a +1/-1 vector on the device: `trials`
+    hyperplane roundings x = sign(Y r) with Gaussian r (drawn from `rng` unless R, trials x p, is given), each improved by up
+    to `sweeps` sweeps of 1-opt local search; the best of them is returned.  Returns (x, value, info): x int8 of length n,
+    value = x' C x, info the dict of Handle.round_hyperplane (all values, sweeps and flips per word of 64 trials)."""
+    Y = np.ascontiguousarray(Y, dtype=np.float64)
+    if R is None:
+        R = (rng or np.random.default_rng(0)).standard_normal((int(trials), Y.shape[1]))
+    h = _lib.Handle.onlyunitdiag(C.tocsr() if sp.issparse(C) else np.asarray(C, dtype=np.float64), pcap=max(32, Y.shape[1]))
+    try:
+        h.set_point(Y)
+        res = h.round_hyperplane(R, sweeps=sweeps)
+    finally:
+        h.close()
+    return res["x"], float(res["values"][res["best"]]), res
+
+
 # =============================================================== onlyunitdiag
 def ManiSDP_onlyunitdiag(C, options=None, verbose=True, rng=None):
     with _host_threads():
@@ -218,6 +260,7 @@ def _onlyunitdiag_impl(C, options=None, verbose=True, rng=None):
     for k, v in DEFAULTS["onlyunitdiag"].items():
         o.setdefault(k, v)
     escape_rr = _escape_rr_option(o)                       # (a bad value is refused before anything is built)
+    rounding = _round_option(o)
     dense_max = int(o.get("dense_eig_max", 3000))          # the host eig(S) is allowed up to this order (options['eig'] = 'host') ...
     dense_default = int(o.get("dense_eig_default", 600))   # ... and the default up to this one (round 6: G1, n = 800, 0.124 s with it, 0.047 s
                                                            # with the device escape + its independent check; the affine kinds switch at 400 / 600)
@@ -395,6 +438,12 @@ def _onlyunitdiag_impl(C, options=None, verbose=True, rng=None):
             dinf = max(0.0, -lam_v) / (1.0 + lmax_v)
         if eig_mode == "device":
             data["escape_rr_stages"] = h.ritz_stages()         # Rayleigh-Ritz stages: (device, host, host after fallback)
+        if rounding is not None and obj is not None:           # options["round"]: +1/-1 vectors from the evaluated point
+            trials, sweeps, seed = rounding
+            h.set_point(Y_eval)
+            res = h.round_hyperplane(np.random.default_rng(seed).standard_normal((trials, Y_eval.shape[1])), sweeps=sweeps)
+            data["round"] = {"x": res["x"], "value": float(res["values"][res["best"]]), "values": res["values"],
+                             "best": res["best"], "info": res["info"]}
     finally:
         h.close()
     if obj is not None:

@@ -108,6 +108,16 @@ int msdp_create_onlyunitdiag_csc(int64_t n, const int64_t* jc, const int64_t* ir
 int msdp_create_onlyunitdiag_dense(int64_t n, const double* C, int32_t pcap,
                                    msdp_handle* out);
 
+/* Same with C = Cs + V diag(s) V' held implicitly: Cs sparse symmetric in CSC as above (its diagonal may be present), V
+ * n x q column-major, s of length q (either sign).  Stands for ManiSDP_onlyunitdiag.m:6 (the cost matrix C the closures of
+ * :117-130 multiply with), without ever forming the dense n x n matrix: a product C*U is the sparse product plus the two
+ * skinny ones T = diag(s) V' U (q x p, a deterministic two-stage reduction) and V T.  1 <= q <= MSDP_LOWRANK_MAX and V, s not
+ * NULL, else MSDP_EINVAL.  Cost, gradient, Hess-vec, msdp_rtr (the generic per-iteration path), the Lanczos escape and
+ * msdp_round_hyperplane accept the handle; joining a communicator of any form returns MSDP_EUNSUPPORTED. */
+#define MSDP_LOWRANK_MAX 8
+int msdp_create_onlyunitdiag_csc_lowrank(int64_t n, const int64_t* jc, const int64_t* ir, const double* pr,
+                                         int32_t q, const double* V, const double* s, int32_t pcap, msdp_handle* out);
+
 /* Pre-sharded synthetic dense problem (BASELINE config 5: n = 100000, p = 64 over 8 GPUs; the full C would be
  * 80 GB): rank `rank` of `nranks` fills ITS rows of a dense symmetric C on the device from a counter-based
  * generator; msdp_synthetic_dense_entry is the same generator on the host (parity tests). */
@@ -309,7 +319,12 @@ int msdp_linesearch_accept(msdp_handle h);
 /* Goemans-Williamson hyperplane rounding of the resident point of a single-rank MSDP_KIND_ONLYUNITDIAG handle to +1/-1
  * vectors, with optional 1-opt local search, on the device (not in the reference, which returns the bound and the factor).
  *   x_t = sign(Y r_t) for the `trials` rows r_t of R (trials x p row-major, p the current width; sign(0) = +1),
- *   val_t = x_t' C x_t (diagonal included), from the rows of C the handle holds.
+ *   val_t = x_t' C x_t (diagonal included), from the rows of C the handle holds.  A sparse-plus-low-rank handle
+ *     (msdp_create_onlyunitdiag_csc_lowrank): val_t = x' Cs x + sum_k s_k (V_k' x)^2, the q sums V_k' x formed in the same
+ *     ordered pass over the rows (per-chunk partials added in index order, then squared); in the 1-opt sweeps
+ *     x_i s_i = (sparse sum over j != i) + sum_k s_k V_ik (x_i t_k - V_ik) with t_k = V_k' x held per trial, formed by
+ *     one ordered pass over the rows at the start of every sweep launch (never carried between launches) and updated
+ *     by t_k -= 2 V_ik x_i(old) at a flip.
  *   sweeps > 0: up to `sweeps` Gauss-Seidel sweeps of 1-opt per trial -- rows i = 0 .. n-1 in order, s_i = sum_{j != i}
  *     C_ij x_j, x_i flipped where x_i s_i > 0 (strict: a tie stays).  The 64 trials of a word sweep together; a word stops
  *     after a sweep of its own without a flip, the call when every word has stopped.  All values are then recomputed from

@@ -43,6 +43,7 @@ class MsdpError(RuntimeError):
 ESTATE, EUNSUPPORTED = -4, -6
 EINVAL = -1
 ROUND_MAX_TRIALS = 4096             # MSDP_ROUND_MAX_TRIALS
+LOWRANK_MAX = 8                     # MSDP_LOWRANK_MAX
 
 
 _P = C.POINTER
@@ -57,6 +58,7 @@ SIGNATURES = {
     "msdp_set_device": (C.c_int, [C.c_int32]),
     "msdp_device_count": (C.c_int, [_P(C.c_int32)]),
     "msdp_create_onlyunitdiag_csc": (C.c_int, [C.c_int64, _i64p, _i64p, _dp, C.c_int32, _P(C.c_void_p)]),
+    "msdp_create_onlyunitdiag_csc_lowrank": (C.c_int, [C.c_int64, _i64p, _i64p, _dp, C.c_int32, _dp, _dp, C.c_int32, _P(C.c_void_p)]),
     "msdp_create_onlyunitdiag_dense": (C.c_int, [C.c_int64, _dp, C.c_int32, _P(C.c_void_p)]),
     "msdp_create_onlyunitdiag_dense_synthetic": (C.c_int, [C.c_int64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32,
                                                           _P(C.c_void_p)]),
@@ -265,6 +267,30 @@ class Handle:
         else:
             Cd = np.ascontiguousarray(Cmat, dtype=np.float64)
             _check(lib.msdp_create_onlyunitdiag_dense(n, _dptr(Cd), pcap, C.byref(out)))
+        return cls(out.value, KIND_ONLYUNITDIAG, n)
+
+    @classmethod
+    def onlyunitdiag_lowrank(cls, Cs, V, s, pcap=32):
+        """C = Cs + V diag(s) V' held implicitly (msdp_create_onlyunitdiag_csc_lowrank): Cs sparse symmetric n x n, V n x q
+        with 1 <= q <= LOWRANK_MAX (a vector counts as one column), s of length q.  q is checked by the library."""
+        import scipy.sparse as sp
+        lib = load()
+        out = C.c_void_p()
+        n = Cs.shape[0]
+        Cc = sp.csc_matrix(Cs)
+        Cc.sort_indices()
+        V = np.asarray(V, dtype=np.float64)
+        if V.ndim == 1:
+            V = V[:, None]
+        s = np.ascontiguousarray(np.atleast_1d(s), dtype=np.float64)
+        if V.ndim != 2 or V.shape[0] != n or s.shape != (V.shape[1],):
+            raise ValueError(f"V must be {n} x q and s of length q, not {V.shape} and {s.shape}")
+        Vf = np.asfortranarray(V)                      # n x q column-major
+        jc = np.ascontiguousarray(Cc.indptr, dtype=np.int64)
+        ir = np.ascontiguousarray(Cc.indices, dtype=np.int64)
+        pr = np.ascontiguousarray(Cc.data, dtype=np.float64)
+        _check(lib.msdp_create_onlyunitdiag_csc_lowrank(n, jc.ctypes.data_as(_i64p), ir.ctypes.data_as(_i64p), _dptr(pr),
+                                                        V.shape[1], Vf.ctypes.data_as(_dp), _dptr(s), pcap, C.byref(out)))
         return cls(out.value, KIND_ONLYUNITDIAG, n)
 
     @classmethod

@@ -288,6 +288,22 @@ extern "C" int msdp_create_onlyunitdiag_csc(int64_t n, const int64_t* jc, const 
     return 0;
 }
 
+// C = Cs + V diag(s) V' (ManiSDP_onlyunitdiag.m:6 with C held implicitly): the sparse handle plus the low-rank fields
+extern "C" int msdp_create_onlyunitdiag_csc_lowrank(int64_t n, const int64_t* jc, const int64_t* ir, const double* pr, int32_t q,
+                                                    const double* V, const double* s, int32_t pcap, msdp_handle* out) {
+    if (q < 1 || q > MSDP_LOWRANK_MAX) { msdp_set_error("low-rank term: q = %d outside 1 .. %d", q, MSDP_LOWRANK_MAX); return MSDP_EINVAL; }
+    if (!V || !s) { msdp_set_error("low-rank term: null V or s"); return MSDP_EINVAL; }
+    if (!out) { msdp_set_error("out handle pointer is null"); return MSDP_EINVAL; }
+    if (n <= 0 || n > 0x7fffffff) { msdp_set_error("matrix order n = %lld out of range", (long long)n); return MSDP_EINVAL; }
+    msdp_handle h = nullptr;
+    int rc = msdp_create_onlyunitdiag_csc(n, jc, ir, pr, pcap, &h);
+    if (rc) return rc;
+    if ((rc = msdp_lowrank_setup(h, q, V, s))) { msdp_destroy(h); return rc; }
+    h->d.costkind = COST_SPLR;
+    *out = h;
+    return 0;
+}
+
 extern "C" int msdp_create_onlyunitdiag_dense(int64_t n, const double* C, int32_t pcap, msdp_handle* out) {
     if (!C) { msdp_set_error("null C"); return MSDP_EINVAL; }
     msdp_handle h = nullptr;
@@ -654,7 +670,7 @@ extern "C" int msdp_set_point(msdp_handle h, int32_t p, const double* Y) {
     d.ld = ((p + 1) / 2) * 2;
     if (!h->use_comm && h->nranks == 1) d.full = d.md;   // overwritten per launch by allgather_rows
     choose_grid(h);
-    if (d.costkind != COST_SPARSE) {
+    if (!msdp_cost_sparse_rows(d.costkind)) {
         int rc = msdp_dense_reserve(h, d.costkind == COST_AFFINE ? 2 : 1);
         if (rc) return rc;
     }
@@ -678,7 +694,7 @@ static int adopt_point(msdp_handle h, int slot, int p) {
     d.ld = ((p + 1) / 2) * 2;
     if (!h->use_comm && h->nranks == 1) d.full = d.md;
     choose_grid(h);
-    if (d.costkind != COST_SPARSE) {
+    if (!msdp_cost_sparse_rows(d.costkind)) {
         int rc = msdp_dense_reserve(h, d.costkind == COST_AFFINE ? 2 : 1);
         if (rc) return rc;
     }
@@ -864,7 +880,7 @@ extern "C" int msdp_get_p(msdp_handle h, int32_t* p) {
 
 // The plans of the symmetric contraction follow the dense_sym* options: reserve again where a dense operand is resident
 static int dense_rereserve(msdp_handle h) {
-    return (h->have_point && h->d.costkind != COST_SPARSE && !h->blocked) ? msdp_dense_reserve(h, h->d.costkind == COST_AFFINE ? 2 : 1) : 0;
+    return (h->have_point && !msdp_cost_sparse_rows(h->d.costkind) && !h->blocked) ? msdp_dense_reserve(h, h->d.costkind == COST_AFFINE ? 2 : 1) : 0;
 }
 
 extern "C" int msdp_set_option(msdp_handle h, const char* name, int32_t value) {

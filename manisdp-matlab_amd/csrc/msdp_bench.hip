@@ -9,6 +9,12 @@ static void algo_cost(msdp_handle h, double* bytes, double* flops) {
         // nnz*(8+4) + (n+1)*4 + 3*8*n*p + 8*n ; 2*nnz*p + 5*n*p
         *bytes = (double)d.nnz * 12.0 + (n + 1) * 4.0 + 24.0 * n * p + 8.0 * n;
         *flops = 2.0 * (double)d.nnz * p + 5.0 * n * p;
+    } else if (d.costkind == COST_SPLR) {
+        // the sparse launch plus the low-rank term: the gather source read once more by the projection (8 n p), V read by
+        // the projection and by the row launch (2 * 8 n q), T written and read (q p, negligible); 2 n q p flops each
+        const double q = d.lrq;
+        *bytes = (double)d.nnz * 12.0 + (n + 1) * 4.0 + 24.0 * n * p + 8.0 * n + 8.0 * n * p + 16.0 * n * q + 16.0 * q * p;
+        *flops = 2.0 * (double)d.nnz * p + 5.0 * n * p + 4.0 * n * q * p;
     } else if (d.costkind == COST_DENSE) {
         *bytes = 8.0 * n * (double)d.n + 24.0 * n * p;
         *flops = 2.0 * n * (double)d.n * p;

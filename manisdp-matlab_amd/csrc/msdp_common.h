@@ -74,7 +74,10 @@ enum { P_F = 0, P_GG = 1, P_DHD = 2, P_S1 = 3, P_S2 = 4, P_S3 = 5, P_RD = 6, P_A
        P_T1 = 9, P_T2 = 10, P_T3 = 11 };
 
 enum { MANI_OBLIQUE = 0, MANI_SPHERE = 1, MANI_EUCLID = 2 };
-enum { COST_SPARSE = 0, COST_DENSE = 1, COST_AFFINE = 2 };
+enum { COST_SPARSE = 0, COST_DENSE = 1, COST_AFFINE = 2,
+       COST_SPLR = 3 };   // C = Cs + V diag(s) V': the sparse rows below plus the low-rank fields lr* (msdp_lowrank.hip)
+// the rows of the cost matrix are sparse rows (no dense n x n operand exists or is reserved)
+static inline bool msdp_cost_sparse_rows(int costkind) { return costkind == COST_SPARSE || costkind == COST_SPLR; }
 
 // Everything a kernel needs, passed by value.
 struct Dev {
@@ -162,7 +165,14 @@ struct Dev {
     unsigned long long* const* xr2_peers;
     int persist_slots;    // A/B: row slots of the persistent tCG plan at p = 17..32 (0: planned)
     int persist_ep;       // CSR rows: the lane groups of a wave share a row and split its entries where the grid allows (1, default) or never (0)
+    // COST_SPLR (msdp_lowrank.hip): lrq = q columns of V; lrV = V row-major (n x q: a row's q values are one contiguous load);
+    // lrs = s (q); lrT = T = diag(s) V' X of the gather source of the running launch (q x ld, row stride ld), written by the
+    // projection launch in front of every row launch; lrTp = its per-workgroup partials (MSDP_LR_PARTS x q x ld)
+    int lrq;
+    const double* lrV; const double* lrs;
+    double* lrT; double* lrTp;
 };
+#define MSDP_LR_PARTS 128         // workgroups (= partial sums per entry of T) of the low-rank projection
 
 // Run-time switches of a handle (msdp_set_option; the environment variables of the same meaning are read ONCE, when
 // the handle is created).  Production = the defaults.
@@ -423,6 +433,10 @@ int msdp_k_sum_to(msdp_handle h, int which, double* out);
 int msdp_k_fgram(msdp_handle h, const double* Y, double* part, int nblk, double* out);
 int msdp_k_frotate(msdp_handle h, int cap, int r, int ldn, const double* Y, const double* Q, double* Yn);
 int msdp_k_fappend(msdp_handle h, int cap, int k, int ldn, const double* Y, const double* V, double alpha, int normalize, double* Yn);
+// msdp_lowrank.hip
+int msdp_lowrank_setup(msdp_handle h, int q, const double* V, const double* s);   // uploads V (row-major) and s, allocates T and its partials
+int msdp_lowrank_project(msdp_handle h, const double* X);     // d.lrT = diag(s) V' X (X: n x ld gather source)
+int msdp_lowrank_sv_add(msdp_handle h, const double* v, double* w);   // w += V (s .* (V' v)) for vectors of n entries (the escape's S*v; uses d.lrT / d.lrTp)
 // msdp_trip1.hip, msdp_trip2.hip
 int msdp_trip1_ok(msdp_handle h);                             // sharded trip with one all-reduce applies to this handle
 int msdp_launch_trip1_init(msdp_handle h);

@@ -406,11 +406,13 @@ static int sapply(EscCtx& c, const double* v, double* w) {
     }
     if (c.M)
         hipLaunchKernelGGL(k_sv_dense, dim3((c.n + 3) / 4), dim3(256), 0, h->stream, c.n, c.n, msdp_dense_nS(c.n), c.M, (const double*)nullptr, v, w, 0);
-    else if (d.costkind == COST_SPARSE)
+    else if (msdp_cost_sparse_rows(d.costkind))
         hipLaunchKernelGGL(k_sv_sparse, dim3((c.n + 255) / 256), dim3(256), 0, h->stream, c.n, c.rp, c.ci, c.cv, c.z, v, w);
     else
         hipLaunchKernelGGL(k_sv_dense, dim3((c.n + 3) / 4), dim3(256), 0, h->stream, c.n, c.n, msdp_dense_nS(c.n), (const double*)d.Cd, c.z, v, w, 0);
     HIPCHK(hipGetLastError());
+    // C = Cs + V diag(s) V': w += V (s .* (V' v)), one ordered reduction and one axpy-like launch (msdp_lowrank.hip)
+    if (!c.M && d.costkind == COST_SPLR) return msdp_lowrank_sv_add(h, v, w);
     return 0;
 }
 

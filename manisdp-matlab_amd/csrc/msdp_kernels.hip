@@ -19,11 +19,55 @@
 
 // spmm_row<LPR, NCH, ELL>: one row of C times the gathered vector -- msdp_device.h (shared with msdp_trip1.hip)
 
+// The low-rank term of COST_SPLR in a row body (LR instances): T = diag(s) V' X of the launch's gather source (d.lrT, written
+// by msdp_lowrank_project in front of the launch) is staged in LDS where the instance's row is at most LR_LDS_COLS columns wide
+// (zero beyond q rows / ld columns, so that the row loop needs no bounds test) and read in place (L1 / L2 resident: at most
+// 8 x 1024 doubles) beyond; a row adds sum_k V[row,k] * T[k, its columns] -- V[row, 0..q) is one contiguous load per lane group.
+#define LR_LDS_COLS 128
+template <int LPR, int NCH>
+__device__ __forceinline__ void lr_stage(const Dev& d, double* shT) {
+    constexpr int LDW = 2 * LPR * NCH;
+    for (int idx = threadIdx.x; idx < MSDP_LOWRANK_MAX * LDW; idx += MSDP_BLOCK) {
+        const int k = idx / LDW, c = idx - k * LDW;
+        shT[idx] = (k < d.lrq && c < d.ld) ? d.lrT[k * d.ld + c] : 0.0;
+    }
+    __syncthreads();
+}
+template <int LPR, int NCH, bool TLDS>
+__device__ __forceinline__ void lr_add(const Dev& d, int row, int sub, const double* T, double2 (&acc)[NCH]) {
+    constexpr int LDW = 2 * LPR * NCH;
+    const double* __restrict__ vr = d.lrV + (int64_t)row * d.lrq;
+#pragma unroll
+    for (int k = 0; k < MSDP_LOWRANK_MAX; ++k) {
+        if (k < d.lrq) {
+            const double v = vr[k];
+#pragma unroll
+            for (int ch = 0; ch < NCH; ++ch) {
+                const int col = 2 * sub + ch * 2 * LPR;
+                if (TLDS || col < d.ld) {
+                    const double2 t = ld2(T + (TLDS ? k * LDW : k * d.ld) + col);
+                    acc[ch].x = fma(v, t.x, acc[ch].x);
+                    acc[ch].y = fma(v, t.y, acc[ch].y);
+                }
+            }
+        }
+    }
+}
+
 // cost + Riemannian gradient at Y[slot] (gather source: d.full holds all rows of Y[slot]).
-template <int LPR, int NCH, bool ELL>
+template <int LPR, int NCH, bool ELL, bool LR = false>
 __device__ __forceinline__ void costgrad_sparse_obl_body(const Dev& d, int slot) {
     __shared__ double sh[3 * MSDP_WAVES];
     if (d.ctl->done) return;
+    constexpr bool TLDS = 2 * LPR * NCH <= LR_LDS_COLS;
+    const double* Tlr = nullptr;
+    if constexpr (LR) {
+        if constexpr (TLDS) {
+            __shared__ __attribute__((aligned(16))) double shT[MSDP_LOWRANK_MAX * 2 * LPR * NCH];
+            lr_stage<LPR, NCH>(d, shT);
+            Tlr = shT;
+        } else Tlr = d.lrT;
+    }
     int lo, hi;
     msdp_chunk_rows(d.n_loc, d.G, lo, hi);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -50,6 +94,7 @@ __device__ __forceinline__ void costgrad_sparse_obl_body(const Dev& d, int slot)
                 y[ch] = (col < d.ld) ? ld2(Yl + (int64_t)row * d.ld + col) : make_double2(0.0, 0.0);
             }
             spmm_row<LPR, NCH, ELL>(d, row, sub, Xf, acc);
+            if constexpr (LR) lr_add<LPR, NCH, TLDS>(d, row, sub, Tlr, acc);
             double dot = 0.0;
 #pragma unroll
             for (int ch = 0; ch < NCH; ++ch) dot += acc[ch].x * y[ch].x + acc[ch].y * y[ch].y;
@@ -72,10 +117,19 @@ __device__ __forceinline__ void costgrad_sparse_obl_body(const Dev& d, int slot)
 }
 
 // Hess-vec: Hmd = proj-fused (C*md - Y.*rowdot(Y, C*md) - md.*eG), partial <md, Hmd>.
-template <int LPR, int NCH, bool ELL>
+template <int LPR, int NCH, bool ELL, bool LR = false>
 __device__ __forceinline__ void hess_sparse_obl_body(const Dev& d) {
     __shared__ double sh[3 * MSDP_WAVES];
     if (!d.F[0].active) return;
+    constexpr bool TLDS = 2 * LPR * NCH <= LR_LDS_COLS;
+    const double* Tlr = nullptr;
+    if constexpr (LR) {
+        if constexpr (TLDS) {
+            __shared__ __attribute__((aligned(16))) double shT[MSDP_LOWRANK_MAX * 2 * LPR * NCH];
+            lr_stage<LPR, NCH>(d, shT);
+            Tlr = shT;
+        } else Tlr = d.lrT;
+    }
     int lo, hi;
     msdp_chunk_rows(d.n_loc, d.G, lo, hi);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -129,6 +183,10 @@ __device__ __forceinline__ void hess_sparse_obl_body(const Dev& d) {
         }
 #pragma unroll
         for (int q = 0; q < UN; ++q) spmm_row<LPR, NCH, ELL>(d, rows[q], sub, Uf, acc[q]);
+        if constexpr (LR) {
+#pragma unroll
+            for (int q = 0; q < UN; ++q) lr_add<LPR, NCH, TLDS>(d, rows[q], sub, Tlr, acc[q]);
+        }
 #pragma unroll
         for (int q = 0; q < UN; ++q) {
             double dot = 0.0;
@@ -159,6 +217,15 @@ template <int LPR, int NCH>
 __global__ __launch_bounds__(MSDP_BLOCK) void k_hess_sparse_obl(Dev d) { hess_sparse_obl_body<LPR, NCH, false>(d); }
 template <int LPR, int NCH>
 __global__ __launch_bounds__(MSDP_BLOCK) void k_hess_ell_obl(Dev d) { hess_sparse_obl_body<LPR, NCH, true>(d); }
+// COST_SPLR: the same bodies with the low-rank term added behind the sparse gather
+template <int LPR, int NCH>
+__global__ __launch_bounds__(MSDP_BLOCK) void k_costgrad_splr_obl(Dev d, int slot) { costgrad_sparse_obl_body<LPR, NCH, false, true>(d, slot); }
+template <int LPR, int NCH>
+__global__ __launch_bounds__(MSDP_BLOCK) void k_costgrad_splr_ell_obl(Dev d, int slot) { costgrad_sparse_obl_body<LPR, NCH, true, true>(d, slot); }
+template <int LPR, int NCH>
+__global__ __launch_bounds__(MSDP_BLOCK) void k_hess_splr_obl(Dev d) { hess_sparse_obl_body<LPR, NCH, false, true>(d); }
+template <int LPR, int NCH>
+__global__ __launch_bounds__(MSDP_BLOCK) void k_hess_splr_ell_obl(Dev d) { hess_sparse_obl_body<LPR, NCH, true, true>(d); }
 
 // ------------------------------------------------------------------ tCG kernels
 // tCG.m:102-157: eta=0, Heta=0, r=grad, mdelta=r, scalars.
@@ -626,12 +693,16 @@ int msdp_launch_costgrad(msdp_handle h, int slot) {
     if (slot >= 2) {
         if (h->d.costkind != COST_SPARSE || h->use_comm) { msdp_set_error("relative slot: sparse single-rank only"); return MSDP_EINVAL; }
     } else {
-        rc = (h->d.costkind == COST_SPARSE) ? msdp_exchange_rows(h, h->d.Y[slot]) : msdp_allgather_rows(h, h->d.Y[slot]);
+        rc = msdp_cost_sparse_rows(h->d.costkind) ? msdp_exchange_rows(h, h->d.Y[slot]) : msdp_allgather_rows(h, h->d.Y[slot]);
     }
     if (rc) return rc;
     if (h->d.costkind == COST_SPARSE) {
         if (h->d.ellW > 0) DISPATCH_LPR(k_costgrad_ell_obl, h, h->d, slot);
         else DISPATCH_LPR(k_costgrad_sparse_obl, h, h->d, slot);
+    } else if (h->d.costkind == COST_SPLR) {
+        if ((rc = msdp_lowrank_project(h, h->d.full))) return rc;      // T = diag(s) V' Y[slot], unconditionally
+        if (h->d.ellW > 0) DISPATCH_LPR(k_costgrad_splr_ell_obl, h, h->d, slot);
+        else DISPATCH_LPR(k_costgrad_splr_obl, h, h->d, slot);
     } else if (h->d.costkind == COST_DENSE) {
         rc = msdp_dense_costgrad(h, slot);
         if (rc) return rc;
@@ -644,12 +715,16 @@ int msdp_launch_costgrad(msdp_handle h, int slot) {
 }
 
 int msdp_launch_hess(msdp_handle h) {
-    int rc = (h->d.costkind == COST_SPARSE) ? msdp_exchange_rows(h, h->d.md) : msdp_allgather_rows(h, h->d.md);
+    int rc = msdp_cost_sparse_rows(h->d.costkind) ? msdp_exchange_rows(h, h->d.md) : msdp_allgather_rows(h, h->d.md);
     if (rc) return rc;
     if (h->d.costkind == COST_SPARSE) {
         if (msdp_window_eligible(h)) { if ((rc = msdp_window_hess(h))) return rc; }        // gathered rows staged in LDS (msdp_window.hip)
         else if (h->d.ellW > 0) DISPATCH_LPR(k_hess_ell_obl, h, h->d);
         else DISPATCH_LPR(k_hess_sparse_obl, h, h->d);
+    } else if (h->d.costkind == COST_SPLR) {
+        if ((rc = msdp_lowrank_project(h, h->d.full))) return rc;      // T = diag(s) V' mdelta, unconditionally
+        if (h->d.ellW > 0) DISPATCH_LPR(k_hess_splr_ell_obl, h, h->d);
+        else DISPATCH_LPR(k_hess_splr_obl, h, h->d);
     } else if (h->d.costkind == COST_DENSE) {
         rc = msdp_dense_hess(h);
         if (rc) return rc;

@@ -81,12 +81,23 @@ __global__ __launch_bounds__(ROUND_WAVES * 64) void k_round_signs(const double* 
     }
 }
 
-// The rows of C as the handle holds them: CSR (COST_SPARSE) or the dense rows d.Cd with stride nS (COST_DENSE).
+// The rows of C as the handle holds them: CSR (COST_SPARSE) or the dense rows d.Cd with stride nS (COST_DENSE); COST_SPLR: the
+// CSR rows of Cs plus the low-rank term V diag(s) V' (V row-major n x q, the kernel instances with LR set).
 struct RoundCost {
     int n, dense, nS;
     const int* rowptr; const int* colind; const double* cval;
     const double* Cd;
+    int q; const double* V; const double* s;
 };
+// The low-rank term keeps lane = trial: lane t holds t_k = V_k' x of its trial in registers; row i of V is wave-uniform.
+// t_k += x_i V_ik for the lane's sign of row i (bit `lane` of the row's mask word set: x_i = -1)
+__device__ inline void round_lr_accum(const RoundCost& c, int i, u64 mi, int lane, double (&tk)[MSDP_LOWRANK_MAX]) {
+    const double* __restrict__ vr = c.V + (size_t)i * c.q;
+    const bool neg = ((mi >> lane) & 1ull) != 0;
+#pragma unroll
+    for (int k = 0; k < MSDP_LOWRANK_MAX; ++k)
+        if (k < c.q) { const double v = vr[k]; tk[k] += neg ? -v : v; }
+}
 
 __device__ inline u64 round_readlane64(u64 v, int l) {
     const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
@@ -147,38 +158,71 @@ __device__ inline double round_row_sum(double acc, const RoundRow& r, int base, 
 
 // val_t = sum_i sum_j C_ij x_i x_j (diagonal included), deterministic: workgroup (g, w) -- one wave -- sums the rows of chunk g
 // for word w in order and writes part[g][64 w + t]; k_round_sum adds the chunks in index order.  No floating-point atomics.
+// LR: the same pass forms the chunk's partial of V_k' x per trial, partT[g][k][64 w + t]; k_round_sum adds the chunks in index order,
+// squares, and adds sum_k s_k (V_k' x)^2 in k order.
+template <bool LR>
 __global__ __launch_bounds__(64) void k_round_values(RoundCost c, const u64* __restrict__ M, int rows_per, int T,
-                                                     double* __restrict__ part) {
+                                                     double* __restrict__ part, double* __restrict__ partT) {
     const int lane = threadIdx.x;
     const int g = blockIdx.x, w = blockIdx.y;
     const u64* Mw = M + (size_t)w * c.n;
     const int i0 = g * rows_per, i1 = std::min(c.n, i0 + rows_per);
     double acc = 0.0;
+    double tk[MSDP_LOWRANK_MAX];
+    if (LR) {
+#pragma unroll
+        for (int k = 0; k < MSDP_LOWRANK_MAX; ++k) tk[k] = 0.0;
+    }
     for (int i = i0; i < i1; ++i) {
         RoundRow r = round_row(c, i);
         round_uniform(r);
-        acc += round_row_sum<false>(0.0, r, r.e0, Mw, i, Mw[i], false, lane);
+        const u64 mi = Mw[i];
+        acc += round_row_sum<false>(0.0, r, r.e0, Mw, i, mi, false, lane);
+        if (LR) round_lr_accum(c, i, mi, lane, tk);
     }
     part[(size_t)g * T + w * 64 + lane] = acc;
+    if (LR) {
+#pragma unroll
+        for (int k = 0; k < MSDP_LOWRANK_MAX; ++k)
+            if (k < c.q) partT[((size_t)g * c.q + k) * T + w * 64 + lane] = tk[k];
+    }
 }
 
-__global__ void k_round_sum(const double* __restrict__ part, int G, int T, double* __restrict__ val) {
+template <bool LR>
+__global__ void k_round_sum(const double* __restrict__ part, const double* __restrict__ partT, int q, const double* __restrict__ sk,
+                            int G, int T, double* __restrict__ val) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= T) return;
     double s = 0.0;
     for (int g = 0; g < G; ++g) s += part[(size_t)g * T + t];
+    if (LR) {
+        for (int k = 0; k < q; ++k) {
+            double tk = 0.0;
+            for (int g = 0; g < G; ++g) tk += partT[((size_t)g * q + k) * T + t];
+            s += sk[k] * (tk * tk);
+        }
+    }
     val[t] = s;
 }
 
 // One Gauss-Seidel sweep of 1-opt: the wave of word w visits the rows in order, forms x_i s_i = sum_{j != i} C_ij x_i x_j per
 // lane and flips x_i where it is > 0 (strict: a tie stays).  st[w] = sweeps this word has run, st[W + w] = flips of its last
 // one; a word whose last sweep flipped nothing returns at once.  The wave is the only reader and writer of its words.
+// LR: t_k = V_k' x per lane, formed by one ordered pass over the rows at the start of EVERY sweep launch (recomputed, never carried
+// between launches or stored per word); x_i s_i gains sum_k s_k V_ik (x_i t_k - V_ik); a flipped lane takes t_k -= 2 V_ik x_i(old).
+template <bool LR>
 __global__ __launch_bounds__(64) void k_round_1opt(RoundCost c, u64* M, int* st, int W, int first) {
     const int lane = threadIdx.x;
     const int w = blockIdx.x;
     if (!first && st[W + w] == 0) return;
     u64* Mw = M + (size_t)w * c.n;
     int flips = 0;
+    double tk[MSDP_LOWRANK_MAX];
+    if (LR) {
+#pragma unroll
+        for (int k = 0; k < MSDP_LOWRANK_MAX; ++k) tk[k] = 0.0;
+        for (int i = 0; i < c.n; ++i) round_lr_accum(c, i, round_word<true>(Mw, i), lane, tk);
+    }
     // The rows of C are read-only: the first 64 entries of row i + 1 and the bounds of row i + 2 are fetched while the words of
     // row i are in flight, so that a row waits for its mask words only.
     const int last = c.n - 1;
@@ -195,10 +239,23 @@ __global__ __launch_bounds__(64) void k_round_1opt(RoundCost c, u64* M, int* st,
         round_fetch(nxt, nxt.e0, std::min(i + 1, last), true, lane, nj, nvb);
         double xs = round_consume(0.0, mi ^ mj, vb, std::min(64, cur.e1 - cur.e0), lane);
         xs = round_row_sum<true>(xs, cur, cur.e0 + 64, Mw, i, mi, true, lane);
+        const double xi = ((mi >> lane) & 1ull) ? -1.0 : 1.0;
+        if (LR) {
+            const double* __restrict__ vr = c.V + (size_t)i * c.q;
+#pragma unroll
+            for (int k = 0; k < MSDP_LOWRANK_MAX; ++k)
+                if (k < c.q) { const double v = vr[k]; xs += (c.s[k] * v) * (xi * tk[k] - v); }
+        }
         const u64 fl = __ballot(xs > 0.0);
         if (fl) {
             if (lane == 0) __hip_atomic_store(&Mw[i], mi ^ fl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
             flips += __popcll(fl);
+            if (LR && ((fl >> lane) & 1ull)) {
+                const double* __restrict__ vr = c.V + (size_t)i * c.q;
+#pragma unroll
+                for (int k = 0; k < MSDP_LOWRANK_MAX; ++k)
+                    if (k < c.q) tk[k] -= 2.0 * vr[k] * xi;
+            }
         }
         round_uniform(nn);
         cur = nxt; nxt = nn; j = nj; vb = nvb;
@@ -206,10 +263,15 @@ __global__ __launch_bounds__(64) void k_round_1opt(RoundCost c, u64* M, int* st,
     if (lane == 0) { st[w] += 1; st[W + w] = flips; }
 }
 
-static int round_values(msdp_handle h, const RoundCost& c, const u64* M, int W, int G, int rows_per, double* part, double* val) {
+static int round_values(msdp_handle h, const RoundCost& c, const u64* M, int W, int G, int rows_per, double* part, double* partT, double* val) {
     const int T = W * 64;
-    hipLaunchKernelGGL(k_round_values, dim3(G, W), dim3(64), 0, h->stream, c, M, rows_per, T, part);
-    hipLaunchKernelGGL(k_round_sum, dim3((T + 255) / 256), dim3(256), 0, h->stream, (const double*)part, G, T, val);
+    if (c.q > 0) {
+        hipLaunchKernelGGL(k_round_values<true>, dim3(G, W), dim3(64), 0, h->stream, c, M, rows_per, T, part, partT);
+        hipLaunchKernelGGL(k_round_sum<true>, dim3((T + 255) / 256), dim3(256), 0, h->stream, (const double*)part, (const double*)partT, c.q, c.s, G, T, val);
+    } else {
+        hipLaunchKernelGGL(k_round_values<false>, dim3(G, W), dim3(64), 0, h->stream, c, M, rows_per, T, part, (double*)nullptr);
+        hipLaunchKernelGGL(k_round_sum<false>, dim3((T + 255) / 256), dim3(256), 0, h->stream, (const double*)part, (const double*)nullptr, 0, (const double*)nullptr, G, T, val);
+    }
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -225,25 +287,28 @@ extern "C" int msdp_round_hyperplane(msdp_handle h, int32_t trials, const double
     if (h->kind != MSDP_KIND_ONLYUNITDIAG) { msdp_set_error("round_hyperplane: the onlyunitdiag kind only"); return MSDP_EUNSUPPORTED; }
     if (h->nranks > 1 || h->use_comm || h->lgroup) { msdp_set_error("round_hyperplane: not on a handle that has joined a communicator"); return MSDP_EUNSUPPORTED; }
     Dev& d = h->d;
-    if (d.costkind != COST_SPARSE && d.costkind != COST_DENSE) { msdp_set_error("round_hyperplane: no cost matrix"); return MSDP_EUNSUPPORTED; }
+    if (d.costkind != COST_SPARSE && d.costkind != COST_DENSE && d.costkind != COST_SPLR) { msdp_set_error("round_hyperplane: no cost matrix"); return MSDP_EUNSUPPORTED; }
     if (!h->have_point) { msdp_set_error("round_hyperplane: no resident point"); return MSDP_ESTATE; }
     const int n = d.n, p = d.p, T = trials, W = T / 64;
     if (n < 1) { msdp_set_error("round_hyperplane: empty problem"); return MSDP_EINVAL; }
     RoundCost c{};
     c.n = n; c.dense = d.costkind == COST_DENSE; c.nS = msdp_dense_nS(n);
     c.rowptr = d.rowptr; c.colind = d.colind; c.cval = d.cval; c.Cd = d.Cd;
+    const bool lr = d.costkind == COST_SPLR;
+    c.q = lr ? d.lrq : 0; c.V = lr ? d.lrV : nullptr; c.s = lr ? d.lrs : nullptr;
     // row chunks of the value sums: about 2048 waves in flight, at least ROUND_ROWS rows each
     const int G = std::max(1, std::min((n + ROUND_ROWS - 1) / ROUND_ROWS, (2048 + W - 1) / W));
     const int rows_per = (n + G - 1) / G;
     const int Gs = std::max(1, std::min((n + ROUND_ROWS - 1) / ROUND_ROWS, (1024 + W - 1) / W));   // workgroups per word of k_round_signs
 
-    u64* M = nullptr; double* part = nullptr; double* val = nullptr; double* Rd = nullptr; int* st = nullptr;
+    u64* M = nullptr; double* part = nullptr; double* partT = nullptr; double* val = nullptr; double* Rd = nullptr; int* st = nullptr;
     auto release = [&]() {
         (void)hipStreamSynchronize(h->stream);
-        msdp_dev_free(h, M); msdp_dev_free(h, part); msdp_dev_free(h, val); msdp_dev_free(h, Rd); msdp_dev_free(h, st);
+        msdp_dev_free(h, M); msdp_dev_free(h, part); msdp_dev_free(h, partT); msdp_dev_free(h, val); msdp_dev_free(h, Rd); msdp_dev_free(h, st);
     };
     int rc = 0;
     if ((rc = msdp_dev_alloc<u64>(h, &M, (size_t)W * n)) || (rc = msdp_dev_alloc<double>(h, &part, (size_t)G * T)) ||
+        (lr && (rc = msdp_dev_alloc<double>(h, &partT, (size_t)G * c.q * T))) ||
         (rc = msdp_dev_alloc<double>(h, &val, (size_t)T)) || (rc = msdp_dev_alloc<double>(h, &Rd, (size_t)T * p)) ||
         (rc = msdp_dev_alloc<int>(h, &st, (size_t)2 * W))) { release(); return rc; }
 #define ROUND_HIP(expr)                                                                                           \
@@ -260,7 +325,7 @@ extern "C" int msdp_round_hyperplane(msdp_handle h, int32_t trials, const double
     hipLaunchKernelGGL(k_round_signs, dim3(Gs, W), dim3(ROUND_WAVES * 64), 0, h->stream, (const double*)d.Y[msdp_host_cur(h)], d.ld, p, n,
                        (const double*)Rd, M);
     ROUND_HIP(hipGetLastError());
-    if ((rc = round_values(h, c, M, W, G, rows_per, part, val))) { release(); return rc; }
+    if ((rc = round_values(h, c, M, W, G, rows_per, part, partT, val))) { release(); return rc; }
     ROUND_HIP(msdp_memcpy_async(values, val, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     ROUND_HIP(hipStreamSynchronize(h->stream));
     if (values0) std::copy(values, values + T, values0);
@@ -268,7 +333,8 @@ extern "C" int msdp_round_hyperplane(msdp_handle h, int32_t trials, const double
     // the host reads the flip counts after every sweep: it stops when no word flipped anything, or after `sweeps` launches
     std::vector<int> hst((size_t)2 * W, 0);
     for (int s = 0; s < sweeps; ++s) {
-        hipLaunchKernelGGL(k_round_1opt, dim3(W), dim3(64), 0, h->stream, c, M, st, W, s == 0 ? 1 : 0);
+        if (lr) hipLaunchKernelGGL(k_round_1opt<true>, dim3(W), dim3(64), 0, h->stream, c, M, st, W, s == 0 ? 1 : 0);
+        else hipLaunchKernelGGL(k_round_1opt<false>, dim3(W), dim3(64), 0, h->stream, c, M, st, W, s == 0 ? 1 : 0);
         ROUND_HIP(hipGetLastError());
         ROUND_HIP(msdp_memcpy_async(hst.data(), st, hst.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
         ROUND_HIP(hipStreamSynchronize(h->stream));
@@ -277,7 +343,7 @@ extern "C" int msdp_round_hyperplane(msdp_handle h, int32_t trials, const double
         if (!any) break;
     }
     if (sweeps > 0) {                                          // never updated incrementally: all values again from the final masks
-        if ((rc = round_values(h, c, M, W, G, rows_per, part, val))) { release(); return rc; }
+        if ((rc = round_values(h, c, M, W, G, rows_per, part, partT, val))) { release(); return rc; }
         ROUND_HIP(msdp_memcpy_async(values, val, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         ROUND_HIP(hipStreamSynchronize(h->stream));
     }

@@ -1154,3 +1154,50 @@ class SyntheticDenseC:
         if self.n > 20000:
             raise ValueError("SyntheticDenseC.toarray: n = %d is a %0.f-GB matrix" % (self.n, 8e-9 * self.n * self.n))
         return self.rows(np.arange(self.n))
+
+
+class SparsePlusLowRank:
+    """The cost ``C = Cs + V diag(s) V'`` of a unit-diagonal SDP, held as its parts: ``Cs`` sparse symmetric (n x n), ``V``
+    n x q with small q (at most ``_lib.LOWRANK_MAX`` on the device), ``s`` of length q (either sign).  Modularity (a rank-one
+    null model), balanced cuts (a cardinality penalty) and Z2 synchronisation (a rank-one mean shift) have this form; the
+    dense n x n matrix never exists (``msdp_create_onlyunitdiag_csc_lowrank``).  ``ManiSDP_onlyunitdiag`` and
+    ``round_unitdiag`` accept an instance in place of ``C``; ``toarray`` is the dense equivalent for tests and the host
+    eigen-solver of small problems."""
+
+    def __init__(self, Cs, V, s):
+        self.Cs = sp.csr_matrix(Cs, dtype=np.float64)
+        V = np.asarray(V, dtype=np.float64)
+        if V.ndim == 1:
+            V = V[:, None]
+        self.V = np.ascontiguousarray(V)
+        self.s = np.ascontiguousarray(np.atleast_1d(s), dtype=np.float64)
+        n = self.Cs.shape[0]
+        if self.Cs.shape != (n, n):
+            raise ValueError(f"Cs must be square, not {self.Cs.shape}")
+        if self.V.ndim != 2 or self.V.shape[0] != n or self.s.shape != (self.V.shape[1],):
+            raise ValueError(f"V must be {n} x q and s of length q, not {self.V.shape} and {self.s.shape}")
+        if self.V.shape[1] < 1:
+            raise ValueError("the low-rank term needs q >= 1 columns (pass the sparse matrix alone otherwise)")
+        self.shape = (n, n)
+        self.q = int(self.V.shape[1])
+
+    def toarray(self):
+        return self.Cs.toarray() + (self.V * self.s) @ self.V.T
+
+    def matvec(self, x):
+        """C @ x for a vector or an n x k array, without the dense matrix."""
+        x = np.asarray(x, dtype=np.float64)
+        t = self.V.T @ x
+        return self.Cs @ x + self.V @ ((self.s * t.T).T)
+
+
+def modularity(A, gamma=1.0):
+    """The cost of community detection by modularity as a SparsePlusLowRank: ``-(A - gamma d d' / (2m))`` with d the degrees
+    and 2m their sum, so that minimising <C, X> over diag X = 1 maximises the (two-community) modularity
+    ``x' B x / (4m)``, B = A - gamma d d'/(2m)."""
+    A = sp.csr_matrix(A, dtype=np.float64)
+    d = np.asarray(A.sum(axis=1)).ravel()
+    two_m = float(d.sum())
+    if two_m <= 0.0:
+        raise ValueError("modularity: the graph has no edges")
+    return SparsePlusLowRank(-A, d, [float(gamma) / two_m])

@@ -231,11 +231,16 @@ def round_unitdiag(C, Y, trials=256, sweeps=50, rng=None, R=None):
     """Round the factor Y (n x p, unit rows) of a unit-diagonal SDP with cost C to a +1/-1 vector on the device: `trials`
     hyperplane roundings x = sign(Y r) with Gaussian r (drawn from `rng` unless R, trials x p, is given), each improved by up
     to `sweeps` sweeps of 1-opt local search; the best of them is returned.  Returns (x, value, info): x int8 of length n,
-    value = x' C x, info the dict of Handle.round_hyperplane (all values, sweeps and flips per word of 64 trials)."""
+    value = x' C x, info the dict of Handle.round_hyperplane (all values, sweeps and flips per word of 64 trials).  C: sparse,
+    dense, or a problems.SparsePlusLowRank."""
     Y = np.ascontiguousarray(Y, dtype=np.float64)
     if R is None:
         R = (rng or np.random.default_rng(0)).standard_normal((int(trials), Y.shape[1]))
-    h = _lib.Handle.onlyunitdiag(C.tocsr() if sp.issparse(C) else np.asarray(C, dtype=np.float64), pcap=max(32, Y.shape[1]))
+    from .problems import SparsePlusLowRank
+    if isinstance(C, SparsePlusLowRank):
+        h = _lib.Handle.onlyunitdiag_lowrank(C.Cs, C.V, C.s, pcap=max(32, Y.shape[1]))
+    else:
+        h = _lib.Handle.onlyunitdiag(C.tocsr() if sp.issparse(C) else np.asarray(C, dtype=np.float64), pcap=max(32, Y.shape[1]))
     try:
         h.set_point(Y)
         res = h.round_hyperplane(R, sweeps=sweeps)
@@ -270,10 +275,20 @@ def _onlyunitdiag_impl(C, options=None, verbose=True, rng=None):
     _say(verbose, "ManiSDP is starting...")
     n = C.shape[0]
     _say(verbose, f"SDP size: n = {n}, m = {n}")
-    from .problems import SyntheticDenseC
+    from .problems import SparsePlusLowRank, SyntheticDenseC
     comm = o.get("comm")
     pcap = max(32, int(o["p0"]) + 2 * int(o["delta"]))
-    if isinstance(C, SyntheticDenseC):
+    if isinstance(C, SparsePlusLowRank):
+        # C = Cs + V diag(s) V' stays in its parts on the device; the dense matrix exists only for the host eigen-solver of
+        # small problems.  Row-sharded low-rank terms are not implemented: the library refuses every communicator.
+        if comm is not None:
+            raise ValueError("a problems.SparsePlusLowRank cost needs a single-rank solve (no options['comm'])")
+        if not 1 <= C.q <= _lib.LOWRANK_MAX:
+            raise ValueError(f"the low-rank term has q = {C.q} columns; the device kernels hold 1 .. {_lib.LOWRANK_MAX}")
+        eig_mode = o.get("eig", "host" if n <= dense_default else "device")
+        Csp = C.toarray() if eig_mode in ("host", "host_sparse") else None
+        h = _lib.Handle.onlyunitdiag_lowrank(C.Cs, C.V, C.s, pcap=pcap)
+    elif isinstance(C, SyntheticDenseC):
         # BASELINE config 5: every rank generates its rows of the dense C on the device; the matrix never exists on the host
         # (only the host eigen-solver of small test problems asks for it)
         eig_mode = o.get("eig", "host" if (n <= dense_default and comm is None) else "device")
@@ -450,6 +465,8 @@ def _onlyunitdiag_impl(C, options=None, verbose=True, rng=None):
         Y = Y_eval          # the point the residues belong to (the loop's last pass has already widened its own copy)
     if S is None and Csp is not None and sp.issparse(Csp) and z is not None:
         S = Csp - sp.diags(z)                              # :49 (kept sparse; the reference returns full(S))
+    if S is None and isinstance(C, SparsePlusLowRank) and z is not None and n <= dense_X_max:
+        S = C.toarray() - np.diag(z)                       # the implicit C is formed only below dense_X_max (None above)
     data.update({"Y": Y, "S": S, "z": z, "dinf": dinf, "gradnorm": gradnorm,
                  "time": time.time() - t0, "p": Y.shape[1],
                  "X": (Y @ Y.T if n <= dense_X_max else None)})   # :45,86

@@ -1,7 +1,10 @@
 // msdp_affine_dev.h -- device view of the affine operator (At in its several layouts) shared by msdp_affine.hip and the dense
-// contraction launch that carries the SDDMM of the sphere Hess-vec as a side job (msdp_dense.hip, k_dense_partial3<.., SIDE>).
+// contraction launch that carries the SDDMM of the sphere Hess-vec as a side job (msdp_dense.hip, k_dense_partial3<.., SIDE>);
+// and the per-handle state of the affine kinds, shared by msdp_affine.hip (operator, primal closures), msdp_affine_setup.hip
+// (set-up, release) and msdp_dual.hip (the dual kinds).
 #pragma once
 #include "msdp_device.h"
+#include "msdp_affine_plan.h"      // SDDMM_CHUNK, FIN_SHORT, ADJ_T, ADJ_LONG, ADJB_LONG: shared with the host plans
 
 struct AffineDev {
     int n, nS, p, ld;
@@ -79,9 +82,7 @@ struct AffineDev {
     int nsup;
 };
 
-#define SDDMM_CHUNK 16
 #define SPB 4                   // panel rows requested together by the sparse A'(w)*Y products
-#define FIN_SHORT 8           // constraints with more items than this are summed by a whole wave (k_sddmm_finish)
 
 // Side job of the contraction launch (sphere / Euclidean Hess-vec on the SDDMM route, one rank; round 4): the work of k_sddmm1 in
 // mode 2 -- w_k = <A_k, Ya Yb'> for the short constraints, the item values of the long ones (ival; the epilogue sums them), the
@@ -164,3 +165,43 @@ __device__ __forceinline__ void msdp_sddmm_side(const SideJob& sj, int job, doub
     }
     if (job == 0 && threadIdx.x == 3) sj.P[P_T3 * MSDP_MAX_GRID + sj.njobs] = 0.0;
 }
+
+// ================================================================== multiblock kind, per-block storage (round 4)
+// ManiSDP_multiblock.m keeps X, S, C as cell arrays of blocks.  Rounds 2-3 embedded the direct sum into ONE dense N x N problem
+// (N = sum n_i): memory and work ~ N^2 -- 3.6 GB per operand at N = 21 100, impossible for thousands of small cliques.  Here
+// every dense operand (c, eS, A'(w), S) is the concatenation of its diagonal blocks, block i an n_i x nS_i row-major array
+// (nS_i = roundup(n_i, 16), zero pad columns): memory and work ~ sum n_i^2.  Row r of the direct sum lives at rbase[r]; its block
+// spans the rows [rlo[r], rhi[r]).  A(.) stays the SDDMM over (i, j) pairs; A'(.) walks the stored positions (CSR by position);
+// the contraction is one MFMA wave per 16-row tile of a block, no split-K, straight into slab 0 of the usual epilogues.
+struct BlockedDev {
+    int nb, N, ntile;
+    int64_t etot;                  // stored entries: sum n_i * nS_i
+    const int64_t* rbase;          // N: offset of the storage row of global row r
+    const int* rlo; const int* rhi; const int* rns;   // N: first / one-past-last row of r's block, its padded order
+    const int* prp;                // etot + 1: CSR by stored position -> (constraint, coefficient)
+    const int* prk; const double* prv;
+    int nlongq; const int* longq;  // stored positions that occur in more than ADJB_LONG constraints (the entry of the monomial 1: in every 'x_i^2 = 1' row of its block): one wave each
+    const int* tile_row0;          // ntile: first row of every 16-row tile (tiles never straddle blocks)
+};
+struct BlockOp { const double* M[2]; const double* X[2]; double scale[2]; int nmat, ld, colofs, ncols; double* out; };
+
+// Per-handle state of the affine kinds (msdp_handle_s::affine): created by the set-ups, deleted by msdp_affine_release
+struct AffineState {
+    AffineDev a{};
+    int64_t nnz = 0;
+    double sigma = 1.0;
+    double* Cdense = nullptr;      // n x nS
+    double* d_y = nullptr;
+    struct DualState* dual = nullptr;   // the dual kinds (msdp_dual.hip, private to that unit)
+    BlockedDev* blk = nullptr;          // multiblock kind with per-block storage (msdp_affine_setup_blocked); host copies of the block offsets:
+    std::vector<int64_t> blk_r0, blk_off; std::vector<int> blk_n, blk_ns;
+    // second stream of the Hess-vec: 2*eS*U does not depend on the A(.) / A'(.) chain and runs beside it (msdp_affine_hess)
+    hipStream_t s2 = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    ~AffineState() {
+        if (ev_fork) (void)hipEventDestroy(ev_fork);
+        if (ev_join) (void)hipEventDestroy(ev_join);
+        if (s2) (void)hipStreamDestroy(s2);
+        delete blk;
+    }
+};

@@ -282,6 +282,8 @@ struct msdp_handle_s {
     // halo exchange (sparse C, option "halo_exchange"): instead of all rows of the direction every rank receives only the rows
     // its rows of C reference (msdp_comm.hip, "Halo exchange")
     struct Halo* halo = nullptr;
+    struct AffineState* affine = nullptr;  // affine, multiblock and dual kinds: the operator At and its operands (msdp_affine_dev.h;
+                                           //   created by msdp_affine_setup[_blocked], deleted by msdp_affine_release)
     struct LocalGroup* lgroup = nullptr;   // in-process stand-in for the RCCL communicator (msdp_comm_init_local)
     unsigned long long* xr_paddr = nullptr; size_t xr_paddr_cap = 0; double* xr_paddr_key[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; int xr_paddr_ld = 0, xr_paddr_n = 0; const int* xr_paddr_pq = nullptr;   // cross-rank push addresses and what they were built from
     bool lgroup_is_ipc = false;                  // the handle's group is a process group (msdp_comm_init_ipc)
@@ -317,7 +319,7 @@ struct msdp_handle_s {
     size_t snap_cap = 0;
     int snap_p = 0;
     double* slab = nullptr;        // split-K partial slabs of the dense MFMA path
-    bool blocked = false;          // multiblock kind with per-block storage: no N x N operand exists (msdp_affine.hip)
+    bool blocked = false;          // multiblock kind with per-block storage: no N x N operand exists (msdp_affine_setup.hip)
     bool dense_symmetric = false;  // every dense operand of the contraction (C, eS, AyU) is symmetric (checked at set-up)
     unsigned long long* trace_buf = nullptr;   // device buffer behind Dev::trace (msdp_debug_persist_trace)
     void* symplans = nullptr;      // work-item plans of the symmetric contraction (msdp_densesym.hip)
@@ -362,7 +364,8 @@ static inline int msdp_host_cur(msdp_handle h) { return h->h_ctl->cur; }
 static inline int msdp_rows_capacity(msdp_handle h) { return (h->d.n + h->nranks - 1) / h->nranks; }
 
 // --- every function one .hip unit defines and another calls, by defining unit (launchers: asynchronous on h->stream) ---
-struct SideJob;                                               // msdp_affine_dev.h
+struct SideJob; struct AffineDev; struct AffineState;         // msdp_affine_dev.h
+struct DualState;                                             // msdp_dual.hip
 // msdp_api.hip
 int msdp_alloc_vectors(msdp_handle h, int pcap);
 int msdp_alloc_common(msdp_handle h);
@@ -389,6 +392,15 @@ template <typename T> inline int msdp_dev_alloc_uncached(msdp_handle h, T** out,
     int rc = msdp_dev_alloc_uncached_bytes(h, &p, (count ? count : 1) * sizeof(T));
     if (!rc) *out = (T*)p;
     return rc;
+}
+// a device copy of a host array (freed with the handle)
+template <typename T> inline int msdp_upload(msdp_handle h, const std::vector<T>& v, const T** out) {
+    void* p = nullptr;
+    int rc = msdp_dev_alloc_bytes(h, &p, v.size() * sizeof(T));
+    if (rc) return rc;
+    if (!v.empty()) HIPCHK(msdp_memcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    *out = (const T*)p;
+    return 0;
 }
 // msdp_comm.hip
 int msdp_allreduce_partials(msdp_handle h, int first, int count);   // no-op when nranks == 1
@@ -496,22 +508,40 @@ int msdp_densesym_eligible(msdp_handle h, int nmat);
 int msdp_densesym_reserve(msdp_handle h, int nmat, size_t* slabs_out);
 int msdp_densesym_gemm(msdp_handle h, hipStream_t stream, int nmat, const double* const* M, const double* const* X, const double* scale, const int* active_flag);
 void msdp_densesym_release(msdp_handle h);
-// msdp_affine.hip
-int msdp_affine_setup(msdp_handle h, const int64_t* jc, const int64_t* ir, const double* pr, const double* b, const double* c);
-int msdp_affine_setup_blocked(msdp_handle h, int nb, const int64_t* block_n, const int64_t* jc, const int64_t* ir, const double* pr,
-                              const double* b, const double* c);   // multiblock kind, per-block storage
-void msdp_affine_release(msdp_handle h);
-int msdp_affine_set_multipliers(msdp_handle h, const double* y, double sigma);
+// msdp_affine.hip: the closures of the affine kinds, and the operator's launchers (`a` is the caller's copy of AffineState::a with
+// p and ld of the current factor; skipped when *flag == when)
 int msdp_affine_costgrad(msdp_handle h, int slot);
 int msdp_affine_hess(msdp_handle h);
 int msdp_affine_linesearch_cost(msdp_handle h, const double* Yt, double* val);
 int msdp_affine_al_primal(msdp_handle h, double* obj, double* Ax_host);
 int msdp_affine_al_dual(msdp_handle h, const double* y_host, double* z_host);
+void msdp_affine_algo_cost(msdp_handle h, double* bytes, double* flops);
+int msdp_sphere_hess_raw(msdp_handle h, const double* slab, int64_t stride, int SK);
+int msdp_affine_launch_A(msdp_handle h, AffineDev& a, int64_t nnz, const double* Ya, const double* Yb, const int* flag, int when,
+                         int mode, double* axb_out, double sigma, int* G2_out = nullptr);                    // w = A(Ya Yb')
+int msdp_affine_launch_adjoint(msdp_handle h, const AffineDev& a, const double* base, const double* vec, double scale, double* out,
+                               const int* flag, int when, bool restricted_ok);                               // out = base + scale * At*vec
+int msdp_affine_gemm(msdp_handle h, int nmat, const double* const* M, const double* const* X, const double* scale,
+                     const int* active_flag, const double** slab_out, int64_t* stride_out, int* SK_out);      // sum_m scale_m M_m X_m -> slabs
+int msdp_affine_gram(msdp_handle h, const double* Ya, const double* Yb, double* W, const int* flag, int when);   // W = Ya*Yb' in the handle's storage
+int msdp_affine_rowdot_slabs(msdp_handle h, const double* Yl, const double* slab, int64_t stride, int SK, double scale_out,
+                             double* dst, double* rowdot_out, int which);                                    // k_rowdot_slabs
+int msdp_affine_grad_finish(msdp_handle h, bool oblique, int slot, double sigma, const double* f_given);     // k_obl_grad_finish / k_sph_grad_finish
+// msdp_affine_setup.hip
+int msdp_affine_setup(msdp_handle h, const int64_t* jc, const int64_t* ir, const double* pr, const double* b, const double* c);
+int msdp_affine_setup_blocked(msdp_handle h, int nb, const int64_t* block_n, const int64_t* jc, const int64_t* ir, const double* pr,
+                              const double* b, const double* c);   // multiblock kind, per-block storage
+void msdp_affine_release(msdp_handle h);
+int msdp_affine_set_multipliers(msdp_handle h, const double* y, double sigma);
 int msdp_affine_get_block(msdp_handle h, int64_t row0, int64_t nbk, double* S);
 int msdp_affine_block_source(msdp_handle h, int64_t row0, int64_t n, int64_t* off, int64_t* ld);   // per-block storage
-void msdp_affine_algo_cost(msdp_handle h, double* bytes, double* flops);
+// msdp_dual.hip
 int msdp_dual_setup(msdp_handle h, const int64_t* at_jc, const int64_t* at_ir, const double* at_pr, const double* b, const double* c,
                     const double* dAAt, int32_t nf, const int64_t* b_jc, const int64_t* b_ir, const double* b_pr, const double* cf, bool generic);
+void msdp_dual_release(DualState* ds);
+int msdp_dual_costgrad(msdp_handle h, AffineState* st, int slot);      // what the msdp_affine_* closures run on a dual handle
+int msdp_dual_hess(msdp_handle h, AffineState* st);
+int msdp_dual_linesearch_cost(msdp_handle h, AffineState* st, const double* Yt, double* val);
 int msdp_dual_set_zrows(msdp_handle h, int64_t zrows);
 int msdp_dual_g_identity(msdp_handle h);
 int msdp_dual_set_penalty_impl(msdp_handle h, double sigma, const double* wf_host);

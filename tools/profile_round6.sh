@@ -60,7 +60,7 @@ DENSE_SRC=$C/msdp_dense.hip,$C/msdp_densesym.hip
 for p in 16 32; do
   [ -d "$OUT/dense20000p${p}_fetch" ] && python3 tools/pmc_sum.py --sources $DENSE_SRC "$OUT/pmc_dense20000_p$p.json" k_dense_hess_epi hbm_bytes_per_hessvec --only k_dense_sym,k_sym_fold,k_dense_partial3,k_dense_hess_epi "$OUT/dense20000p${p}_fetch" "$OUT/dense20000p${p}_write"
 done
-AFF_SRC=$C/msdp_affine.hip,$C/msdp_affine_dev.h,$C/msdp_dense.hip,$C/msdp_densesym.hip,$C/msdp_sphere.hip
+AFF_SRC=$C/msdp_affine.hip,$C/msdp_affine_setup.hip,$C/msdp_dual.hip,$C/msdp_affine_dev.h,$C/msdp_affine_plan.h,$C/msdp_dense.hip,$C/msdp_densesym.hip,$C/msdp_sphere.hip
 [ -d "$OUT/bqp60_fetch" ] && python3 tools/pmc_sum.py --sources $AFF_SRC "$OUT/pmc_bqp60_p32.json" k_dense_hess_epi hbm_bytes_per_hessvec --only k_gram_mfma,k_gram_apply,k_adjoint_gram,k_adjoint_tiled,k_dense_partial3,k_dense_sym,k_sym_fold,k_dense_hess_epi "$OUT/bqp60_fetch" "$OUT/bqp60_write"
 [ -d "$OUT/theta5000_fetch" ] && python3 tools/pmc_sum.py --sources $AFF_SRC "$OUT/pmc_theta5000_p32.json" k_sph_hess_fused hbm_bytes_per_hessvec --only k_sddmm,k_support_spmm,k_dense_partial3,k_dense_sym,k_sym_fold,k_sph_hess "$OUT/theta5000_fetch" "$OUT/theta5000_write"
 [ -d "$OUT/hess1e6win_fetch" ] && python3 tools/pmc_to_json.py k_hess_win "$OUT/pmc_hess_win_n1e6_p32.json" --sources $C/msdp_window.hip,$C/msdp_device.h "$OUT/hess1e6win_fetch" "$OUT/hess1e6win_write"

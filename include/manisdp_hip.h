@@ -595,6 +595,28 @@ int msdp_tcg_path(msdp_handle h, int32_t* path);
  * "persist_pipe", rows of <= 8 entries or shared CSR rows, p <= 32, every vector in registers), 1 = the "persist_early" form, 0 = two reductions per
  * trip (tCG.m:166 and :227-241 separately); -1 = the tCG is not persistent.  All forms follow tCG.m:95-292. */
 int msdp_debug_persist_form(msdp_handle h, int32_t* form);
+/* (test / diagnostic) What the set-up of a primal affine handle (MSDP_KIND_UNITDIAG, _UNITTRACE, _GENERIC) planned from the constraint
+ * data, and which branch the last calls took.  Host only: no launch, the handle is not modified.  out[0..15]:
+ *    0 usym      1 = c and every A_k are symmetric entry by entry (upper view, tiled adjoint, B route possible)
+ *    1 ntp       32 x 32 upper tile pairs of the tiled adjoint (0: data not symmetric, the flat adjoint kernel runs)
+ *    2 nlong_e   matrix entries (i <= j) in more than 8 constraints: one wave each in the tiled adjoint
+ *    3 bW        ELL width 1..4 of the B route (0: not built)
+ *    4 packed    1 = the B matrix is stored as position | coefficient code (at most 256 distinct coefficients)
+ *    5 bnlong    rows of B wider than bW: one wave each
+ *    6 nsup      entries At touches when they are at most 1/8 of the matrix (0: restricted adjoint and sparse products not built)
+ *    7 nlong     constraints of more than 128 nonzeros (summed through item values)
+ *    8 nshort    the other constraints
+ *    9 nlit      work items of the long constraints
+ *   10 n         order of the matrix
+ *   11 nS        padded row length of the dense operands
+ *   12 last_hess_path   0 no Hess-vec yet, 1 two streams (option "affine_overlap"), 2 B route, 3 fused sphere / Euclidean Hess-vec
+ *                       with the SDDMM as a side job of the contraction, 4 the same with the SDDMM as a launch of its own, 5 two
+ *                       passes with the sparse product on the touched entries, 6 two passes with the adjoint and the two-matrix
+ *                       contraction
+ *   13 last_A_route     0 none yet, 1 SDDMM + finish kernel, 2 fused SDDMM, 3 Gram matrix (a side job leaves it as it was)
+ *   14, 15       zero
+ * MSDP_ESTATE: a dual handle, a handle with per-block storage, a kind without affine state. */
+int msdp_debug_affine_plan(msdp_handle h, int32_t* out);
 
 /* ------------------------------------------------------------ measurement */
 

@@ -136,6 +136,7 @@ SIGNATURES = {
     "msdp_debug_shard": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "msdp_tcg_path": (C.c_int, [C.c_void_p, _P(C.c_int32)]),
     "msdp_debug_persist_form": (C.c_int, [C.c_void_p, _P(C.c_int32)]),
+    "msdp_debug_affine_plan": (C.c_int, [C.c_void_p, _P(C.c_int32)]),
     "msdp_point_snapshot": (C.c_int, [C.c_void_p]),
     "msdp_point_restore": (C.c_int, [C.c_void_p]),
     "msdp_al_primal": (C.c_int, [C.c_void_p, _dp, _dp]),
@@ -147,6 +148,9 @@ SIGNATURES = {
     "msdp_last_error": (C.c_char_p, []),
     "msdp_version": (C.c_char_p, []),
 }
+
+AFFINE_PLAN_FIELDS = ("usym", "ntp", "nlong_e", "bW", "packed", "bnlong", "nsup", "nlong", "nshort", "nlit", "n", "nS",
+                      "last_hess_path", "last_A_route")
 
 _lib = None
 
@@ -818,6 +822,13 @@ class Handle:
         v = C.c_int32()
         _check(self._lib.msdp_debug_persist_form(self._h, C.byref(v)))
         return v.value
+
+    def affine_plan(self):
+        """What the set-up of a primal affine handle planned and which branch the last Hess-vec / A(.) took, as a dict
+        (msdp_debug_affine_plan in include/manisdp_hip.h explains every field)."""
+        v = (C.c_int32 * 16)()
+        _check(self._lib.msdp_debug_affine_plan(self._h, v))
+        return dict(zip(AFFINE_PLAN_FIELDS, v))
 
     # ---- measurement
     def persist_trace(self, reps=256):

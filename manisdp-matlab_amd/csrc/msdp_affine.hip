@@ -1173,6 +1173,7 @@ int msdp_affine_launch_A(msdp_handle h, AffineDev& a, int64_t nnz, const double*
         hipLaunchKernelGGL(k_gram_apply, dim3(G), dim3(MSDP_BLOCK), 0, h->stream, a, (const double*)a.W, mode, axb_out, sigma,
                            h->d.P, flag, when);
         HIPCHK(hipGetLastError());
+        h->affine->last_A_route = 3;
         return 0;
     }
     if (sddmm1_ok(h, a, nnz)) {
@@ -1193,6 +1194,7 @@ int msdp_affine_launch_A(msdp_handle h, AffineDev& a, int64_t nnz, const double*
         }
         DISPATCH_LPR_A(k_sddmm1, h, (int)g1, a, h->d, Ya, Yb, mode, axb_out, sigma, flag, when, nbl);
         HIPCHK(hipGetLastError());
+        h->affine->last_A_route = 2;
         return 0;
     }
     if (mode == 2) { msdp_set_error("launch_A: mode 2 needs the fused SDDMM"); return MSDP_ESTATE; }
@@ -1205,12 +1207,14 @@ int msdp_affine_launch_A(msdp_handle h, AffineDev& a, int64_t nnz, const double*
         hipLaunchKernelGGL(k_gram_apply, dim3(G), dim3(MSDP_BLOCK), 0, h->stream, a, (const double*)a.W, mode, axb_out, sigma,
                            h->d.P, flag, when);
         HIPCHK(hipGetLastError());
+        h->affine->last_A_route = 3;
         return 0;
     }
     DISPATCH_LPR_A(k_sddmm, h, sddmm_grid(a, a.ld), a, Ya, Yb, flag, when);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_sddmm_finish, dim3(G), dim3(MSDP_BLOCK), 0, h->stream, a, mode, axb_out, sigma, h->d.P, flag, when);
     HIPCHK(hipGetLastError());
+    h->affine->last_A_route = 1;
     return 0;
 }
 
@@ -1414,6 +1418,7 @@ int msdp_affine_hess(msdp_handle h) {
     const double* slab; int64_t stride; int SK;
     int rc;
     if (h->tune.affine_overlap) {
+        st->last_hess_path = 1;
         // A/B switch, default OFF.  Two branches of the Hess-vec are independent until the epilogue sums their slabs: 2*eS*U (one
         // dense contraction) and the chain w = A(Y U') -> A'(w) -> 4 sigma A'(w)*Y.  Here they run side by side on two streams
         // (fork / join by events; inside a captured chunk the second stream joins the capture).  Measured in round 3: slower than
@@ -1453,6 +1458,7 @@ int msdp_affine_hess(msdp_handle h) {
     }
     if (a.bW > 0 && h->tune.affine_broute && !sharded(h) && !(a.nsup > 0 && d.ld <= 512) && use_gram_route(h, a, st->nnz, a.ld)) {
         // B route: AyU = B * (Y U' + U Y') in one sparse pass over the upper entries (k_adjoint_gram) -- no w, At read once
+        st->last_hess_path = 2;
         dim3 grid((a.nS + 63) / 64, (a.n + 63) / 64);
         hipLaunchKernelGGL(k_gram_mfma, grid, dim3(512), 0, h->stream, a.n, a.nS, a.ld, Yf, Uf, a.Wg, act, 0, 1);
         HIPCHK(hipGetLastError());
@@ -1514,6 +1520,7 @@ int msdp_affine_hess(msdp_handle h) {
         }
         DISPATCH_LPR_A(k_sph_hess_fused, h, d.G, d, a, slab, stride, SK, sigma, G2, support ? 1 : 0, cur, hetero);
         HIPCHK(hipGetLastError());
+        st->last_hess_path = hetero ? 3 : 4;
         return 0;
     }
     // w = A(Y U') ; AyU = A'(w)
@@ -1528,12 +1535,14 @@ int msdp_affine_hess(msdp_handle h) {
         double* extra = const_cast<double*>(slab) + (int64_t)SK * stride;
         if ((rc = launch_support_spmm(h, a, (const double*)a.w, (const double*)d.Y[cur], 4.0 * sigma, extra, act, 0))) return rc;
         ++SK;
+        st->last_hess_path = 5;
     } else {
         { int rca = msdp_affine_launch_adjoint(h, a, (const double*)nullptr, a.w, 1.0, d.AyU, act, 0, true); if (rca) return rca; }
         const double* M[2] = {d.eS[cur] + roff, d.AyU + roff};
         const double* X[2] = {Uf, Yf};
         const double sc[2] = {2.0, 4.0 * sigma};
         if ((rc = msdp_affine_gemm(h, 2, M, X, sc, act, &slab, &stride, &SK))) return rc;
+        st->last_hess_path = 6;
     }
     if (d.manifold == MANI_OBLIQUE) return msdp_dense_hess_epilogue_obl(h, slab, stride, SK);
     return msdp_sphere_hess_raw(h, slab, stride, SK);

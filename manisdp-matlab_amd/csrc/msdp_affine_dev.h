@@ -198,6 +198,9 @@ struct AffineState {
     // second stream of the Hess-vec: 2*eS*U does not depend on the A(.) / A'(.) chain and runs beside it (msdp_affine_hess)
     hipStream_t s2 = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    // host-side record of the branch the last msdp_affine_hess / msdp_affine_launch_A call took (msdp_debug_affine_plan lists the
+    // codes): two ints written next to the launches, read by nothing but that query
+    int last_hess_path = 0, last_A_route = 0;
     ~AffineState() {
         if (ev_fork) (void)hipEventDestroy(ev_fork);
         if (ev_join) (void)hipEventDestroy(ev_join);

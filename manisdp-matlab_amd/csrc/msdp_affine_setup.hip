@@ -245,3 +245,16 @@ int msdp_affine_set_multipliers(msdp_handle h, const double* y, double sigma) {
     h->h_ctl->sigma = sigma;
     return 0;
 }
+
+// (test / diagnostic) What the set-up planned and which branch the last Hess-vec and the last A(.) took: 16 ints, the unused ones
+// zero (include/manisdp_hip.h lists the fields).  Host only: nothing is launched and the handle is not modified.
+extern "C" int msdp_debug_affine_plan(msdp_handle h, int32_t* out) {
+    if (!h || !out) { msdp_set_error("affine_plan: null argument"); return MSDP_EINVAL; }
+    const AffineState* st = h->affine;
+    if (!st || st->dual || st->blk) { msdp_set_error("affine_plan: not a primal affine handle with N x N storage"); return MSDP_ESTATE; }
+    const AffineDev& a = st->a;
+    const int32_t v[16] = {a.usym, a.ntp, a.nlong_e, a.bW, a.bpk != nullptr, a.bnlong, a.nsup, a.nlong, a.nshort, a.nlit, a.n, a.nS,
+                           st->last_hess_path, st->last_A_route, 0, 0};
+    for (int i = 0; i < 16; ++i) out[i] = v[i];
+    return 0;
+}

@@ -118,6 +118,21 @@ int msdp_create_onlyunitdiag_dense(int64_t n, const double* C, int32_t pcap,
 int msdp_create_onlyunitdiag_csc_lowrank(int64_t n, const int64_t* jc, const int64_t* ir, const double* pr,
                                          int32_t q, const double* V, const double* s, int32_t pcap, msdp_handle* out);
 
+/* The complex problem  min <C, X>  s.t. X Hermitian PSD, X_ii = 1  with a sparse Hermitian C = A + iB (phase synchronisation,
+ * unimodular quadratic programmes; manopt's elliptope_SDP_complex).  jc / ir as for msdp_create_onlyunitdiag_csc; val holds
+ * nnz interleaved (re, im) pairs -- the bytes of a complex128 array -- in the same CSC order.  C must be Hermitian (row i is
+ * read as the conjugate of column i); a diagonal entry with a non-zero imaginary part returns MSDP_EINVAL.
+ * Width convention: a factor of complex width p (n x p complex numbers, row-major) crosses EVERY entry point as its real
+ * view of width 2p -- msdp_set_point(h, 2p, Y) with Y the n x 2p doubles (re, im, re, im, ...) of the complex rows, and
+ * msdp_get_point, msdp_hessvec, msdp_rgrad, msdp_proj, msdp_retr likewise; msdp_get_p reports 2p.  An odd width returns
+ * MSDP_EINVAL.  pcap of this call counts complex columns.  msdp_cost and msdp_get_z stay real (z_i = Re conj(y_i) (C Y)_i).
+ * msdp_escape_eigs returns k complex eigenvectors of S = C - diag(z): V holds k columns of n (re, im) pairs (2 n k doubles),
+ * orthonormal in the complex inner product, eigenvalues ascending, none reported more often than S has it (Lanczos path on
+ * the real view; span(Y) is not deflated).  msdp_rtr runs the generic per-iteration path.
+ * MSDP_EUNSUPPORTED: every communicator, msdp_round_hyperplane, msdp_factor_gram / _rotate / _append. */
+int msdp_create_onlyunitdiag_csc_hermitian(int64_t n, const int64_t* jc, const int64_t* ir, const double* val, int32_t pcap,
+                                           msdp_handle* out);
+
 /* Pre-sharded synthetic dense problem (BASELINE config 5: n = 100000, p = 64 over 8 GPUs; the full C would be
  * 80 GB): rank `rank` of `nranks` fills ITS rows of a dense symmetric C on the device from a counter-based
  * generator; msdp_synthetic_dense_entry is the same generator on the host (parity tests). */

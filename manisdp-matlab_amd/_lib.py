@@ -59,6 +59,7 @@ SIGNATURES = {
     "msdp_device_count": (C.c_int, [_P(C.c_int32)]),
     "msdp_create_onlyunitdiag_csc": (C.c_int, [C.c_int64, _i64p, _i64p, _dp, C.c_int32, _P(C.c_void_p)]),
     "msdp_create_onlyunitdiag_csc_lowrank": (C.c_int, [C.c_int64, _i64p, _i64p, _dp, C.c_int32, _dp, _dp, C.c_int32, _P(C.c_void_p)]),
+    "msdp_create_onlyunitdiag_csc_hermitian": (C.c_int, [C.c_int64, _i64p, _i64p, _dp, C.c_int32, _P(C.c_void_p)]),
     "msdp_create_onlyunitdiag_dense": (C.c_int, [C.c_int64, _dp, C.c_int32, _P(C.c_void_p)]),
     "msdp_create_onlyunitdiag_dense_synthetic": (C.c_int, [C.c_int64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32,
                                                           _P(C.c_void_p)]),
@@ -232,6 +233,25 @@ def ritz_device(G, H):
     return theta, W, rank.value, status.value
 
 
+def hermitian_csc(Cmat):
+    """The CSC form (sorted indices, complex128) of a scipy sparse matrix that must be Hermitian: C == C^H exactly and a real
+    diagonal, else ValueError.  No library call."""
+    import scipy.sparse as sp
+    if not sp.issparse(Cmat):
+        raise ValueError("the Hermitian cost matrix must be a scipy sparse matrix")
+    Cc = sp.csc_matrix(Cmat, dtype=np.complex128)
+    if Cc.shape[0] != Cc.shape[1]:
+        raise ValueError(f"the cost matrix is not Hermitian: shape {Cc.shape}")
+    Cc.sum_duplicates()
+    Cc.sort_indices()
+    if np.any(Cc.diagonal().imag != 0.0):
+        raise ValueError("the cost matrix is not Hermitian: its diagonal has imaginary parts")
+    D = (Cc - Cc.conj().T).tocsr()
+    if D.nnz and np.any(D.data != 0):
+        raise ValueError("the cost matrix is not Hermitian: C != C^H")
+    return Cc
+
+
 def default_opts(**kw):
     o = RtrOpts()
     load().msdp_rtr_default_opts(C.byref(o))
@@ -251,6 +271,7 @@ class Handle:
         self.kind = kind
         self.n = n
         self.p = 0
+        self.hermitian = False            # onlyunitdiag_hermitian: factors are complex (n, p) arrays, p counts complex columns
         self._lib = load()
 
     # ---- construction
@@ -296,6 +317,25 @@ class Handle:
         _check(lib.msdp_create_onlyunitdiag_csc_lowrank(n, jc.ctypes.data_as(_i64p), ir.ctypes.data_as(_i64p), _dptr(pr),
                                                         V.shape[1], Vf.ctypes.data_as(_dp), _dptr(s), pcap, C.byref(out)))
         return cls(out.value, KIND_ONLYUNITDIAG, n)
+
+    @classmethod
+    def onlyunitdiag_hermitian(cls, Cmat, pcap=32):
+        """min <C, X> over Hermitian PSD X with unit diagonal, C a scipy sparse complex Hermitian matrix
+        (msdp_create_onlyunitdiag_csc_hermitian).  C == C^H is checked exactly.  On this handle set_point, get_point, rgrad,
+        hessvec, proj, retr and the V of escape_eigs take or return complex (n, p) arrays (they cross the C ABI as their real
+        views of width 2p); cost and get_z stay real.  pcap counts complex columns."""
+        Cc = hermitian_csc(Cmat)
+        lib = load()
+        out = C.c_void_p()
+        n = Cc.shape[0]
+        jc = np.ascontiguousarray(Cc.indptr, dtype=np.int64)
+        ir = np.ascontiguousarray(Cc.indices, dtype=np.int64)
+        val = np.ascontiguousarray(Cc.data, dtype=np.complex128).view(np.float64)      # nnz (re, im) pairs
+        _check(lib.msdp_create_onlyunitdiag_csc_hermitian(n, jc.ctypes.data_as(_i64p), ir.ctypes.data_as(_i64p), _dptr(val), pcap,
+                                                          C.byref(out)))
+        h = cls(out.value, KIND_ONLYUNITDIAG, n)
+        h.hermitian = True
+        return h
 
     @classmethod
     def dense_synthetic(cls, n, seed, nranks=1, rank=0, pcap=32):
@@ -476,6 +516,9 @@ class Handle:
 
     # ---- layout helpers
     def _to_boundary(self, Y):
+        if self.hermitian:                        # complex (n, p) -> its real view (n, 2p)
+            Y = np.ascontiguousarray(Y, dtype=np.complex128)
+            return Y.view(np.float64).reshape(Y.shape[0], -1)
         Y = np.asarray(Y, dtype=np.float64)
         if self.kind in (KIND_UNITTRACE, KIND_GENERIC, KIND_DUAL):
             return np.asfortranarray(Y)           # MATLAB n x p column-major
@@ -483,21 +526,27 @@ class Handle:
 
     def _empty(self):
         # zero-initialised: a row-sharded handle (comm_init / debug_shard) only writes its own rows
+        if self.hermitian:
+            return np.zeros((self.n, 2 * self.p), dtype=np.float64, order="C")
         if self.kind in (KIND_UNITTRACE, KIND_GENERIC, KIND_DUAL):
             return np.zeros((self.n, self.p), dtype=np.float64, order="F")
         return np.zeros((self.n, self.p), dtype=np.float64, order="C")
+
+    def _from_boundary(self, out):
+        out = np.ascontiguousarray(out)
+        return out.view(np.complex128) if self.hermitian else out
 
     # ---- point I/O
     def set_point(self, Y):
         Yb = self._to_boundary(Y)
         assert Yb.shape[0] == self.n
-        self.p = Yb.shape[1]
-        _check(self._lib.msdp_set_point(self._h, self.p, _dptr(Yb)))
+        self.p = Yb.shape[1] // 2 if self.hermitian else Yb.shape[1]
+        _check(self._lib.msdp_set_point(self._h, Yb.shape[1], _dptr(Yb)))
 
     def get_point(self):
         out = self._empty()
         _check(self._lib.msdp_get_point(self._h, _dptr(out)))
-        return np.ascontiguousarray(out)
+        return self._from_boundary(out)
 
     def get_point_all(self):
         """All n rows of the resident point on every rank of a row-sharded handle (one all-gather + download)."""
@@ -544,13 +593,13 @@ class Handle:
     def rgrad(self):
         out = self._empty()
         _check(self._lib.msdp_rgrad(self._h, _dptr(out)))
-        return np.ascontiguousarray(out)
+        return self._from_boundary(out)
 
     def _vec_op(self, fn, U):
         Ub = self._to_boundary(U)
         out = self._empty()
         _check(fn(self._h, _dptr(Ub), _dptr(out)))
-        return np.ascontiguousarray(out)
+        return self._from_boundary(out)
 
     def hessvec(self, U):
         return self._vec_op(self._lib.msdp_hessvec, U)
@@ -568,7 +617,7 @@ class Handle:
         sweep, per word of 64 trials), best (trial of the smallest value), x (its +1/-1 vector, int8) and masks (trials/64 x n
         uint64 sign bits, bit t of masks[w, i] set when x_i = -1 in trial 64 w + t; None unless asked for)."""
         R = np.ascontiguousarray(R, dtype=np.float64)
-        if R.ndim != 2 or (self.p and R.shape[1] != self.p):        # (no point yet: the library refuses the call)
+        if R.ndim != 2 or (self.p and R.shape[1] != self.p and not self.hermitian):   # (no point yet, or a Hermitian handle: the library refuses the call)
             raise ValueError(f"round_hyperplane: R must be trials x p = {self.p}, not {R.shape}")
         T = R.shape[0]
         W = max(T // 64, 1)
@@ -612,7 +661,7 @@ class Handle:
 
     def escape_eigs(self, k, tol=1e-10, maxit=500):
         lam = np.empty(k)
-        V = np.empty((self.n, k), order="F")
+        V = np.empty((self.n, k), order="F", dtype=np.complex128 if self.hermitian else np.float64)   # complex: (re, im) pairs, column by column
         lmax = C.c_double()
         its = C.c_int32()
         _check(self._lib.msdp_escape_eigs(self._h, k, tol, maxit, _dptr(lam), _dptr(V), C.byref(lmax), C.byref(its)))

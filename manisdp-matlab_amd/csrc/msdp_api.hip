@@ -304,6 +304,41 @@ extern "C" int msdp_create_onlyunitdiag_csc_lowrank(int64_t n, const int64_t* jc
     return 0;
 }
 
+// C = A + iB Hermitian (msdp_hermitian.hip): the pattern as above, val = nnz (re, im) pairs; pcap counts complex columns
+extern "C" int msdp_create_onlyunitdiag_csc_hermitian(int64_t n, const int64_t* jc, const int64_t* ir, const double* val, int32_t pcap,
+                                                      msdp_handle* out) {
+    if (!out) { msdp_set_error("out handle pointer is null"); return MSDP_EINVAL; }
+    if (n <= 0 || n > 0x7fffffff) { msdp_set_error("matrix order n = %lld out of range", (long long)n); return MSDP_EINVAL; }
+    if (!jc || (!ir && jc[n] > 0) || (!val && jc[n] > 0)) { msdp_set_error("null sparse arrays"); return MSDP_EINVAL; }
+    const int64_t nnz = jc[n];
+    if (nnz < 0 || nnz > 0x7fffffff) { msdp_set_error("nnz(C) too large"); return MSDP_EINVAL; }
+    if (pcap > 512) { msdp_set_error("Hermitian cost: pcap = %d complex columns exceeds 512 (real width 1024)", pcap); return MSDP_EUNSUPPORTED; }
+    for (int64_t j = 0; j < n; ++j) {
+        if (jc[j] > jc[j + 1] || jc[j] < 0 || jc[j + 1] > nnz) { msdp_set_error("column pointers not monotone"); return MSDP_EINVAL; }
+        for (int64_t k = jc[j]; k < jc[j + 1]; ++k) {
+            if (ir[k] < 0 || ir[k] >= n) { msdp_set_error("row index out of range"); return MSDP_EINVAL; }
+            if (ir[k] == j && val[2 * k + 1] != 0.0) {
+                msdp_set_error("Hermitian cost: diagonal entry %lld has the imaginary part %g (a Hermitian matrix has a real diagonal)", (long long)j, val[2 * k + 1]);
+                return MSDP_EINVAL;
+            }
+        }
+    }
+    msdp_handle h = nullptr;
+    int rc = new_handle(MSDP_KIND_ONLYUNITDIAG, n, &h);
+    if (rc) return rc;
+    h->h_rowptr.resize(n + 1);
+    h->h_colind.resize(nnz);
+    for (int64_t i = 0; i <= n; ++i) h->h_rowptr[i] = (int)jc[i];
+    for (int64_t k = 0; k < nnz; ++k) h->h_colind[k] = (int)ir[k];
+    h->d.costkind = COST_HERM;
+    if ((rc = msdp_alloc_common(h)) || (rc = msdp_hermitian_setup(h, val)) || (rc = msdp_alloc_vectors(h, 2 * (pcap > 0 ? pcap : 32)))) {
+        msdp_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return 0;
+}
+
 extern "C" int msdp_create_onlyunitdiag_dense(int64_t n, const double* C, int32_t pcap, msdp_handle* out) {
     if (!C) { msdp_set_error("null C"); return MSDP_EINVAL; }
     msdp_handle h = nullptr;
@@ -662,6 +697,7 @@ extern "C" int msdp_set_point(msdp_handle h, int32_t p, const double* Y) {
     if (p < 1 || !Y) { msdp_set_error("set_point: p = %d, Y = %p", p, (const void*)Y); return MSDP_EINVAL; }
     if (p > 1024) { msdp_set_error("factor width p = %d exceeds the supported maximum of 1024", p); return MSDP_EUNSUPPORTED; }
     Dev& d = h->d;
+    if (d.costkind == COST_HERM && (p & 1)) { msdp_set_error("set_point: a Hermitian handle takes the real view of a complex factor, an even width (p = %d)", p); return MSDP_EINVAL; }
     if (p > h->pcap) {
         int rc = msdp_alloc_vectors(h, p + 16);
         if (rc) return rc;
@@ -706,6 +742,7 @@ static int adopt_point(msdp_handle h, int slot, int p) {
 
 extern "C" int msdp_factor_gram(msdp_handle h, double* G) {
     MSDP_CHECK_H(h);
+    if (h->d.costkind == COST_HERM) { msdp_set_error("factor_gram: not for a Hermitian handle (the rank cut of a complex factor stays on the host)"); return MSDP_EUNSUPPORTED; }
     if (!h->have_point || !G) { msdp_set_error("factor_gram: no resident point / null out"); return MSDP_ESTATE; }
     Dev& d = h->d;
     const int ld = d.ld, p = d.p;
@@ -724,6 +761,7 @@ extern "C" int msdp_factor_gram(msdp_handle h, double* G) {
 
 extern "C" int msdp_factor_rotate(msdp_handle h, int32_t r, const double* Q) {
     MSDP_CHECK_H(h);
+    if (h->d.costkind == COST_HERM) { msdp_set_error("factor_rotate: not for a Hermitian handle (the rank cut of a complex factor stays on the host)"); return MSDP_EUNSUPPORTED; }
     if (!h->have_point || !Q) { msdp_set_error("factor_rotate: no resident point / null Q"); return MSDP_ESTATE; }
     Dev& d = h->d;
     if (r < 1 || r > d.p) { msdp_set_error("factor_rotate: r = %d outside 1..p = %d", r, d.p); return MSDP_EINVAL; }
@@ -741,6 +779,7 @@ extern "C" int msdp_factor_rotate(msdp_handle h, int32_t r, const double* Q) {
 
 extern "C" int msdp_factor_append(msdp_handle h, int32_t k, const double* V, double alpha, int32_t normalize) {
     MSDP_CHECK_H(h);
+    if (h->d.costkind == COST_HERM) { msdp_set_error("factor_append: not for a Hermitian handle (the rank cut of a complex factor stays on the host)"); return MSDP_EUNSUPPORTED; }
     if (!h->have_point || !V) { msdp_set_error("factor_append: no resident point / null V"); return MSDP_ESTATE; }
     Dev& d = h->d;
     if (k < 1) { msdp_set_error("factor_append: k = %d", k); return MSDP_EINVAL; }

@@ -15,6 +15,10 @@ static void algo_cost(msdp_handle h, double* bytes, double* flops) {
         const double q = d.lrq;
         *bytes = (double)d.nnz * 12.0 + (n + 1) * 4.0 + 24.0 * n * p + 8.0 * n + 8.0 * n * p + 16.0 * n * q + 16.0 * q * p;
         *flops = 2.0 * (double)d.nnz * p + 5.0 * n * p + 4.0 * n * q * p;
+    } else if (d.costkind == COST_HERM) {
+        // p = the real width: complex values of 16 bytes, a complex multiply-add (4 fma) per entry and double2
+        *bytes = (double)d.nnz * 20.0 + (n + 1) * 4.0 + 24.0 * n * p + 8.0 * n;
+        *flops = 4.0 * (double)d.nnz * p + 5.0 * n * p;
     } else if (d.costkind == COST_DENSE) {
         *bytes = 8.0 * n * (double)d.n + 24.0 * n * p;
         *flops = 2.0 * n * (double)d.n * p;

@@ -75,9 +75,10 @@ enum { P_F = 0, P_GG = 1, P_DHD = 2, P_S1 = 3, P_S2 = 4, P_S3 = 5, P_RD = 6, P_A
 
 enum { MANI_OBLIQUE = 0, MANI_SPHERE = 1, MANI_EUCLID = 2 };
 enum { COST_SPARSE = 0, COST_DENSE = 1, COST_AFFINE = 2,
-       COST_SPLR = 3 };   // C = Cs + V diag(s) V': the sparse rows below plus the low-rank fields lr* (msdp_lowrank.hip)
+       COST_SPLR = 3,     // C = Cs + V diag(s) V': the sparse rows below plus the low-rank fields lr* (msdp_lowrank.hip)
+       COST_HERM = 4 };   // C = A + iB Hermitian: rowptr / colind below with the complex values hzv / hzell (msdp_hermitian.hip); cval and ellv are null
 // the rows of the cost matrix are sparse rows (no dense n x n operand exists or is reserved)
-static inline bool msdp_cost_sparse_rows(int costkind) { return costkind == COST_SPARSE || costkind == COST_SPLR; }
+static inline bool msdp_cost_sparse_rows(int costkind) { return costkind == COST_SPARSE || costkind == COST_SPLR || costkind == COST_HERM; }
 
 // Everything a kernel needs, passed by value.
 struct Dev {
@@ -171,6 +172,10 @@ struct Dev {
     int lrq;
     const double* lrV; const double* lrs;
     double* lrT; double* lrTp;
+    // COST_HERM (msdp_hermitian.hip): the complex values (re, im) of the CSR rows (beside rowptr / colind) and of the ELL slices
+    // (beside ellc, padded with (row, 0 + 0i)).  A factor row of complex width p is its real view of 2p doubles: one double2 per
+    // complex entry, so d.p = 2p and d.ld = 2p on such a handle
+    const double2* hzv; const double2* hzell;
 };
 #define MSDP_LR_PARTS 128         // workgroups (= partial sums per entry of T) of the low-rank projection
 
@@ -449,6 +454,10 @@ int msdp_k_fappend(msdp_handle h, int cap, int k, int ldn, const double* Y, cons
 int msdp_lowrank_setup(msdp_handle h, int q, const double* V, const double* s);   // uploads V (row-major) and s, allocates T and its partials
 int msdp_lowrank_project(msdp_handle h, const double* X);     // d.lrT = diag(s) V' X (X: n x ld gather source)
 int msdp_lowrank_sv_add(msdp_handle h, const double* v, double* w);   // w += V (s .* (V' v)) for vectors of n entries (the escape's S*v; uses d.lrT / d.lrTp)
+// msdp_hermitian.hip
+int msdp_hermitian_setup(msdp_handle h, const double* val);   // the complex CSR / ELL values of a COST_HERM handle (val: nnz (re, im) pairs in CSC order)
+int msdp_hermitian_sv(msdp_handle h, const double* z, const double* v, double* w);   // w = C v - z .* v, v and w n complex entries (re, im interleaved)
+int msdp_hermitian_jcopy(msdp_handle h, const double* v, double* w);                 // w = i * v: (re, im) -> (-im, re)
 // msdp_trip1.hip, msdp_trip2.hip
 int msdp_trip1_ok(msdp_handle h);                             // sharded trip with one all-reduce applies to this handle
 int msdp_launch_trip1_init(msdp_handle h);

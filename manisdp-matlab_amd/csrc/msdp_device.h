@@ -325,3 +325,53 @@ __device__ __forceinline__ void spmm_row(const Dev& d, int row, int sub, const d
         }
     }
 }
+
+// The same gather for a Hermitian C = A + iB (COST_HERM, msdp_hermitian.hip): the values are complex (d.hzv / d.hzell) and a
+// double2 of X is one complex number, acc += c * x.  Entries in ascending column order, the real-part product first: with
+// B = 0 the sums carry the bits of spmm_row.
+template <int LPR, int NCH, bool ELL>
+__device__ __forceinline__ void spmm_row_herm(const Dev& d, int row, int sub, const double* __restrict__ X,
+                                              double2 (&acc)[NCH]) {
+    if (ELL) {
+        int c[MSDP_ELL_MAXW];
+        double2 v[MSDP_ELL_MAXW];
+#pragma unroll
+        for (int w = 0; w < MSDP_ELL_MAXW; ++w) {
+            const bool ok = w < d.ellW;
+            c[w] = ok ? d.ellc[(int64_t)w * d.ell_stride + row] : row;
+            v[w] = ok ? d.hzell[(int64_t)w * d.ell_stride + row] : make_double2(0.0, 0.0);
+        }
+#pragma unroll
+        for (int w = 0; w < MSDP_ELL_MAXW; ++w) {
+            if (w < d.ellW) {
+                const double* src = X + (int64_t)c[w] * d.ld + 2 * sub;
+#pragma unroll
+                for (int ch = 0; ch < NCH; ++ch) {
+                    if (2 * sub + ch * 2 * LPR < d.ld) {
+                        const double2 x = ld2(src + ch * 2 * LPR);
+                        acc[ch].x = fma(v[w].x, x.x, acc[ch].x); acc[ch].x = fma(-v[w].y, x.y, acc[ch].x);
+                        acc[ch].y = fma(v[w].x, x.y, acc[ch].y); acc[ch].y = fma(v[w].y, x.x, acc[ch].y);
+                    }
+                }
+            }
+        }
+        return;
+    }
+    const int start = d.rowptr[row], end = d.rowptr[row + 1];
+    const int* __restrict__ ci = d.colind;
+    const double2* __restrict__ cv = d.hzv;
+#pragma unroll 4
+    for (int k = start; k < end; ++k) {
+        const int c = ci[k];
+        const double2 v = cv[k];
+        const double* src = X + (int64_t)c * d.ld + 2 * sub;
+#pragma unroll
+        for (int ch = 0; ch < NCH; ++ch) {
+            if (2 * sub + ch * 2 * LPR < d.ld) {
+                const double2 x = ld2(src + ch * 2 * LPR);
+                acc[ch].x = fma(v.x, x.x, acc[ch].x); acc[ch].x = fma(-v.y, x.y, acc[ch].x);
+                acc[ch].y = fma(v.x, x.y, acc[ch].y); acc[ch].y = fma(v.y, x.x, acc[ch].y);
+            }
+        }
+    }
+}

@@ -404,6 +404,8 @@ static int sapply(EscCtx& c, const double* v, double* w) {
         HIPCHK(msdp_memcpy_async(w, c.w_all, (size_t)c.n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
         return 0;
     }
+    // Hermitian C: v and w are complex vectors of d.n entries in their real view (c.n = 2 d.n), w = C v - z .* v (msdp_hermitian.hip)
+    if (!c.M && d.costkind == COST_HERM) return msdp_hermitian_sv(h, c.z, v, w);
     if (c.M)
         hipLaunchKernelGGL(k_sv_dense, dim3((c.n + 3) / 4), dim3(256), 0, h->stream, c.n, c.n, msdp_dense_nS(c.n), c.M, (const double*)nullptr, v, w, 0);
     else if (msdp_cost_sparse_rows(d.costkind))
@@ -871,7 +873,14 @@ static int escape_impl_once(msdp_handle h, int k, double tol, int maxit, double*
         if (rcg) return rcg;
     }
     if (k < 1) { msdp_set_error("escape_eigs: k >= 1"); return MSDP_EINVAL; }
-    const int n = d.n, p = d.p;
+    // Hermitian C (COST_HERM): the real recurrence runs on the real view of the complex vectors -- length 2 n everywhere below
+    // (workspace, the basis bound, maxit <= 4 n).  As a real operator S has every eigenvalue twice, with eigenvectors v and i v:
+    // whenever a vector enters the deflation set its i-multiple enters with it, so that the next run cannot return it as the
+    // "smallest pair of the complement".  span(Y) is not deflated for this kind, and nothing below reads the factor (its rows
+    // are not vectors of this length).
+    const bool herm = !Mdev && d.costkind == COST_HERM;
+    if (herm && d.n > 0x3fffffff) { msdp_set_error("escape_eigs: Hermitian handle of order %d (the real view exceeds the index range)", d.n); return MSDP_EUNSUPPORTED; }
+    const int n = herm ? 2 * d.n : d.n, p = d.p;
     if (maxit < 8) maxit = 8;
     // Sparse C: the block eigen-solver does the work (msdp_blockeig.hip); the Lanczos machinery below then only serves its
     // short lambda_max run, and `maxit` is the budget of filter steps
@@ -905,7 +914,8 @@ static int escape_impl_once(msdp_handle h, int k, double tol, int maxit, double*
     c.Ypt = (rep_sparse || shard_dense) ? (const double*)h->full_buf
                        : (((h->nranks != 1 || h->use_comm) && h->yfull[cur]) ? (const double*)h->yfull[cur] : (const double*)d.Y[cur]);
     c.ld = d.ld; c.p = d.p;
-    const int qcap = p + k + 1;
+    if (herm) c.Ypt = nullptr;
+    const int qcap = herm ? 2 * k + 2 : p + k + 1;
     double* mem = nullptr;
     const size_t slot_doubles = msdp_lanczos_slot_bytes() / sizeof(double);
     // [prev | Q | V | Z | w | alpha | beta | hbuf | X | slots | err]; prev (n doubles) = warm start kept between calls;
@@ -1008,7 +1018,7 @@ static int escape_impl_once(msdp_handle h, int k, double tol, int maxit, double*
         // Validated on G81/G11/G1: with this threshold the AL loop converges exactly as with the undeflated
         // process (dinf trace to < 1e-8) while the Lanczos runs are ~6x shorter.
         const double dthr = 1e-6;
-        const bool deflate_y = h->tune.escape_deflate && h->gradnorm_valid && gnorm <= dthr * std::max(1.0, fabs(h->h_ctl->fx));
+        const bool deflate_y = !herm && h->tune.escape_deflate && h->gradnorm_valid && gnorm <= dthr * std::max(1.0, fabs(h->h_ctl->fx));
         const bool dbg = h->tune.esc_debug != 0;
         auto tp0 = std::chrono::steady_clock::now();
         double ynorm_max = 0.0;
@@ -1028,6 +1038,7 @@ static int escape_impl_once(msdp_handle h, int k, double tol, int maxit, double*
         auto tp1 = std::chrono::steady_clock::now();
         // sequential deflation: smallest eigenpair of the complement; if negative keep it and repeat (<= k times)
         std::vector<double> found;
+        std::vector<int> herm_x;                        // Hermitian C: the columns of Q that are accepted vectors (the others are their i-multiples)
         bool have_xstart = false;                       // Z doubles as the warm-start buffer until the final Rayleigh-Ritz
         // Across calls: S changes little from one outer iteration to the next, so the first run starts from the
         // bottom eigenvectors the previous call found (deflated against the current Q inside lanczos_smallest)
@@ -1057,6 +1068,13 @@ static int escape_impl_once(msdp_handle h, int k, double tol, int maxit, double*
             if (dbg) fprintf(stderr, "[escape] run at t=%d: nq=%d steps=%d theta=%.6e res=%.2e lmax=%.4f accepted=%d (host checkpoint analysis so far %.1f ms)\n", t, r, m, theta, res, lmx, nacc, 1e3 * c.host_analysis_s);
             lam_max = std::max(lam_max, lmx);
             for (int i = 0; i < nacc; ++i) found.push_back(thetas[i]);
+            if (herm) {
+                // the i-multiples of the accepted vectors, behind them: orthogonal to them and to everything deflated before
+                // (that set is closed under the multiplication), and unit vectors like them
+                for (int i = 0; i < nacc; ++i) ESC_CHECK(msdp_hermitian_jcopy(h, Q + (size_t)(r + i) * n, Q + (size_t)(r + nacc + i) * n));
+                for (int i = 0; i < nacc; ++i) herm_x.push_back(r + i);
+                r += nacc;
+            }
             r += nacc; nfound += nacc; t += nacc;
             const double scale = std::max(fabs(theta), fabs(lam_max)) + 1e-300;
             last_theta = theta; last_res = res;
@@ -1076,6 +1094,13 @@ static int escape_impl_once(msdp_handle h, int k, double tol, int maxit, double*
         }
         // ---- final Rayleigh-Ritz on Z = [Q_Y | X]: recouples the blocks when S*Y is only approximately zero
         const int nz = r;
+        const int nx = (int)herm_x.size();              // Hermitian C: nz = 2 nx, Z = [x_1 .. x_nx | i x_1 .. i x_nx]
+        if (herm) {
+            for (int j = 0; j < nx; ++j) {
+                ESC_HIP(msdp_memcpy_async(Z + (size_t)j * n, Q + (size_t)herm_x[j] * n, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+                ESC_CHECK(msdp_hermitian_jcopy(h, Z + (size_t)j * n, Z + (size_t)(nx + j) * n));
+            }
+        } else
         ESC_HIP(msdp_memcpy_async(Z, Q, (size_t)nz * n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
         // ... and measures how far span(Z) is from invariant: coupling = |(I - ZZ') S Z|_F, from which a lower ESTIMATE of
         // lambda_min follows (Weyl): S = [A E'; E B] in the basis [Z, complement], lambda_min(S) >= min(lambda_min(A),
@@ -1084,7 +1109,9 @@ static int escape_impl_once(msdp_handle h, int k, double tol, int maxit, double*
         // within res of theta, not that none lies below.
         std::vector<double> M((size_t)nz * nz, 0.0), col(nz + 1);
         double coupling2 = 0.0;
-        for (int j = 0; j < nz; ++j) {
+        // Hermitian C: S (i x) = i (S x), so the products with the first nx columns give the whole matrix -- in the basis
+        // [x | i x] it is [[A, -B], [B, A]] with x_i^H S x_j = A_ij + i B_ij
+        for (int j = 0; j < (herm ? nx : nz); ++j) {
             ESC_CHECK(sapply(c, Z + (size_t)j * n, w));
             hipLaunchKernelGGL(k_multidot, dim3(nz), dim3(MSDP_BLOCK), 0, h->stream, n, Z, (int64_t)n, w, c.hbuf);
             hipLaunchKernelGGL(k_dot1, dim3(1), dim3(MSDP_BLOCK), 0, h->stream, n, w, w, c.hbuf + nz, 0);
@@ -1092,7 +1119,9 @@ static int escape_impl_once(msdp_handle h, int k, double tol, int maxit, double*
             ESC_HIP(hipStreamSynchronize(h->stream));
             double inside = 0.0;
             for (int i = 0; i < nz; ++i) { M[(size_t)i * nz + j] = col[i]; inside += col[i] * col[i]; }
-            coupling2 += std::max(0.0, col[nz] - inside);
+            coupling2 += (herm ? 2.0 : 1.0) * std::max(0.0, col[nz] - inside);
+            if (herm)
+                for (int i = 0; i < nx; ++i) { M[(size_t)i * nz + nx + j] = -col[nx + i]; M[(size_t)(nx + i) * nz + nx + j] = col[i]; }
         }
         for (int i = 0; i < nz; ++i) for (int j = i + 1; j < nz; ++j) {
             const double sm = 0.5 * (M[(size_t)i * nz + j] + M[(size_t)j * nz + i]);
@@ -1103,12 +1132,36 @@ static int escape_impl_once(msdp_handle h, int k, double tol, int maxit, double*
         std::vector<int> eo(nz);
         for (int i = 0; i < nz; ++i) eo[i] = i;
         std::sort(eo.begin(), eo.end(), [&](int a2, int b2) { return ew[a2] < ew[b2]; });
-        const int nout = std::min(k, nz);
+        // Hermitian C: every Ritz value appears twice, with coefficient vectors a and i a (a_j = cz[j] + i cz[nx + j]).  The
+        // pairs are taken in ascending order and a candidate is kept only for what it has outside the complex span of those kept
+        // before it (complex Gram-Schmidt on the coefficients: the columns x_j are orthonormal in the complex inner product):
+        // nx vectors, orthonormal in that product, and no eigenvalue of S reported more often than S has it.
+        std::vector<std::vector<double>> hz_keep;
+        std::vector<int> hz_idx;
+        if (herm) {
+            for (int e = 0; e < nz && (int)hz_keep.size() < nx; ++e) {
+                std::vector<double> a(nz);
+                for (int i = 0; i < nz; ++i) a[i] = EV[(size_t)i * nz + eo[e]];
+                for (int pass = 0; pass < 2; ++pass)
+                    for (const std::vector<double>& b : hz_keep) {
+                        double re = 0.0, im = 0.0;                 // b^H a
+                        for (int i = 0; i < nx; ++i) { re += b[i] * a[i] + b[nx + i] * a[nx + i]; im += b[i] * a[nx + i] - b[nx + i] * a[i]; }
+                        for (int i = 0; i < nx; ++i) { a[i] -= re * b[i] - im * b[nx + i]; a[nx + i] -= re * b[nx + i] + im * b[i]; }
+                    }
+                double nn = 0.0;
+                for (int i = 0; i < nz; ++i) nn += a[i] * a[i];
+                if (!(nn > 0.25)) continue;                        // the i-multiple of a vector already kept
+                nn = 1.0 / sqrt(nn);
+                for (int i = 0; i < nz; ++i) a[i] *= nn;
+                hz_keep.push_back(a); hz_idx.push_back(eo[e]);
+            }
+        }
+        const int nout = herm ? std::min(k, (int)hz_keep.size()) : std::min(k, nz);
         std::vector<double> cz(nz);
         for (int t = 0; t < k; ++t) {
             if (t < nout) {
-                lam_out[t] = ew[eo[t]];
-                for (int i = 0; i < nz; ++i) cz[i] = EV[(size_t)i * nz + eo[t]];
+                lam_out[t] = ew[herm ? hz_idx[t] : eo[t]];
+                for (int i = 0; i < nz; ++i) cz[i] = herm ? hz_keep[t][i] : EV[(size_t)i * nz + eo[t]];
                 ESC_HIP(msdp_memcpy_async(c.hbuf, cz.data(), nz * sizeof(double), hipMemcpyHostToDevice, h->stream));
                 ESC_HIP(hipMemsetAsync(w, 0, n * sizeof(double), h->stream));
                 hipLaunchKernelGGL(k_multiaxpy, gr, bl, 0, h->stream, n, nz, Z, (int64_t)n, c.hbuf, 1.0, w);

@@ -55,7 +55,7 @@ __device__ __forceinline__ void lr_add(const Dev& d, int row, int sub, const dou
 }
 
 // cost + Riemannian gradient at Y[slot] (gather source: d.full holds all rows of Y[slot]).
-template <int LPR, int NCH, bool ELL, bool LR = false>
+template <int LPR, int NCH, bool ELL, bool LR = false, bool HZ = false>
 __device__ __forceinline__ void costgrad_sparse_obl_body(const Dev& d, int slot) {
     __shared__ double sh[3 * MSDP_WAVES];
     if (d.ctl->done) return;
@@ -93,7 +93,8 @@ __device__ __forceinline__ void costgrad_sparse_obl_body(const Dev& d, int slot)
                 const int col = 2 * sub + ch * 2 * LPR;
                 y[ch] = (col < d.ld) ? ld2(Yl + (int64_t)row * d.ld + col) : make_double2(0.0, 0.0);
             }
-            spmm_row<LPR, NCH, ELL>(d, row, sub, Xf, acc);
+            if constexpr (HZ) spmm_row_herm<LPR, NCH, ELL>(d, row, sub, Xf, acc);     // complex values: acc += c * x per double2
+            else spmm_row<LPR, NCH, ELL>(d, row, sub, Xf, acc);
             if constexpr (LR) lr_add<LPR, NCH, TLDS>(d, row, sub, Tlr, acc);
             double dot = 0.0;
 #pragma unroll
@@ -117,7 +118,7 @@ __device__ __forceinline__ void costgrad_sparse_obl_body(const Dev& d, int slot)
 }
 
 // Hess-vec: Hmd = proj-fused (C*md - Y.*rowdot(Y, C*md) - md.*eG), partial <md, Hmd>.
-template <int LPR, int NCH, bool ELL, bool LR = false>
+template <int LPR, int NCH, bool ELL, bool LR = false, bool HZ = false>
 __device__ __forceinline__ void hess_sparse_obl_body(const Dev& d) {
     __shared__ double sh[3 * MSDP_WAVES];
     if (!d.F[0].active) return;
@@ -182,7 +183,10 @@ __device__ __forceinline__ void hess_sparse_obl_body(const Dev& d) {
             eg[q] = eG[rows[q]];
         }
 #pragma unroll
-        for (int q = 0; q < UN; ++q) spmm_row<LPR, NCH, ELL>(d, rows[q], sub, Uf, acc[q]);
+        for (int q = 0; q < UN; ++q) {
+            if constexpr (HZ) spmm_row_herm<LPR, NCH, ELL>(d, rows[q], sub, Uf, acc[q]);
+            else spmm_row<LPR, NCH, ELL>(d, rows[q], sub, Uf, acc[q]);
+        }
         if constexpr (LR) {
 #pragma unroll
             for (int q = 0; q < UN; ++q) lr_add<LPR, NCH, TLDS>(d, rows[q], sub, Tlr, acc[q]);
@@ -226,6 +230,15 @@ template <int LPR, int NCH>
 __global__ __launch_bounds__(MSDP_BLOCK) void k_hess_splr_obl(Dev d) { hess_sparse_obl_body<LPR, NCH, false, true>(d); }
 template <int LPR, int NCH>
 __global__ __launch_bounds__(MSDP_BLOCK) void k_hess_splr_ell_obl(Dev d) { hess_sparse_obl_body<LPR, NCH, true, true>(d); }
+// COST_HERM: the same bodies with the complex gather (spmm_row_herm); the row dots are Re<.,.> on C^p, eG stays a real n-vector
+template <int LPR, int NCH>
+__global__ __launch_bounds__(MSDP_BLOCK) void k_costgrad_herm_obl(Dev d, int slot) { costgrad_sparse_obl_body<LPR, NCH, false, false, true>(d, slot); }
+template <int LPR, int NCH>
+__global__ __launch_bounds__(MSDP_BLOCK) void k_costgrad_herm_ell_obl(Dev d, int slot) { costgrad_sparse_obl_body<LPR, NCH, true, false, true>(d, slot); }
+template <int LPR, int NCH>
+__global__ __launch_bounds__(MSDP_BLOCK) void k_hess_herm_obl(Dev d) { hess_sparse_obl_body<LPR, NCH, false, false, true>(d); }
+template <int LPR, int NCH>
+__global__ __launch_bounds__(MSDP_BLOCK) void k_hess_herm_ell_obl(Dev d) { hess_sparse_obl_body<LPR, NCH, true, false, true>(d); }
 
 // ------------------------------------------------------------------ tCG kernels
 // tCG.m:102-157: eta=0, Heta=0, r=grad, mdelta=r, scalars.
@@ -703,6 +716,9 @@ int msdp_launch_costgrad(msdp_handle h, int slot) {
         if ((rc = msdp_lowrank_project(h, h->d.full))) return rc;      // T = diag(s) V' Y[slot], unconditionally
         if (h->d.ellW > 0) DISPATCH_LPR(k_costgrad_splr_ell_obl, h, h->d, slot);
         else DISPATCH_LPR(k_costgrad_splr_obl, h, h->d, slot);
+    } else if (h->d.costkind == COST_HERM) {
+        if (h->d.ellW > 0) DISPATCH_LPR(k_costgrad_herm_ell_obl, h, h->d, slot);
+        else DISPATCH_LPR(k_costgrad_herm_obl, h, h->d, slot);
     } else if (h->d.costkind == COST_DENSE) {
         rc = msdp_dense_costgrad(h, slot);
         if (rc) return rc;
@@ -725,6 +741,9 @@ int msdp_launch_hess(msdp_handle h) {
         if ((rc = msdp_lowrank_project(h, h->d.full))) return rc;      // T = diag(s) V' mdelta, unconditionally
         if (h->d.ellW > 0) DISPATCH_LPR(k_hess_splr_ell_obl, h, h->d);
         else DISPATCH_LPR(k_hess_splr_obl, h, h->d);
+    } else if (h->d.costkind == COST_HERM) {
+        if (h->d.ellW > 0) DISPATCH_LPR(k_hess_herm_ell_obl, h, h->d);
+        else DISPATCH_LPR(k_hess_herm_obl, h, h->d);
     } else if (h->d.costkind == COST_DENSE) {
         rc = msdp_dense_hess(h);
         if (rc) return rc;

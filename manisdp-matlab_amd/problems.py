@@ -1201,3 +1201,27 @@ def modularity(A, gamma=1.0):
     if two_m <= 0.0:
         raise ValueError("modularity: the graph has no edges")
     return SparsePlusLowRank(-A, d, [float(gamma) / two_m])
+
+
+def phase_synchronization(n, degree, sigma, rng):
+    """Phase (angular) synchronisation on a circulant measurement graph: recover unit-modulus z from noisy relative phases
+    ``z_i conj(z_j) + sigma w_ij``.  Returns ``(C, z)``: the complex Hermitian cost (CSR, zero diagonal) of
+    ``min <C, X>, X Hermitian PSD, X_ii = 1`` and the planted phases.  Definition, in draw order: ``z = exp(2 pi i
+    rng.random(n))``; for d = 1 .. degree/2 the directed edges i -> (i + d^2 + 1) mod n, all d concatenated, self-loops
+    dropped (m edges); ``w = (rng.standard_normal(m) + 1j rng.standard_normal(m)) / sqrt(2)``, the real draw first; H from
+    the entries ``z_i conj(z_j) + sigma w``, then ``H += H^H``; ``C = -H``."""
+    n = int(n)
+    z = np.exp(2j * np.pi * rng.random(n))
+    i = np.concatenate([np.arange(n) for _ in range(1, int(degree) // 2 + 1)] or [np.zeros(0, dtype=np.int64)])
+    j = np.concatenate([(np.arange(n) + d * d + 1) % n for d in range(1, int(degree) // 2 + 1)] or [np.zeros(0, dtype=np.int64)])
+    keep = i != j
+    i, j = i[keep], j[keep]
+    m = i.size
+    wr = rng.standard_normal(m)
+    wi = rng.standard_normal(m)
+    w = (wr + 1j * wi) / np.sqrt(2.0)
+    H = sp.coo_matrix((z[i] * np.conj(z[j]) + float(sigma) * w, (i, j)), shape=(n, n)).tocsr()
+    H = H + H.conj().T
+    C = sp.csr_matrix(-H)
+    C.sort_indices()
+    return C, z

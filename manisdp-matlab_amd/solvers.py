@@ -264,6 +264,8 @@ def _onlyunitdiag_impl(C, options=None, verbose=True, rng=None):
     o = dict(options or {})
     for k, v in DEFAULTS["onlyunitdiag"].items():
         o.setdefault(k, v)
+    if getattr(C, "dtype", None) is not None and np.dtype(C.dtype).kind == "c":
+        return _onlyunitdiag_hermitian_impl(C, o, verbose, rng)     # complex C: the Hermitian problem (real C: untouched below)
     escape_rr = _escape_rr_option(o)                       # (a bad value is refused before anything is built)
     rounding = _round_option(o)
     dense_max = int(o.get("dense_eig_max", 3000))          # the host eig(S) is allowed up to this order (options['eig'] = 'host') ...
@@ -474,6 +476,116 @@ def _onlyunitdiag_impl(C, options=None, verbose=True, rng=None):
         data["status"] = 1
         _say(verbose, "Iteration maximum is reached!")
     _say(verbose, "ManiSDP: optimum = %0.8f, time = %0.2fs" % (obj, time.time() - t0))
+    return Y, obj, data
+
+
+def _onlyunitdiag_hermitian_impl(C, o, verbose, rng):
+    """ManiSDP_onlyunitdiag for a complex Hermitian C:  min <C, X>  s.t. X Hermitian PSD, X_ii = 1  (phase synchronisation,
+    unimodular quadratic programmes; manopt's elliptope_SDP_complex).  The algorithm, the defaults and the option names are
+    those of ManiSDP_onlyunitdiag.m; the algebra is complex: the factor Y is n x p complex with rows of unit modulus sum,
+    z = Re sum((C Y) .* conj(Y), 2), the rank decision comes from Y^H Y, the cut is Y Q(:, 1:r), widening is [Y, alpha v] with
+    the rows renormalised, X = Y Y^H.  ``o``: the options with the defaults filled in.  Every refusal comes before the first
+    library call."""
+    Csp = _lib.hermitian_csc(sp.csc_matrix(C) if not sp.issparse(C) else C).tocsr()   # ValueError unless C == C^H exactly
+    for name, what in (("round", "+1/-1 rounding belongs to the real problem"), ("comm", "a single-rank solve is needed")):
+        if o.get(name) is not None:
+            raise ValueError(f"options[{name!r}] is not available for a complex Hermitian C: {what}")
+    if o["line_search"] == 1:
+        raise ValueError("options['line_search'] = 1 is not available for a complex Hermitian C")
+    if o.get("device_factor"):
+        raise ValueError("options['device_factor'] is not available for a complex Hermitian C: the rank cut stays on the host")
+    dense_max = int(o.get("dense_eig_max", 3000))
+    dense_default = int(o.get("dense_eig_default", 600))
+    dense_X_max = int(o.get("dense_X_max", 4000))
+    rng = rng or np.random.default_rng(0)
+    n = Csp.shape[0]
+    eig_mode = o.get("eig", "host" if n <= dense_default else "device")
+    if eig_mode not in ("host", "device"):
+        raise ValueError(f"options['eig'] must be 'host' or 'device' for a complex Hermitian C, not {eig_mode!r}")
+    _say(verbose, "ManiSDP is starting...")
+    _say(verbose, f"SDP size: n = {n}, m = {n} (complex Hermitian)")
+    p = int(o["p0"])
+    delta = int(o["delta"])
+    Y = o.get("Y0", None)
+    if Y is None:
+        Y = rng.standard_normal((n, p)) + 1j * rng.standard_normal((n, p))
+        Y /= np.sqrt(np.sum(np.abs(Y) ** 2, axis=1, keepdims=True))
+    Y = np.ascontiguousarray(Y, dtype=np.complex128)
+    p = Y.shape[1]
+    h = _lib.Handle.onlyunitdiag_hermitian(Csp, pcap=max(32, p + 2 * delta))
+    for name, value in (o.get("device_options") or {}).items():
+        h.set_option(name, int(value))
+    topts = _rtr_opts(o)
+    data = {"status": 0, "hessvecs": 0, "cost_evals": 0, "rejected": 0, "rtr_seconds": 0.0, "eig_seconds": 0.0, "log": []}
+    t0 = time.time()
+    dinf0 = None
+    obj = dinf = gradnorm = z = None
+    certified = True
+    Y_eval = Y
+    try:
+        for it in range(1, int(o["AL_maxiter"]) + 1):      # :38
+            h.set_point(Y)
+            st = h.rtr(topts)                              # :43
+            data["rtr_seconds"] += st.seconds
+            data["hessvecs"] += st.hessvecs
+            data["cost_evals"] += st.cost_evals
+            data["rejected"] += st.rejected
+            gradnorm = st.gradnorm
+            Y = h.get_point()
+            Y_eval = Y
+            z = h.get_z()                                  # :46-47  z = Re sum((C Y) .* conj(Y), 2)
+            obj = float(np.sum(z))
+            t1 = time.time()
+            certified = True
+            if eig_mode == "host":
+                dS, vS, nneg = _extreme_eigs_host(Csp - sp.diags(z), delta, dense_max)    # eigh of the complex S
+                lam_min, lam_max = dS[0], dS[-1]
+            else:
+                lam, vS, lam_max, _, certified = _device_escape(
+                    h, lambda tol, maxit: h.escape_eigs(delta, tol=tol, maxit=maxit), o, data, 1e-9, 60000)
+                lam_min = lam[0]
+                nneg = int(np.sum(lam < 0))
+                data["escape_method"] = h.escape_method()
+            data["eig_seconds"] += time.time() - t1
+            dinf = max(0.0, -lam_min) / (1.0 + lam_max)    # :51
+            if eig_mode == "device" and certified and (dinf < o["tol"] or it == int(o["AL_maxiter"])):
+                lam_v, v_v, lmax_v, certified = _verify_lambda_min(
+                    h, lambda tol, maxit: h.escape_eigs(1, tol=tol, maxit=maxit), o, data, 1e-9, 60000)
+                dinf_v = max(0.0, -lam_v) / (1.0 + lmax_v)
+                if dinf_v >= o["tol"] > dinf:
+                    vS = np.hstack([v_v, vS[:, :max(delta - 1, 0)]])
+                    nneg = max(nneg, 1)
+                dinf = dinf_v
+            Q, e, r = _thin_svd_rank(None, float(o["theta"]), gram=Y.conj().T @ Y)   # :52-54 from Y^H Y
+            _say(verbose, "Iter %d, obj:%0.8f, dinf:%0.1e, r:%d, p:%d, time:%0.2fs" % (it, obj, dinf, r, p, time.time() - t0))
+            data["log"].append((it, obj, dinf, r, p, time.time() - t0, st.hessvecs))
+            data["iters"] = it
+            if dinf < o["tol"] and certified:              # :57-60
+                _say(verbose, "Optimality is reached!")
+                break
+            if it % 20 == 0:                               # :61-69
+                if it > 50 and dinf > dinf0:
+                    data["status"] = 2
+                    _say(verbose, "Slow progress!")
+                    break
+                dinf0 = dinf
+            nne = max(min(nneg, delta), 1)                 # :74
+            if r <= p - 1:                                 # :70-73
+                Y = _rank_cut(Y, Q, e, r)
+                p = r
+            Y = np.hstack([Y, o["alpha"] * vS[:, :nne]])   # :78-83
+            Y = np.ascontiguousarray(Y / np.sqrt(np.sum(np.abs(Y) ** 2, axis=1, keepdims=True)))
+            p = p + nne
+    finally:
+        h.close()
+    Y = Y_eval
+    data.update({"Y": Y, "S": (Csp - sp.diags(z)) if z is not None else None, "z": z, "dinf": dinf, "gradnorm": gradnorm,
+                 "time": time.time() - t0, "p": Y.shape[1], "X": (Y @ Y.conj().T if n <= dense_X_max else None)})
+    if data["status"] == 0 and (dinf is None or dinf > o["tol"] or not certified):
+        data["status"] = 1
+        _say(verbose, "Iteration maximum is reached!")
+    if obj is not None:
+        _say(verbose, "ManiSDP: optimum = %0.8f, time = %0.2fs" % (obj, time.time() - t0))
     return Y, obj, data
 
 

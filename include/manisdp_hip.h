@@ -133,6 +133,31 @@ int msdp_create_onlyunitdiag_csc_lowrank(int64_t n, const int64_t* jc, const int
 int msdp_create_onlyunitdiag_csc_hermitian(int64_t n, const int64_t* jc, const int64_t* ir, const double* val, int32_t pcap,
                                            msdp_handle* out);
 
+/* The unit-block-diagonal problem  min <C, X>  s.t. X PSD of order N = n d, X_[ii] = I_d (i = 1..n)  with d = 2 or 3
+ * (synchronisation over O(d) / SO(d): rotation averaging, pose graphs).  jc / ir / val: the symmetric order-N cost matrix in
+ * CSC as for msdp_create_onlyunitdiag_csc; it is stored in block CSR of block order d (one column index per d x d block,
+ * zero-filled where the pattern covers a block in part).  d outside {2, 3} and N % d != 0 return MSDP_EINVAL; pcap > 256
+ * returns MSDP_EUNSUPPORTED, as does msdp_set_point with p > 256.
+ * The factor Y (N x p row-major, as for the other onlyunitdiag handles) is n blocks of d consecutive rows with
+ * Y_i Y_i' = I_d: manopt's stiefelstackedfactory(n, d, p), which replaces the n d (d - 1) / 2 affine constraints and the
+ * multipliers the same SDP needs through msdp_create_unitdiag.  With sym(M) = (M + M') / 2 and f = <C, Y Y'> / 2:
+ *   msdp_cost      f;   Lambda_i = sym((C Y)_i Y_i'),  S = C - blockdiag(Lambda),  <C, X> = sum_i tr Lambda_i = 2 f
+ *   msdp_rgrad     (C Y)_i - Lambda_i Y_i                                     (stiefelstackedfactory.m:81-87)
+ *   msdp_hessvec   W_i - sym(W_i Y_i') Y_i  with  W = C U - blockdiag(Lambda) U   (:93-101)
+ *   msdp_proj      Z_i - sym(Z_i Y_i') Y_i                                    (:81-89)
+ *   msdp_retr      the polar factor (A_i A_i')^(-1/2) A_i of A_i = Y_i + U_i  (:103-117)
+ * The trust-region radius defaults to Delta_bar = sqrt(n (p d - d (d + 1) / 2)) (:43,53), Delta0 = Delta_bar / 8.
+ * msdp_set_point takes any N x p array: p < d and blocks that are not orthonormal are the caller's business.
+ * msdp_get_z returns the N diagonal entries of the Lambda_i (sum = <C, X>), msdp_get_blockmult the blocks themselves.
+ * msdp_rtr runs the generic per-iteration path; msdp_escape_eigs the Lanczos path on S (span(Y) deflated at near-stationary
+ * points, as for the scalar kind: the columns of Y are N-vectors with S Y = 0 at a critical point).
+ * MSDP_EUNSUPPORTED: every communicator, msdp_round_hyperplane, msdp_factor_gram / _rotate / _append (the rank cut and the
+ * re-orthonormalisation of the blocks stay on the host), msdp_linesearch_cost / _accept. */
+int msdp_create_onlyunitblockdiag_csc(int64_t N, int32_t d, const int64_t* jc, const int64_t* ir, const double* val, int32_t pcap,
+                                      msdp_handle* out);
+/* Lam: n d d doubles, block i = Lambda_i row-major (symmetric), at the resident point.  Other handles: MSDP_EUNSUPPORTED. */
+int msdp_get_blockmult(msdp_handle h, double* Lam);
+
 /* Pre-sharded synthetic dense problem (BASELINE config 5: n = 100000, p = 64 over 8 GPUs; the full C would be
  * 80 GB): rank `rank` of `nranks` fills ITS rows of a dense symmetric C on the device from a counter-based
  * generator; msdp_synthetic_dense_entry is the same generator on the host (parity tests). */

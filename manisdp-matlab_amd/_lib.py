@@ -60,6 +60,8 @@ SIGNATURES = {
     "msdp_create_onlyunitdiag_csc": (C.c_int, [C.c_int64, _i64p, _i64p, _dp, C.c_int32, _P(C.c_void_p)]),
     "msdp_create_onlyunitdiag_csc_lowrank": (C.c_int, [C.c_int64, _i64p, _i64p, _dp, C.c_int32, _dp, _dp, C.c_int32, _P(C.c_void_p)]),
     "msdp_create_onlyunitdiag_csc_hermitian": (C.c_int, [C.c_int64, _i64p, _i64p, _dp, C.c_int32, _P(C.c_void_p)]),
+    "msdp_create_onlyunitblockdiag_csc": (C.c_int, [C.c_int64, C.c_int32, _i64p, _i64p, _dp, C.c_int32, _P(C.c_void_p)]),
+    "msdp_get_blockmult": (C.c_int, [C.c_void_p, _dp]),
     "msdp_create_onlyunitdiag_dense": (C.c_int, [C.c_int64, _dp, C.c_int32, _P(C.c_void_p)]),
     "msdp_create_onlyunitdiag_dense_synthetic": (C.c_int, [C.c_int64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32,
                                                           _P(C.c_void_p)]),
@@ -272,6 +274,7 @@ class Handle:
         self.n = n
         self.p = 0
         self.hermitian = False            # onlyunitdiag_hermitian: factors are complex (n, p) arrays, p counts complex columns
+        self.blk = 0                      # onlyunitblockdiag: the block order d (0: no blocks)
         self._lib = load()
 
     # ---- construction
@@ -335,6 +338,28 @@ class Handle:
                                                           C.byref(out)))
         h = cls(out.value, KIND_ONLYUNITDIAG, n)
         h.hermitian = True
+        return h
+
+    @classmethod
+    def onlyunitblockdiag(cls, Cmat, d, pcap=32):
+        """min <C, X> over PSD X of order N = n d with identity diagonal blocks X_[ii] = I_d, d = 2 or 3
+        (msdp_create_onlyunitblockdiag_csc): C a symmetric scipy sparse (or dense) N x N matrix.  Factors are (N, p) arrays whose
+        blocks of d consecutive rows are orthonormal; get_z returns the N diagonal entries of the multiplier blocks, get_blockmult
+        the blocks.  d, N % d and pcap <= 256 are checked by the library."""
+        import scipy.sparse as sp
+        lib = load()
+        out = C.c_void_p()
+        Cc = sp.csc_matrix(Cmat, dtype=np.float64)
+        Cc.sum_duplicates()
+        Cc.sort_indices()
+        N = Cc.shape[0]
+        jc = np.ascontiguousarray(Cc.indptr, dtype=np.int64)
+        ir = np.ascontiguousarray(Cc.indices, dtype=np.int64)
+        val = np.ascontiguousarray(Cc.data, dtype=np.float64)
+        _check(lib.msdp_create_onlyunitblockdiag_csc(N, int(d), jc.ctypes.data_as(_i64p), ir.ctypes.data_as(_i64p), _dptr(val),
+                                                     pcap, C.byref(out)))
+        h = cls(out.value, KIND_ONLYUNITDIAG, N)
+        h.blk = int(d)
         return h
 
     @classmethod
@@ -641,6 +666,13 @@ class Handle:
         z = np.zeros(self.n)
         _check(self._lib.msdp_get_z(self._h, _dptr(z)))
         return z
+
+    def get_blockmult(self):
+        """The multiplier blocks Lambda_i = sym((C Y)_i Y_i') of an onlyunitblockdiag handle: an (n, d, d) array."""
+        nb = self.n // self.blk if self.blk else 0
+        Lam = np.zeros((max(nb, 1), max(self.blk, 1), max(self.blk, 1)))
+        _check(self._lib.msdp_get_blockmult(self._h, _dptr(Lam)))
+        return Lam
 
     def get_z_all(self):
         z = np.zeros(self.n)

@@ -19,6 +19,12 @@ static void algo_cost(msdp_handle h, double* bytes, double* flops) {
         // p = the real width: complex values of 16 bytes, a complex multiply-add (4 fma) per entry and double2
         *bytes = (double)d.nnz * 20.0 + (n + 1) * 4.0 + 24.0 * n * p + 8.0 * n;
         *flops = 4.0 * (double)d.nnz * p + 5.0 * n * p;
+    } else if (d.costkind == COST_BLOCK) {
+        // d.nnz = stored values (d^2 per block entry, 8 bytes each), one 4-byte column index per d^2 of them; the multiplier
+        // blocks (d values per row) in place of eG; 2 d n p flops more for Lambda U and as many for sym(W Y') and its product
+        const double dd = (double)d.blk * d.blk;
+        *bytes = (double)d.nnz * (8.0 + 4.0 / dd) + (d.nb + 1) * 4.0 + 24.0 * n * p + 8.0 * n * d.blk;
+        *flops = 2.0 * (double)d.nnz * p + (1.0 + 6.0 * d.blk) * n * p;
     } else if (d.costkind == COST_DENSE) {
         *bytes = 8.0 * n * (double)d.n + 24.0 * n * p;
         *flops = 2.0 * n * (double)d.n * p;

@@ -73,12 +73,14 @@ enum { P_F = 0, P_GG = 1, P_DHD = 2, P_S1 = 3, P_S2 = 4, P_S3 = 5, P_RD = 6, P_A
        // sphere Hess-vec, fused form (msdp_affine.hip, k_sddmm1 mode 2): <U, G>, <U, Y>, sum_k w_k (A x)_k
        P_T1 = 9, P_T2 = 10, P_T3 = 11 };
 
-enum { MANI_OBLIQUE = 0, MANI_SPHERE = 1, MANI_EUCLID = 2 };
+enum { MANI_OBLIQUE = 0, MANI_SPHERE = 1, MANI_EUCLID = 2,
+       MANI_STIEFEL = 3 };   // stacked Stiefel manifold: the d rows of a block are orthonormal (msdp_stiefel.hip)
 enum { COST_SPARSE = 0, COST_DENSE = 1, COST_AFFINE = 2,
        COST_SPLR = 3,     // C = Cs + V diag(s) V': the sparse rows below plus the low-rank fields lr* (msdp_lowrank.hip)
-       COST_HERM = 4 };   // C = A + iB Hermitian: rowptr / colind below with the complex values hzv / hzell (msdp_hermitian.hip); cval and ellv are null
+       COST_HERM = 4,     // C = A + iB Hermitian: rowptr / colind below with the complex values hzv / hzell (msdp_hermitian.hip); cval and ellv are null
+       COST_BLOCK = 5 };  // C in block CSR of block order d.blk (brp / bci / bval below, msdp_stiefel.hip); rowptr, colind, cval and the ELL copy are null
 // the rows of the cost matrix are sparse rows (no dense n x n operand exists or is reserved)
-static inline bool msdp_cost_sparse_rows(int costkind) { return costkind == COST_SPARSE || costkind == COST_SPLR || costkind == COST_HERM; }
+static inline bool msdp_cost_sparse_rows(int costkind) { return costkind == COST_SPARSE || costkind == COST_SPLR || costkind == COST_HERM || costkind == COST_BLOCK; }
 
 // Everything a kernel needs, passed by value.
 struct Dev {
@@ -176,6 +178,14 @@ struct Dev {
     // (beside ellc, padded with (row, 0 + 0i)).  A factor row of complex width p is its real view of 2p doubles: one double2 per
     // complex entry, so d.p = 2p and d.ld = 2p on such a handle
     const double2* hzv; const double2* hzell;
+    // COST_BLOCK / MANI_STIEFEL (msdp_stiefel.hip): block order blk = d in {2, 3} and block count nb = n / d; the cost matrix in
+    // block CSR -- block row i holds the entries brp[i] .. brp[i + 1], entry k the block column bci[k] and the d x d values
+    // bval[k * d * d ..] row-major (zero where the caller's pattern is partial); Lam[slot] = the multiplier blocks
+    // Lambda_i = sym((C Y)_i Y_i') of the point in that slot (nb * d * d doubles, each block row-major and symmetric); eG[slot]
+    // carries their diagonals, row by row
+    int blk, nb;
+    const int* brp; const int* bci; const double* bval;
+    double* Lam[2];
 };
 #define MSDP_LR_PARTS 128         // workgroups (= partial sums per entry of T) of the low-rank projection
 
@@ -458,6 +468,15 @@ int msdp_lowrank_sv_add(msdp_handle h, const double* v, double* w);   // w += V 
 int msdp_hermitian_setup(msdp_handle h, const double* val);   // the complex CSR / ELL values of a COST_HERM handle (val: nnz (re, im) pairs in CSC order)
 int msdp_hermitian_sv(msdp_handle h, const double* z, const double* v, double* w);   // w = C v - z .* v, v and w n complex entries (re, im interleaved)
 int msdp_hermitian_jcopy(msdp_handle h, const double* v, double* w);                 // w = i * v: (re, im) -> (-im, re)
+// msdp_stiefel.hip
+int msdp_stiefel_setup(msdp_handle h, int blk, const int64_t* jc, const int64_t* ir, const double* val);   // block CSR of a COST_BLOCK handle from the caller's CSC arrays; Lam[0..1]
+int msdp_stiefel_costgrad(msdp_handle h, int slot);           // Y[slot] -> Gr[slot], Lam[slot], eG[slot], P_F, P_GG (gather source: d.full)
+int msdp_stiefel_hess(msdp_handle h);
+int msdp_stiefel_upd2(msdp_handle h);
+int msdp_stiefel_retract(msdp_handle h);
+int msdp_stiefel_proj(msdp_handle h, const double* Y, const double* U, double* V);
+int msdp_stiefel_retr(msdp_handle h, const double* Y, const double* U, double* Z, double alpha);
+int msdp_stiefel_sv(msdp_handle h, const double* Lam, const double* v, double* w);   // w = C v - blockdiag(Lam) v for vectors of n entries (the escape's S*v)
 // msdp_trip1.hip, msdp_trip2.hip
 int msdp_trip1_ok(msdp_handle h);                             // sharded trip with one all-reduce applies to this handle
 int msdp_launch_trip1_init(msdp_handle h);

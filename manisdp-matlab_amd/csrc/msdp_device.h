@@ -375,3 +375,186 @@ __device__ __forceinline__ void spmm_row_herm(const Dev& d, int row, int sub, co
         }
     }
 }
+
+// ------------------------------------------------------------------ stacked Stiefel manifold (MANI_STIEFEL, msdp_stiefel.hip)
+// The gather of a block row of a block-CSR cost matrix (COST_BLOCK): a lane group owns the D rows of block `blk`, NCH double2
+// each.  Per entry the D x D values are read once (the same addresses in every lane of the group: one L1 line), the D
+// contiguous rows of the neighbour block are gathered once and each is used D times: acc[a] += sum_b c[a][b] * x[b].
+// Entries in ascending block-column order, b ascending inside an entry.  UN entries are in flight together (1 where the caller
+// holds three vectors of the block in registers and D = 3: two would spill at 128 registers per lane).
+template <int D, int LPR, int NCH, int UN = 2>
+__device__ __forceinline__ void spmm_block(const Dev& d, int blk, int sub, const double* __restrict__ X,
+                                           double2 (&acc)[D][NCH]) {
+    const int start = d.brp[blk], end = d.brp[blk + 1];
+    const int* __restrict__ ci = d.bci;
+    const double* __restrict__ cv = d.bval;
+#pragma unroll UN
+    for (int k = start; k < end; ++k) {
+        const int j = ci[k];
+        double c[D][D];
+#pragma unroll
+        for (int a = 0; a < D; ++a)
+#pragma unroll
+            for (int b = 0; b < D; ++b) c[a][b] = cv[(int64_t)k * (D * D) + a * D + b];
+        const double* src = X + (int64_t)j * D * d.ld + 2 * sub;
+        double2 x[D][NCH];
+#pragma unroll
+        for (int b = 0; b < D; ++b)
+#pragma unroll
+            for (int ch = 0; ch < NCH; ++ch)
+                x[b][ch] = (2 * sub + ch * 2 * LPR < d.ld) ? ld2(src + (int64_t)b * d.ld + ch * 2 * LPR) : make_double2(0.0, 0.0);
+#pragma unroll
+        for (int a = 0; a < D; ++a)
+#pragma unroll
+            for (int b = 0; b < D; ++b)
+#pragma unroll
+                for (int ch = 0; ch < NCH; ++ch) {
+                    acc[a][ch].x = fma(c[a][b], x[b][ch].x, acc[a][ch].x);
+                    acc[a][ch].y = fma(c[a][b], x[b][ch].y, acc[a][ch].y);
+                }
+    }
+}
+
+// T = sym(A B') of two D-row blocks held by a lane group: T[a][b] = (<A_a, B_b> + <A_b, B_a>) / 2, D (D + 1) / 2 group sums;
+// the same bits in every lane of the group
+template <int D, int LPR, int NCH>
+__device__ __forceinline__ void msdp_block_symdot(const double2 (&A)[D][NCH], const double2 (&B)[D][NCH], double (&T)[D][D]) {
+#pragma unroll
+    for (int a = 0; a < D; ++a)
+#pragma unroll
+        for (int b = a; b < D; ++b) {
+            double s = 0.0;
+#pragma unroll
+            for (int ch = 0; ch < NCH; ++ch) {
+                s += A[a][ch].x * B[b][ch].x + A[a][ch].y * B[b][ch].y;
+                if (b != a) s += A[b][ch].x * B[a][ch].x + A[b][ch].y * B[a][ch].y;
+            }
+            s = msdp_group_sum<LPR>(s);
+            T[a][b] = T[b][a] = (b != a) ? 0.5 * s : s;
+        }
+}
+
+// R = G^(-1/2) of a symmetric positive definite D x D matrix in registers (the polar retraction: G = A A' of a block A = Y + eta,
+// G = I + eta eta' >= I for tangent eta).  Symmetric eigen-decomposition by Jacobi rotations -- for D = 2 a single rotation is
+// the closed form; D = 3 runs cyclic sweeps until the off-diagonal part is below rounding (|off|^2 <= 1e-32 |diag|^2), at most
+// MSDP_JACOBI_SWEEPS of them (quadratic convergence: four or five in practice).  Every index is a compile-time constant after
+// unrolling: the matrices stay in registers.
+#define MSDP_JACOBI_SWEEPS 12
+template <int D>
+__device__ __forceinline__ void msdp_sym_invsqrt(const double (&G)[D][D], double (&R)[D][D]) {
+    double A[D][D], V[D][D];
+#pragma unroll
+    for (int a = 0; a < D; ++a)
+#pragma unroll
+        for (int b = 0; b < D; ++b) { A[a][b] = G[a][b]; V[a][b] = (a == b) ? 1.0 : 0.0; }
+    for (int sweep = 0; sweep < (D == 2 ? 1 : MSDP_JACOBI_SWEEPS); ++sweep) {
+        if (D > 2) {
+            double off = 0.0, dg = 0.0;
+#pragma unroll
+            for (int a = 0; a < D; ++a) {
+                dg += A[a][a] * A[a][a];
+#pragma unroll
+                for (int b = a + 1; b < D; ++b) off += A[a][b] * A[a][b];
+            }
+            if (off <= 1e-32 * dg) break;
+        }
+#pragma unroll
+        for (int p = 0; p < D; ++p)
+#pragma unroll
+            for (int q = p + 1; q < D; ++q) {
+                const double apq = A[p][q];
+                if (apq != 0.0) {
+                    const double th = (A[q][q] - A[p][p]) / (2.0 * apq);
+                    const double t = copysign(1.0, th) / (fabs(th) + sqrt(th * th + 1.0));
+                    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+                    A[p][p] -= t * apq; A[q][q] += t * apq;
+                    A[p][q] = A[q][p] = 0.0;
+#pragma unroll
+                    for (int r = 0; r < D; ++r) {
+                        if (r != p && r != q) {
+                            const double arp = A[r][p], arq = A[r][q];
+                            A[r][p] = A[p][r] = c * arp - s * arq;
+                            A[r][q] = A[q][r] = s * arp + c * arq;
+                        }
+                        const double vrp = V[r][p], vrq = V[r][q];
+                        V[r][p] = c * vrp - s * vrq;
+                        V[r][q] = s * vrp + c * vrq;
+                    }
+                }
+            }
+    }
+    double is[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) is[k] = 1.0 / sqrt(A[k][k]);
+#pragma unroll
+    for (int a = 0; a < D; ++a)
+#pragma unroll
+        for (int b = a; b < D; ++b) {
+            double s = 0.0;
+#pragma unroll
+            for (int k = 0; k < D; ++k) s += V[a][k] * is[k] * V[b][k];
+            R[a][b] = R[b][a] = s;
+        }
+}
+
+// tCG.m:227-287, the scalar part of the second update of a trip (everything k_tcg_upd2_obl decides before it touches a row):
+// model check, convergence test, loop bound, the new frame.  Returns true when a new direction mdelta = tangent(r + beta mdelta)
+// is due, with beta; false when the tCG has ended (or was not running) -- the frame and the progress word are written either
+// way.  Called by every thread of the launch; shb: 4 doubles of LDS.
+__device__ __forceinline__ bool msdp_tcg_upd2_scalars(const Dev& d, double* shb, double& beta_out) {
+    const Frame* fi = &d.F[1];
+    const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
+    const int active = fi->active;
+    const double z_r = fi->z_r, d_Pd = fi->d_Pd, e_Pd = fi->e_Pd, e_Pe = fi->e_Pe;
+    const double model_value = fi->model_value, norm_r0 = fi->norm_r0, beta0 = fi->beta, alpha = fi->alpha;
+    const int j0 = fi->j, stop0 = fi->stop, ix = fi->eta_idx;
+    if (!active) {
+        if (lead) {
+            frame_store(&d.F[0], z_r, d_Pd, e_Pd, e_Pe, model_value, norm_r0, alpha, beta0, 0, j0, stop0, ix);
+            d.ctl->tcg_running = 0;
+            msdp_publish(d, d.ctl->k, j0, 0);
+        }
+        return false;
+    }
+    const Ctl* c = d.ctl;
+    const bool bench = c->bench_mode != 0;
+    double s1, s2, r_r;
+    msdp_sum_partials3_block(d.P, P_S1, P_S2, P_S3, d.G, shb, s1, s2, r_r);
+    const double new_model = s1 + 0.5 * s2;                 // :227
+    const int j = j0 + 1;
+    if (!bench && new_model >= model_value) {               // :228
+        if (lead) {
+            frame_store(&d.F[0], z_r, d_Pd, e_Pd, e_Pe, model_value, norm_r0, alpha, beta0, 0, j, 6, ix);
+            d.ctl->tcg_running = 0;
+            msdp_publish(d, c->k, j, 0);
+        }
+        return false;
+    }
+    const int nix = ix ^ 1;                                 // :233-235 commit new_eta/new_Heta
+    const double norm_r = sqrt(r_r);
+    const double nr0t = (c->theta == 1.0) ? norm_r0 : pow(norm_r0, c->theta);   // norm_r0^theta
+    if (!bench && j >= c->mininner && norm_r <= norm_r0 * fmin(nr0t, c->kappa)) {   // :249
+        if (lead) {
+            frame_store(&d.F[0], z_r, d_Pd, e_Pd, e_Pe, new_model, norm_r0, alpha, beta0, 0, j, (c->kappa < nr0t) ? 3 : 4, nix);
+            d.ctl->tcg_running = 0;
+            msdp_publish(d, c->k, j, 0);
+        }
+        return false;
+    }
+    if (j >= c->maxinner) {                                 // loop bound :160 (stop stays 5)
+        if (lead) {
+            frame_store(&d.F[0], z_r, d_Pd, e_Pd, e_Pe, new_model, norm_r0, alpha, beta0, 0, j, stop0, nix);
+            d.ctl->tcg_running = 0;
+            msdp_publish(d, c->k, j, 0);
+        }
+        return false;
+    }
+    const double beta = r_r / z_r;                          // :272
+    if (lead) {
+        frame_store(&d.F[0], r_r, r_r + beta * beta * d_Pd /* :287 */, beta * (e_Pd + alpha * d_Pd) /* :286 */, e_Pe,
+                    new_model, norm_r0, alpha, beta, 1, j, stop0, nix);
+        msdp_publish(d, c->k, j, 1);
+    }
+    beta_out = beta;
+    return true;
+}

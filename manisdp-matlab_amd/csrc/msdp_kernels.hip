@@ -719,6 +719,8 @@ int msdp_launch_costgrad(msdp_handle h, int slot) {
     } else if (h->d.costkind == COST_HERM) {
         if (h->d.ellW > 0) DISPATCH_LPR(k_costgrad_herm_ell_obl, h, h->d, slot);
         else DISPATCH_LPR(k_costgrad_herm_obl, h, h->d, slot);
+    } else if (h->d.costkind == COST_BLOCK) {
+        if ((rc = msdp_stiefel_costgrad(h, slot))) return rc;          // block CSR on the stacked Stiefel manifold (msdp_stiefel.hip)
     } else if (h->d.costkind == COST_DENSE) {
         rc = msdp_dense_costgrad(h, slot);
         if (rc) return rc;
@@ -744,6 +746,8 @@ int msdp_launch_hess(msdp_handle h) {
     } else if (h->d.costkind == COST_HERM) {
         if (h->d.ellW > 0) DISPATCH_LPR(k_hess_herm_ell_obl, h, h->d);
         else DISPATCH_LPR(k_hess_herm_obl, h, h->d);
+    } else if (h->d.costkind == COST_BLOCK) {
+        if ((rc = msdp_stiefel_hess(h))) return rc;
     } else if (h->d.costkind == COST_DENSE) {
         rc = msdp_dense_hess(h);
         if (rc) return rc;
@@ -773,6 +777,7 @@ int msdp_launch_upd2(msdp_handle h) {
         HIPCHK(hipGetLastError());
         return 0;
     }
+    if (h->d.manifold == MANI_STIEFEL) return msdp_stiefel_upd2(h);
     return msdp_sphere_upd2(h);
 }
 
@@ -781,6 +786,10 @@ int msdp_launch_retract(msdp_handle h) {
         DISPATCH_LPR(k_retract_obl, h, h->d);
         HIPCHK(hipGetLastError());
         return msdp_allreduce_partials(h, P_RD, 1);
+    }
+    if (h->d.manifold == MANI_STIEFEL) {
+        int rc = msdp_stiefel_retract(h);
+        return rc ? rc : msdp_allreduce_partials(h, P_RD, 1);
     }
     return msdp_sphere_retract(h);
 }

@@ -1,6 +1,7 @@
 // msdp_rtr.hip -- host side of the device-resident RTR / tCG driver (msdp_rtr): which path a call takes (fused launch,
 // persistent tCG, chunk graphs, lock-step chunks, cross-rank persistent tCG) and the host loop around each.
 #include "msdp_common.h"
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -51,9 +52,11 @@ void msdp_fill_ctl(msdp_handle h, const msdp_rtr_opts* o) {
     c->psync_backoff = h->tune.psync_backoff;
     c->psync8_backoff = h->tune.psync8_backoff;
     // trustregions.m:363-372; typicaldist: pi*sqrt(n) (ManiSDP_onlyunitdiag.m:137) or pi (spherefactory.m:111)
-    // ... or sqrt(n*p) (euclideanfactory.m:57)
+    // ... or sqrt(n*p) (euclideanfactory.m:57) or sqrt(dim) = sqrt(nb (p d - d (d + 1) / 2)) (stiefelstackedfactory.m:43,53)
+    const double stf_dim = (double)h->d.nb * ((double)h->d.p * h->d.blk - 0.5 * h->d.blk * (h->d.blk + 1));
     const double typical = (h->d.manifold == MANI_OBLIQUE) ? M_PI * sqrt((double)h->d.n)
-                           : (h->d.manifold == MANI_EUCLID ? sqrt((double)h->d.n * (double)h->d.p) : M_PI);
+                           : (h->d.manifold == MANI_EUCLID ? sqrt((double)h->d.n * (double)h->d.p)
+                           : (h->d.manifold == MANI_STIEFEL ? sqrt(std::max(stf_dim, 1.0)) : M_PI));
     c->Delta_bar = (o->Delta_bar > 0) ? o->Delta_bar : typical;
     c->Delta0 = (o->Delta0 > 0) ? o->Delta0 : c->Delta_bar / 8.0;
 }

@@ -29,6 +29,7 @@ __all__ = [
     "read_gset", "gset_laplacian", "maxcut_cost_matrix", "toroidal_grid_maxcut",
     "from_sdpa", "get_basis", "bqpmom", "qsmom", "theta_problem", "generate_hamming",
     "dense_unitdiag_cost", "vec_index",
+    "rotation_synchronization", "round_rotations", "rotation_error",
 ]
 
 
@@ -1225,3 +1226,71 @@ def phase_synchronization(n, degree, sigma, rng):
     C = sp.csr_matrix(-H)
     C.sort_indices()
     return C, z
+
+
+# --------------------------------------------------------------------------- rotation synchronisation
+def _to_so(M):
+    """The nearest rotation(s) to the d x d matrix / stack of matrices M (Frobenius norm): U diag(1, .., det(U V')) V'."""
+    U, _, Vt = np.linalg.svd(M)
+    s = np.sign(np.linalg.det(U @ Vt))
+    U = U.copy()
+    U[..., :, -1] *= np.where(s == 0, 1.0, s)[..., None]
+    return U @ Vt
+
+
+def rotation_synchronization(n, d, degree, sigma, seed):
+    """Synchronisation over SO(d): recover rotations R_1 .. R_n from noisy relative rotations on a connected random graph.
+    Returns ``(C, R_true, edges)``: the symmetric cost (CSR, order n d, zero diagonal blocks) of
+    ``min <C, X>, X PSD, X_[ii] = I_d``, the planted rotations (n, d, d) and the (m, 2) edge list with i < j.
+    Definition, in draw order from ``np.random.default_rng(seed)``: the ring edges {i, i + 1 mod n}; ``n (degree - 2) / 2`` chords
+    ``rng.integers(0, n, size=(.., 2))`` of which self-loops and repetitions (of the ring too) are dropped; ``R_true`` = the
+    nearest rotations to ``rng.standard_normal((n, d, d))``; per edge (sorted by (i, j)) the measurement = the nearest rotation
+    to ``R_i R_j' + sigma rng.standard_normal((m, d, d))``; ``C_[ij] = -measurement``, ``C_[ji]`` its transpose.  Without noise the
+    optimum is ``-2 m d`` at rank d."""
+    n, d = int(n), int(d)
+    rng = np.random.default_rng(seed)
+    ring = np.stack([np.arange(n), (np.arange(n) + 1) % n], axis=1)
+    nch = max(int(n * (int(degree) - 2)) // 2, 0)
+    chords = rng.integers(0, n, size=(nch, 2))
+    e = np.concatenate([ring, chords], axis=0)
+    e = np.sort(e[e[:, 0] != e[:, 1]], axis=1)
+    edges = np.unique(e, axis=0)
+    m = edges.shape[0]
+    R_true = _to_so(rng.standard_normal((n, d, d)))
+    i, j = edges[:, 0], edges[:, 1]
+    meas = R_true[i] @ np.transpose(R_true[j], (0, 2, 1)) + float(sigma) * rng.standard_normal((m, d, d))
+    meas = _to_so(meas)
+    a, b = np.meshgrid(np.arange(d), np.arange(d), indexing="ij")
+    rows = (i[:, None, None] * d + a[None]).ravel()
+    cols = (j[:, None, None] * d + b[None]).ravel()
+    H = sp.coo_matrix((meas.ravel(), (rows, cols)), shape=(n * d, n * d)).tocsr()
+    C = sp.csr_matrix(-(H + H.T))
+    C.sort_indices()
+    return C, R_true, edges
+
+
+def round_rotations(Y, d):
+    """Rotations from the factor Y (n d x p, orthonormal blocks of d rows) of the unit-block-diagonal SDP, on the host: Y is
+    restricted to its top-d right singular subspace, every d x d block replaced by its polar factor, and the determinant sign
+    fixed by the majority of the blocks (a global reflection, which the SDP cannot see); a block the majority leaves with
+    determinant -1 goes to its nearest rotation.  Returns an (n, d, d) array."""
+    Y = np.asarray(Y, dtype=np.float64)
+    d = int(d)
+    n = Y.shape[0] // d
+    _, _, Vt = np.linalg.svd(Y, full_matrices=False)
+    Z = (Y @ Vt[:d].T).reshape(n, d, d)
+    U, _, Wt = np.linalg.svd(Z)
+    R = U @ Wt
+    if np.sum(np.linalg.det(R) < 0) > n / 2:
+        R = R.copy()
+        R[:, :, -1] *= -1.0
+    return _to_so(R)
+
+
+def rotation_error(R, R_true):
+    """max_i |R_i Q - R_true_i|_F after the alignment by the orthogonal Procrustes transform Q = polar(sum_i R_i' R_true_i)
+    (the gauge of the synchronisation problem: X = R R' does not change with R -> R Q)."""
+    R, R_true = np.asarray(R), np.asarray(R_true)
+    U, _, Vt = np.linalg.svd(np.einsum("nab,nac->bc", R, R_true))
+    Q = U @ Vt
+    return float(np.max(np.linalg.norm(R @ Q - R_true, axis=(1, 2))))

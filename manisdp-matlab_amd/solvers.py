@@ -54,7 +54,8 @@ def _host_threads():
     return threadpool_limits(limits=max(1, min(ncpu, 16)))
 
 __all__ = ["ManiSDP_onlyunitdiag", "ManiSDP_unitdiag", "ManiSDP_unittrace", "ManiSDP", "ManiSDP_multiblock",
-           "ManiDSDP_unitdiag", "round_unitdiag", "DEFAULTS", "DATA_FIELDS"]
+           "ManiDSDP_unitdiag", "round_unitdiag", "ManiSDP_onlyunitblockdiag", "onlyunitblockdiag_defaults", "DEFAULTS",
+           "DATA_FIELDS"]
 
 # Option defaults of the reference's entry points: ManiSDP_onlyunitdiag.m:8-17,
 # ManiSDP_unitdiag.m:10-26, ManiSDP_unittrace.m:10-25, ManiSDP.m:9-25.
@@ -581,6 +582,158 @@ def _onlyunitdiag_hermitian_impl(C, o, verbose, rng):
     Y = Y_eval
     data.update({"Y": Y, "S": (Csp - sp.diags(z)) if z is not None else None, "z": z, "dinf": dinf, "gradnorm": gradnorm,
                  "time": time.time() - t0, "p": Y.shape[1], "X": (Y @ Y.conj().T if n <= dense_X_max else None)})
+    if data["status"] == 0 and (dinf is None or dinf > o["tol"] or not certified):
+        data["status"] = 1
+        _say(verbose, "Iteration maximum is reached!")
+    if obj is not None:
+        _say(verbose, "ManiSDP: optimum = %0.8f, time = %0.2fs" % (obj, time.time() - t0))
+    return Y, obj, data
+
+
+# =============================================================== onlyunitblockdiag
+def onlyunitblockdiag_defaults(d):
+    """The option defaults of ManiSDP_onlyunitblockdiag for block order d: those of ManiSDP_onlyunitdiag except p0 = d + 2 and
+    delta = d (see its docstring)."""
+    return dict(DEFAULTS["onlyunitdiag"], p0=int(d) + 2, delta=int(d))
+
+
+def _polar_blocks(Y, d):
+    """Every block of d rows replaced by its polar factor u v' (the nearest block with orthonormal rows)."""
+    u, _, vt = np.linalg.svd(Y.reshape(Y.shape[0] // d, d, Y.shape[1]), full_matrices=False)
+    return np.ascontiguousarray((u @ vt).reshape(Y.shape))
+
+
+def ManiSDP_onlyunitblockdiag(C, d, options=None, verbose=True, rng=None):
+    """``min <C, X>  s.t. X PSD of order N = n d, X_[ii] = I_d`` for d = 2 or 3 (synchronisation over O(d) / SO(d): rotation
+    averaging, pose graphs; problems.rotation_synchronization), on the stacked Stiefel manifold of the factor: blocks of d
+    consecutive rows of Y (N x p) are orthonormal, manopt's stiefelstackedfactory(n, d, p).  No multipliers and no penalty: the
+    constraint is the manifold, as X_ii = 1 is for ManiSDP_onlyunitdiag, whose loop, option names and printed protocol this
+    follows.  Returns (Y, obj, data); ``data["Lambda"]`` holds the multiplier blocks (n, d, d), S = C - blockdiag(Lambda).
+
+    Defaults: those of ManiSDP_onlyunitdiag except ``p0 = d + 2`` and ``delta = d`` -- both are choices (a start above the
+    rank-d solution of the noise-free problem; one escape direction per row of a block), neither is measured.  The random
+    start takes the Q factors of randn(p, d).  lambda_min / lambda_max of S come from the host for N <= dense_eig_default and
+    from the device escape, with the independent cold check before "Optimality is reached!", above that (options["eig"]).
+    The rank decision is that of the reference (Y'Y); the factor is cut to r columns only when d <= r <= p - 1, widened by
+    [Y, alpha V(:, 1:nne)], and after either step every block is re-orthonormalised on the host by its polar factor.
+    ``line_search = 1``, ``device_factor``, ``round`` and ``comm`` raise ValueError before the library is loaded."""
+    with _host_threads():
+        return _onlyunitblockdiag_impl(C, d, options, verbose, rng)
+
+
+def _onlyunitblockdiag_impl(C, d, options, verbose, rng):
+    d = int(d)
+    if d not in (2, 3):
+        raise ValueError(f"the block order d must be 2 or 3, not {d}")
+    o = dict(options or {})
+    for k, v in onlyunitblockdiag_defaults(d).items():
+        o.setdefault(k, v)
+    for name, what in (("round", "+1/-1 rounding belongs to the unit-diagonal problem (problems.round_rotations rounds rotations)"),
+                       ("comm", "a single-rank solve is needed")):
+        if o.get(name) is not None:
+            raise ValueError(f"options[{name!r}] is not available for the unit-block-diagonal problem: {what}")
+    if o["line_search"] == 1:
+        raise ValueError("options['line_search'] = 1 is not available for the unit-block-diagonal problem")
+    if o.get("device_factor"):
+        raise ValueError("options['device_factor'] is not available for the unit-block-diagonal problem: the rank cut stays on the host")
+    if C.shape[0] != C.shape[1] or C.shape[0] % d:
+        raise ValueError(f"the cost matrix must be square of an order that is a multiple of d = {d}, not {C.shape}")
+    dense_max = int(o.get("dense_eig_max", 3000))
+    dense_default = int(o.get("dense_eig_default", 600))
+    dense_X_max = int(o.get("dense_X_max", 4000))
+    N = C.shape[0]
+    nb = N // d
+    eig_mode = o.get("eig", "host" if N <= dense_default else "device")
+    if eig_mode not in ("host", "device"):
+        raise ValueError(f"options['eig'] must be 'host' or 'device' for the unit-block-diagonal problem, not {eig_mode!r}")
+    p = int(o["p0"])
+    delta = int(o["delta"])
+    Y = o.get("Y0", None)
+    if Y is None and p < d:
+        raise ValueError(f"options['p0'] = {p} is below the block order d = {d}")
+    Csp = sp.csr_matrix(C, dtype=np.float64)
+    rng = rng or np.random.default_rng(0)
+    _say(verbose, "ManiSDP is starting...")
+    _say(verbose, f"SDP size: n = {N}, m = {nb * d * (d + 1) // 2} ({nb} blocks of order {d})")
+    if Y is None:
+        Y = np.empty((nb, d, p))
+        for i in range(nb):                                # stiefelstackedfactory.m:142-150
+            Y[i] = np.linalg.qr(rng.standard_normal((p, d)))[0].T
+        Y = Y.reshape(N, p)
+    Y = np.ascontiguousarray(Y, dtype=np.float64)
+    p = Y.shape[1]
+    h = _lib.Handle.onlyunitblockdiag(Csp, d, pcap=min(256, max(32, p + 2 * delta)))
+    for name, value in (o.get("device_options") or {}).items():
+        h.set_option(name, int(value))
+    topts = _rtr_opts(o)
+    data = {"status": 0, "hessvecs": 0, "cost_evals": 0, "rejected": 0, "rtr_seconds": 0.0, "eig_seconds": 0.0, "log": []}
+    t0 = time.time()
+    dinf0 = None
+    obj = dinf = gradnorm = z = Lam = r = None
+    certified = True
+    Y_eval = Y
+    try:
+        for it in range(1, int(o["AL_maxiter"]) + 1):
+            h.set_point(Y)
+            st = h.rtr(topts)
+            data["rtr_seconds"] += st.seconds
+            data["hessvecs"] += st.hessvecs
+            data["cost_evals"] += st.cost_evals
+            data["rejected"] += st.rejected
+            gradnorm = st.gradnorm
+            Y = h.get_point()
+            Y_eval = Y
+            Lam = h.get_blockmult()                        # Lambda_i = sym((C Y)_i Y_i')
+            z = np.ascontiguousarray(np.diagonal(Lam, axis1=1, axis2=2)).ravel()
+            obj = float(np.sum(z))
+            t1 = time.time()
+            certified = True
+            if eig_mode == "host":
+                dS, vS, nneg = _extreme_eigs_host(Csp - sp.block_diag(list(Lam), format="csr"), delta, dense_max)
+                lam_min, lam_max = dS[0], dS[-1]
+            else:
+                lam, vS, lam_max, _, certified = _device_escape(
+                    h, lambda tol, maxit: h.escape_eigs(delta, tol=tol, maxit=maxit), o, data, 1e-9, 60000)
+                lam_min = lam[0]
+                nneg = int(np.sum(lam < 0))
+                data["escape_method"] = h.escape_method()
+            data["eig_seconds"] += time.time() - t1
+            dinf = max(0.0, -lam_min) / (1.0 + lam_max)
+            if eig_mode == "device" and certified and (dinf < o["tol"] or it == int(o["AL_maxiter"])):
+                lam_v, v_v, lmax_v, certified = _verify_lambda_min(
+                    h, lambda tol, maxit: h.escape_eigs(1, tol=tol, maxit=maxit), o, data, 1e-9, 60000)
+                dinf_v = max(0.0, -lam_v) / (1.0 + lmax_v)
+                if dinf_v >= o["tol"] > dinf:
+                    vS = np.hstack([v_v, vS[:, :max(delta - 1, 0)]])
+                    nneg = max(nneg, 1)
+                dinf = dinf_v
+            Q, e, r = _thin_svd_rank(Y, float(o["theta"]))
+            _say(verbose, "Iter %d, obj:%0.8f, dinf:%0.1e, r:%d, p:%d, time:%0.2fs" % (it, obj, dinf, r, p, time.time() - t0))
+            data["log"].append((it, obj, dinf, r, p, time.time() - t0, st.hessvecs))
+            data["iters"] = it
+            if dinf < o["tol"] and certified:
+                _say(verbose, "Optimality is reached!")
+                break
+            if it % 20 == 0:
+                if it > 50 and dinf > dinf0:
+                    data["status"] = 2
+                    _say(verbose, "Slow progress!")
+                    break
+                dinf0 = dinf
+            nne = max(min(nneg, delta), 1)
+            if d <= r <= p - 1:                            # never below the block order: d orthonormal rows need d columns
+                Y = _polar_blocks(_rank_cut(Y, Q, e, r), d)
+                p = r
+            if p + nne > 256:
+                raise RuntimeError(f"the factor width would exceed the device's 256 columns (p = {p}, {nne} more)")
+            Y = _polar_blocks(np.hstack([Y, o["alpha"] * vS[:, :nne]]), d)
+            p = p + nne
+    finally:
+        h.close()
+    Y = Y_eval
+    S = (Csp - sp.block_diag(list(Lam), format="csr")) if Lam is not None else None
+    data.update({"Y": Y, "S": S, "z": z, "Lambda": Lam, "dinf": dinf, "gradnorm": gradnorm, "rank": r,
+                 "time": time.time() - t0, "p": Y.shape[1], "X": (Y @ Y.T if N <= dense_X_max else None)})
     if data["status"] == 0 and (dinf is None or dinf > o["tol"] or not certified):
         data["status"] = 1
         _say(verbose, "Iteration maximum is reached!")

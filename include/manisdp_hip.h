@@ -155,8 +155,36 @@ int msdp_create_onlyunitdiag_csc_hermitian(int64_t n, const int64_t* jc, const i
  * re-orthonormalisation of the blocks stay on the host), msdp_linesearch_cost / _accept. */
 int msdp_create_onlyunitblockdiag_csc(int64_t N, int32_t d, const int64_t* jc, const int64_t* ir, const double* val, int32_t pcap,
                                       msdp_handle* out);
-/* Lam: n d d doubles, block i = Lambda_i row-major (symmetric), at the resident point.  Other handles: MSDP_EUNSUPPORTED. */
+/* Lam: n d d doubles, block i = Lambda_i row-major (symmetric), at the resident point (a pose-graph handle: the d x d
+ * multipliers of its rotation rows).  Other handles: MSDP_EUNSUPPORTED. */
 int msdp_get_blockmult(msdp_handle h, double* Lam);
+
+/* The pose-graph problem  min <C, X>  s.t. X PSD of order N = n (d + 1), (X_[ii])_{1..d,1..d} = I_d (i = 1..n)  with d = 2 or
+ * 3 (synchronisation over SE(d), the non-marginalised form of SE-Sync / Cartan-Sync): only the leading d x d part of every
+ * diagonal block is pinned, the last row and column of a block are free.  jc / ir / val: the symmetric order-N cost matrix in
+ * CSC as for msdp_create_onlyunitblockdiag_csc, stored in block CSR of block order d + 1.  The caller is responsible for C
+ * being bounded below on the free rows (a pose-graph C is PSD).  d outside {2, 3} and N % (d + 1) != 0 return MSDP_EINVAL;
+ * pcap > 256 returns MSDP_EUNSUPPORTED, as does msdp_set_point with p > 256.
+ * The factor Y (N x p row-major) is n blocks of d rows Y_i with Y_i Y_i' = I_d followed by one free row tau_i: manopt's
+ * productmanifold of stiefelstackedfactory(n, d, p) and euclideanfactory(n, p), Frobenius metric.  With (C Y)_i = [G_i; g_i],
+ * sym(M) = (M + M') / 2 and f = <C, Y Y'> / 2:
+ *   msdp_cost      f;   Lambda_i = sym(G_i Y_i') (d x d),  S = C - blockdiag(Lambda_i (+) 0)
+ *                  <C, X> = 2 f = sum_i tr Lambda_i + sum_i <g_i, tau_i>: the dual value sum_i tr Lambda_i equals <C, X> only
+ *                  at a critical point (g = 0 there)
+ *   msdp_rgrad     [G_i - Lambda_i Y_i ; g_i]                                  (stiefelstackedfactory.m:81-87, euclideanfactory.m:38)
+ *   msdp_hessvec   W = C U - blockdiag(Lambda (+) 0) U;  rotation rows W_i - sym(W_i Y_i') Y_i, the free row of W unchanged
+ *   msdp_proj      Z_i - sym(Z_i Y_i') Y_i on the rotation rows, the identity on the free row
+ *   msdp_retr      the polar factor of Y_i + U_i (stiefelstackedfactory.m:103-117), tau_i + u_i on the free row (euclideanfactory.m:44)
+ * The trust-region radius defaults to Delta_bar = sqrt(n (p d - d (d + 1) / 2) + n p) (productmanifold.m:160-166 over
+ * stiefelstackedfactory.m:53 and euclideanfactory.m:57), Delta0 = Delta_bar / 8.
+ * msdp_get_z returns N values, the diagonal of Lambda_i followed by 0 for the free row, block by block: their sum is the dual
+ * value.  msdp_get_blockmult returns the n d x d blocks.  msdp_rtr runs the generic per-iteration path; msdp_escape_eigs the
+ * Lanczos path on S with the zero-padded multiplier (S Y = 0 at a critical point, so span(Y) is deflated as for the other
+ * kinds; for a pose-graph C the global shift 1 (x) e_{d+1} is always in the null space of S).
+ * MSDP_EUNSUPPORTED, with the kind named in msdp_last_error: every communicator, msdp_debug_shard, msdp_round_hyperplane,
+ * msdp_factor_gram / _rotate / _append, msdp_linesearch_cost / _accept. */
+int msdp_create_posegraph_csc(int64_t N, int32_t d, const int64_t* jc, const int64_t* ir, const double* val, int32_t pcap,
+                              msdp_handle* out);
 
 /* Pre-sharded synthetic dense problem (BASELINE config 5: n = 100000, p = 64 over 8 GPUs; the full C would be
  * 80 GB): rank `rank` of `nranks` fills ITS rows of a dense symmetric C on the device from a counter-based

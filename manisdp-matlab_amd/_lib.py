@@ -62,6 +62,7 @@ SIGNATURES = {
     "msdp_create_onlyunitdiag_csc_hermitian": (C.c_int, [C.c_int64, _i64p, _i64p, _dp, C.c_int32, _P(C.c_void_p)]),
     "msdp_create_onlyunitblockdiag_csc": (C.c_int, [C.c_int64, C.c_int32, _i64p, _i64p, _dp, C.c_int32, _P(C.c_void_p)]),
     "msdp_get_blockmult": (C.c_int, [C.c_void_p, _dp]),
+    "msdp_create_posegraph_csc": (C.c_int, [C.c_int64, C.c_int32, _i64p, _i64p, _dp, C.c_int32, _P(C.c_void_p)]),
     "msdp_create_onlyunitdiag_dense": (C.c_int, [C.c_int64, _dp, C.c_int32, _P(C.c_void_p)]),
     "msdp_create_onlyunitdiag_dense_synthetic": (C.c_int, [C.c_int64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32,
                                                           _P(C.c_void_p)]),
@@ -274,7 +275,8 @@ class Handle:
         self.n = n
         self.p = 0
         self.hermitian = False            # onlyunitdiag_hermitian: factors are complex (n, p) arrays, p counts complex columns
-        self.blk = 0                      # onlyunitblockdiag: the block order d (0: no blocks)
+        self.blk = 0                      # onlyunitblockdiag / posegraph: the block order of the factor and of the storage, as
+        self.efree = 0                    # Dev.blk (0: no blocks), and how many of a block's rows are free (posegraph: 1, blk = d + 1)
         self._lib = load()
 
     # ---- construction
@@ -341,11 +343,9 @@ class Handle:
         return h
 
     @classmethod
-    def onlyunitblockdiag(cls, Cmat, d, pcap=32):
-        """min <C, X> over PSD X of order N = n d with identity diagonal blocks X_[ii] = I_d, d = 2 or 3
-        (msdp_create_onlyunitblockdiag_csc): C a symmetric scipy sparse (or dense) N x N matrix.  Factors are (N, p) arrays whose
-        blocks of d consecutive rows are orthonormal; get_z returns the N diagonal entries of the multiplier blocks, get_blockmult
-        the blocks.  d, N % d and pcap <= 256 are checked by the library."""
+    def _block_csc(cls, create, Cmat, d, efree, pcap):
+        """A block-CSR handle from a symmetric scipy sparse (or dense) matrix through `create` (one of the two msdp_create_*_csc
+        calls with the signature (N, d, jc, ir, val, pcap, out)): blocks of d + efree rows, efree of them free."""
         import scipy.sparse as sp
         lib = load()
         out = C.c_void_p()
@@ -356,11 +356,28 @@ class Handle:
         jc = np.ascontiguousarray(Cc.indptr, dtype=np.int64)
         ir = np.ascontiguousarray(Cc.indices, dtype=np.int64)
         val = np.ascontiguousarray(Cc.data, dtype=np.float64)
-        _check(lib.msdp_create_onlyunitblockdiag_csc(N, int(d), jc.ctypes.data_as(_i64p), ir.ctypes.data_as(_i64p), _dptr(val),
-                                                     pcap, C.byref(out)))
+        _check(getattr(lib, create)(N, int(d), jc.ctypes.data_as(_i64p), ir.ctypes.data_as(_i64p), _dptr(val), pcap, C.byref(out)))
         h = cls(out.value, KIND_ONLYUNITDIAG, N)
-        h.blk = int(d)
+        h.blk = int(d) + int(efree)
+        h.efree = int(efree)
         return h
+
+    @classmethod
+    def onlyunitblockdiag(cls, Cmat, d, pcap=32):
+        """min <C, X> over PSD X of order N = n d with identity diagonal blocks X_[ii] = I_d, d = 2 or 3
+        (msdp_create_onlyunitblockdiag_csc): C a symmetric scipy sparse (or dense) N x N matrix.  Factors are (N, p) arrays whose
+        blocks of d consecutive rows are orthonormal; get_z returns the N diagonal entries of the multiplier blocks, get_blockmult
+        the blocks.  d, N % d and pcap <= 256 are checked by the library."""
+        return cls._block_csc("msdp_create_onlyunitblockdiag_csc", Cmat, d, 0, pcap)
+
+    @classmethod
+    def posegraph(cls, Cmat, d, pcap=32):
+        """min <C, X> over PSD X of order N = n (d + 1) whose diagonal blocks have the leading d x d part I_d, d = 2 or 3
+        (msdp_create_posegraph_csc): C a symmetric scipy sparse (or dense) N x N matrix.  Factors are (N, p) arrays of blocks of
+        d orthonormal rows followed by one free row; get_z returns N values (the diagonals of the d x d multiplier blocks, 0 for
+        the free rows: their sum is the dual value), get_blockmult the (n, d, d) blocks.  d, N % (d + 1) and pcap <= 256 are
+        checked by the library."""
+        return cls._block_csc("msdp_create_posegraph_csc", Cmat, d, 1, pcap)
 
     @classmethod
     def dense_synthetic(cls, n, seed, nranks=1, rank=0, pcap=32):
@@ -668,9 +685,11 @@ class Handle:
         return z
 
     def get_blockmult(self):
-        """The multiplier blocks Lambda_i = sym((C Y)_i Y_i') of an onlyunitblockdiag handle: an (n, d, d) array."""
+        """The multiplier blocks Lambda_i = sym((C Y)_i Y_i') of an onlyunitblockdiag handle (of a posegraph handle: of the d
+        rotation rows of every block): an (n, d, d) array."""
         nb = self.n // self.blk if self.blk else 0
-        Lam = np.zeros((max(nb, 1), max(self.blk, 1), max(self.blk, 1)))
+        d = max(self.blk - self.efree, 1)                  # the multiplier blocks are of the order of the orthonormal rows
+        Lam = np.zeros((max(nb, 1), d, d))
         _check(self._lib.msdp_get_blockmult(self._h, _dptr(Lam)))
         return Lam
 

@@ -360,7 +360,37 @@ extern "C" int msdp_create_onlyunitblockdiag_csc(int64_t N, int32_t d, const int
     if (rc) return rc;
     h->d.manifold = MANI_STIEFEL;
     h->d.costkind = COST_BLOCK;
-    if ((rc = msdp_alloc_common(h)) || (rc = msdp_stiefel_setup(h, d, jc, ir, val)) || (rc = msdp_alloc_vectors(h, pcap > 0 ? std::max(pcap, d) : 32))) {
+    if ((rc = msdp_alloc_common(h)) || (rc = msdp_stiefel_setup(h, d, 0, jc, ir, val)) || (rc = msdp_alloc_vectors(h, pcap > 0 ? std::max(pcap, d) : 32))) {
+        msdp_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return 0;
+}
+
+// The pose-graph problem, (X_[ii])_{1..d,1..d} = I_d with one free row per block (msdp_pose.hip): C of order N = n (d + 1) in
+// block CSR of block order d + 1; the manifold is productmanifold.m:160-166 over stiefelstackedfactory.m:53 and euclideanfactory.m:57
+extern "C" int msdp_create_posegraph_csc(int64_t N, int32_t d, const int64_t* jc, const int64_t* ir, const double* val,
+                                         int32_t pcap, msdp_handle* out) {
+    if (!out) { msdp_set_error("out handle pointer is null"); return MSDP_EINVAL; }
+    if (N <= 0 || N > 0x7fffffff) { msdp_set_error("matrix order N = %lld out of range", (long long)N); return MSDP_EINVAL; }
+    if (d != 2 && d != 3) { msdp_set_error("pose-graph handle: dimension d = %d (2 or 3)", d); return MSDP_EINVAL; }
+    if (N % (d + 1) != 0) { msdp_set_error("pose-graph handle: N = %lld is no multiple of the block order d + 1 = %d", (long long)N, d + 1); return MSDP_EINVAL; }
+    if (!jc || (!ir && jc[N] > 0) || (!val && jc[N] > 0)) { msdp_set_error("null sparse arrays"); return MSDP_EINVAL; }
+    const int64_t nnz = jc[N];
+    if (nnz < 0 || nnz > 0x7fffffff) { msdp_set_error("nnz(C) too large"); return MSDP_EINVAL; }
+    if (pcap > MSDP_BLOCK_PMAX) { msdp_set_error("pose-graph handle: pcap = %d exceeds the supported width of %d", pcap, MSDP_BLOCK_PMAX); return MSDP_EUNSUPPORTED; }
+    for (int64_t j = 0; j < N; ++j) {
+        if (jc[j] > jc[j + 1] || jc[j] < 0 || jc[j + 1] > nnz) { msdp_set_error("column pointers not monotone"); return MSDP_EINVAL; }
+        for (int64_t k = jc[j]; k < jc[j + 1]; ++k)
+            if (ir[k] < 0 || ir[k] >= N) { msdp_set_error("row index out of range"); return MSDP_EINVAL; }
+    }
+    msdp_handle h = nullptr;
+    int rc = new_handle(MSDP_KIND_ONLYUNITDIAG, N, &h);
+    if (rc) return rc;
+    h->d.manifold = MANI_STIEFEL;
+    h->d.costkind = COST_BLOCK;
+    if ((rc = msdp_alloc_common(h)) || (rc = msdp_stiefel_setup(h, d + 1, 1, jc, ir, val)) || (rc = msdp_alloc_vectors(h, pcap > 0 ? std::max(pcap, d) : 32))) {
         msdp_destroy(h);
         return rc;
     }
@@ -726,7 +756,7 @@ extern "C" int msdp_set_point(msdp_handle h, int32_t p, const double* Y) {
     if (p < 1 || !Y) { msdp_set_error("set_point: p = %d, Y = %p", p, (const void*)Y); return MSDP_EINVAL; }
     if (p > 1024) { msdp_set_error("factor width p = %d exceeds the supported maximum of 1024", p); return MSDP_EUNSUPPORTED; }
     Dev& d = h->d;
-    if (d.manifold == MANI_STIEFEL && p > 256) { msdp_set_error("set_point: a unit-block-diagonal handle holds factor widths up to 256 (p = %d)", p); return MSDP_EUNSUPPORTED; }
+    if (d.manifold == MANI_STIEFEL && p > MSDP_BLOCK_PMAX) { msdp_set_error("set_point: a %s handle holds factor widths up to %d (p = %d)", msdp_block_kind_name(d.efree), MSDP_BLOCK_PMAX, p); return MSDP_EUNSUPPORTED; }
     if (d.costkind == COST_HERM && (p & 1)) { msdp_set_error("set_point: a Hermitian handle takes the real view of a complex factor, an even width (p = %d)", p); return MSDP_EINVAL; }
     if (p > h->pcap) {
         int rc = msdp_alloc_vectors(h, p + 16);
@@ -773,7 +803,7 @@ static int adopt_point(msdp_handle h, int slot, int p) {
 extern "C" int msdp_factor_gram(msdp_handle h, double* G) {
     MSDP_CHECK_H(h);
     if (h->d.costkind == COST_HERM) { msdp_set_error("factor_gram: not for a Hermitian handle (the rank cut of a complex factor stays on the host)"); return MSDP_EUNSUPPORTED; }
-    if (h->d.manifold == MANI_STIEFEL) { msdp_set_error("factor_gram: not for a unit-block-diagonal handle (the rank cut and the re-orthonormalisation of the blocks stay on the host)"); return MSDP_EUNSUPPORTED; }
+    if (h->d.manifold == MANI_STIEFEL) { msdp_set_error("factor_gram: not for a %s handle (the rank cut and the re-orthonormalisation of the blocks stay on the host)", msdp_block_kind_name(h->d.efree)); return MSDP_EUNSUPPORTED; }
     if (!h->have_point || !G) { msdp_set_error("factor_gram: no resident point / null out"); return MSDP_ESTATE; }
     Dev& d = h->d;
     const int ld = d.ld, p = d.p;
@@ -793,7 +823,7 @@ extern "C" int msdp_factor_gram(msdp_handle h, double* G) {
 extern "C" int msdp_factor_rotate(msdp_handle h, int32_t r, const double* Q) {
     MSDP_CHECK_H(h);
     if (h->d.costkind == COST_HERM) { msdp_set_error("factor_rotate: not for a Hermitian handle (the rank cut of a complex factor stays on the host)"); return MSDP_EUNSUPPORTED; }
-    if (h->d.manifold == MANI_STIEFEL) { msdp_set_error("factor_rotate: not for a unit-block-diagonal handle (the rank cut and the re-orthonormalisation of the blocks stay on the host)"); return MSDP_EUNSUPPORTED; }
+    if (h->d.manifold == MANI_STIEFEL) { msdp_set_error("factor_rotate: not for a %s handle (the rank cut and the re-orthonormalisation of the blocks stay on the host)", msdp_block_kind_name(h->d.efree)); return MSDP_EUNSUPPORTED; }
     if (!h->have_point || !Q) { msdp_set_error("factor_rotate: no resident point / null Q"); return MSDP_ESTATE; }
     Dev& d = h->d;
     if (r < 1 || r > d.p) { msdp_set_error("factor_rotate: r = %d outside 1..p = %d", r, d.p); return MSDP_EINVAL; }
@@ -812,7 +842,7 @@ extern "C" int msdp_factor_rotate(msdp_handle h, int32_t r, const double* Q) {
 extern "C" int msdp_factor_append(msdp_handle h, int32_t k, const double* V, double alpha, int32_t normalize) {
     MSDP_CHECK_H(h);
     if (h->d.costkind == COST_HERM) { msdp_set_error("factor_append: not for a Hermitian handle (the rank cut of a complex factor stays on the host)"); return MSDP_EUNSUPPORTED; }
-    if (h->d.manifold == MANI_STIEFEL) { msdp_set_error("factor_append: not for a unit-block-diagonal handle (the rank cut and the re-orthonormalisation of the blocks stay on the host)"); return MSDP_EUNSUPPORTED; }
+    if (h->d.manifold == MANI_STIEFEL) { msdp_set_error("factor_append: not for a %s handle (the rank cut and the re-orthonormalisation of the blocks stay on the host)", msdp_block_kind_name(h->d.efree)); return MSDP_EUNSUPPORTED; }
     if (!h->have_point || !V) { msdp_set_error("factor_append: no resident point / null V"); return MSDP_ESTATE; }
     Dev& d = h->d;
     if (k < 1) { msdp_set_error("factor_append: k = %d", k); return MSDP_EINVAL; }
@@ -1110,14 +1140,16 @@ extern "C" int msdp_get_z(msdp_handle h, double* z) {
     return 0;
 }
 
-// The multiplier blocks Lambda_i = sym((C Y)_i Y_i') of a unit-block-diagonal handle at the resident point
+// The multiplier blocks Lambda_i = sym((C Y)_i Y_i') of a unit-block-diagonal handle at the resident point (a pose-graph handle:
+// of its rotation rows, d x d with d = blk - efree)
 extern "C" int msdp_get_blockmult(msdp_handle h, double* Lam) {
     MSDP_CHECK_H(h);
-    if (h->d.manifold != MANI_STIEFEL) { msdp_set_error("get_blockmult: only for unit-block-diagonal handles"); return MSDP_EUNSUPPORTED; }
+    if (h->d.manifold != MANI_STIEFEL) { msdp_set_error("get_blockmult: only for unit-block-diagonal and pose-graph handles"); return MSDP_EUNSUPPORTED; }
     if (!Lam) { msdp_set_error("get_blockmult: null out"); return MSDP_EINVAL; }
     int rc = msdp_ensure_state(h);
     if (rc) return rc;
-    HIPCHK(msdp_memcpy_async(Lam, h->d.Lam[msdp_host_cur(h)], (size_t)h->d.nb * h->d.blk * h->d.blk * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    const size_t lord = (size_t)(h->d.blk - h->d.efree);
+    HIPCHK(msdp_memcpy_async(Lam, h->d.Lam[msdp_host_cur(h)], (size_t)h->d.nb * lord * lord * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return 0;
 }
@@ -1139,7 +1171,7 @@ extern "C" int msdp_get_z_all(msdp_handle h, double* z) {
 // co() of the line search at retr(Y + alpha*U): for onlyunitdiag co = sum((Y*C).*Y) = 2 f.
 extern "C" int msdp_linesearch_cost(msdp_handle h, const double* U, double alpha, double* val) {
     MSDP_CHECK_H(h);
-    if (h->d.manifold == MANI_STIEFEL) { msdp_set_error("linesearch_cost: not for a unit-block-diagonal handle (its solver takes the widening step without a line search)"); return MSDP_EUNSUPPORTED; }
+    if (h->d.manifold == MANI_STIEFEL) { msdp_set_error("linesearch_cost: not for a %s handle (its solver takes the widening step without a line search)", msdp_block_kind_name(h->d.efree)); return MSDP_EUNSUPPORTED; }
     if (!h->have_point || !val) { msdp_set_error("linesearch_cost: no point / null out"); return MSDP_ESTATE; }
     int rc;
     const int cur = msdp_host_cur(h);
@@ -1168,7 +1200,7 @@ extern "C" int msdp_linesearch_cost(msdp_handle h, const double* U, double alpha
 // Adopt the retraction of Y + alpha*U as the new resident point (result of line_search).
 extern "C" int msdp_linesearch_accept(msdp_handle h) {
     MSDP_CHECK_H(h);
-    if (h->d.manifold == MANI_STIEFEL) { msdp_set_error("linesearch_accept: not for a unit-block-diagonal handle (its solver takes the widening step without a line search)"); return MSDP_EUNSUPPORTED; }
+    if (h->d.manifold == MANI_STIEFEL) { msdp_set_error("linesearch_accept: not for a %s handle (its solver takes the widening step without a line search)", msdp_block_kind_name(h->d.efree)); return MSDP_EUNSUPPORTED; }
     h->h_ctl->cur ^= 1;
     h->state_valid = false;
     h->gradnorm_valid = false;

@@ -25,6 +25,13 @@ static void algo_cost(msdp_handle h, double* bytes, double* flops) {
         const double dd = (double)d.blk * d.blk;
         *bytes = (double)d.nnz * (8.0 + 4.0 / dd) + (d.nb + 1) * 4.0 + 24.0 * n * p + 8.0 * n * d.blk;
         *flops = 2.0 * (double)d.nnz * p + (1.0 + 6.0 * d.blk) * n * p;
+        if (d.efree) {
+            // the pose-graph kind: nb free rows carry no multiplier and no projection -- Lambda is nb d^2 values with
+            // d = blk - 1, and the 6 d p flops per row of Lambda U, sym(W Y') and its product fall on the nb d rotation rows
+            const double dr = d.blk - 1.0;
+            *bytes = (double)d.nnz * (8.0 + 4.0 / dd) + (d.nb + 1) * 4.0 + 24.0 * n * p - 8.0 * d.nb * p + 8.0 * d.nb * dr * dr;
+            *flops = 2.0 * (double)d.nnz * p + 1.0 * n * p + 6.0 * dr * (d.nb * dr) * p;
+        }
     } else if (d.costkind == COST_DENSE) {
         *bytes = 8.0 * n * (double)d.n + 24.0 * n * p;
         *flops = 2.0 * n * (double)d.n * p;

@@ -704,7 +704,7 @@ extern "C" int msdp_comm_init_local(msdp_handle h, int32_t nranks, int32_t rank,
     MSDP_CHECK_H(h);
     if (nranks < 1 || nranks > LOCAL_MAX_RANKS || rank < 0 || rank >= nranks) { msdp_set_error("comm_init_local: bad arguments"); return MSDP_EINVAL; }
     if (h->d.costkind == COST_HERM) { msdp_set_error("comm_init_local: a Hermitian handle joins no communicator (row-sharded complex factors are not implemented)"); return MSDP_EUNSUPPORTED; }
-    if (h->d.costkind == COST_BLOCK) { msdp_set_error("comm_init_local: a unit-block-diagonal handle joins no communicator (row-sharded block rows are not implemented)"); return MSDP_EUNSUPPORTED; }
+    if (h->d.costkind == COST_BLOCK) { msdp_set_error("comm_init_local: a %s handle joins no communicator (row-sharded block rows are not implemented)", msdp_block_kind_name(h->d.efree)); return MSDP_EUNSUPPORTED; }
     if (h->d.costkind == COST_SPLR) { msdp_set_error("comm_init_local: a sparse-plus-low-rank handle joins no communicator (row-sharded low-rank terms are not implemented)"); return MSDP_EUNSUPPORTED; }
     if (h->have_point || h->use_comm) { msdp_set_error("comm_init_local must precede set_point / comm_init"); return MSDP_ESTATE; }
     if (h->presharded && (nranks != h->nranks || rank != h->rank)) { msdp_set_error("comm_init_local: shard was created as rank %d of %d", h->rank, h->nranks); return MSDP_EINVAL; }
@@ -728,7 +728,7 @@ extern "C" int msdp_comm_init_ipc(msdp_handle h, int32_t nranks, int32_t rank, c
     MSDP_CHECK_H(h);
     if (nranks < 1 || nranks > LOCAL_MAX_RANKS || rank < 0 || rank >= nranks || !name || name[0] != '/') { msdp_set_error("comm_init_ipc: bad arguments (the name starts with '/')"); return MSDP_EINVAL; }
     if (h->d.costkind == COST_HERM) { msdp_set_error("comm_init_ipc: a Hermitian handle joins no communicator (row-sharded complex factors are not implemented)"); return MSDP_EUNSUPPORTED; }
-    if (h->d.costkind == COST_BLOCK) { msdp_set_error("comm_init_ipc: a unit-block-diagonal handle joins no communicator (row-sharded block rows are not implemented)"); return MSDP_EUNSUPPORTED; }
+    if (h->d.costkind == COST_BLOCK) { msdp_set_error("comm_init_ipc: a %s handle joins no communicator (row-sharded block rows are not implemented)", msdp_block_kind_name(h->d.efree)); return MSDP_EUNSUPPORTED; }
     if (h->d.costkind == COST_SPLR) { msdp_set_error("comm_init_ipc: a sparse-plus-low-rank handle joins no communicator (row-sharded low-rank terms are not implemented)"); return MSDP_EUNSUPPORTED; }
     if (h->have_point || h->use_comm) { msdp_set_error("comm_init_ipc must precede set_point / comm_init"); return MSDP_ESTATE; }
     if (h->presharded && (nranks != h->nranks || rank != h->rank)) { msdp_set_error("comm_init_ipc: shard was created as rank %d of %d", h->rank, h->nranks); return MSDP_EINVAL; }
@@ -914,7 +914,7 @@ extern "C" int msdp_comm_init(msdp_handle h, int32_t nranks, int32_t rank, const
     MSDP_CHECK_H(h);
     if (nranks < 1 || rank < 0 || rank >= nranks || !id128) { msdp_set_error("bad comm arguments"); return MSDP_EINVAL; }
     if (h->d.costkind == COST_HERM) { msdp_set_error("comm_init: a Hermitian handle joins no communicator (row-sharded complex factors are not implemented)"); return MSDP_EUNSUPPORTED; }
-    if (h->d.costkind == COST_BLOCK) { msdp_set_error("comm_init: a unit-block-diagonal handle joins no communicator (row-sharded block rows are not implemented)"); return MSDP_EUNSUPPORTED; }
+    if (h->d.costkind == COST_BLOCK) { msdp_set_error("comm_init: a %s handle joins no communicator (row-sharded block rows are not implemented)", msdp_block_kind_name(h->d.efree)); return MSDP_EUNSUPPORTED; }
     if (h->d.costkind == COST_SPLR) { msdp_set_error("comm_init: a sparse-plus-low-rank handle joins no communicator (row-sharded low-rank terms are not implemented)"); return MSDP_EUNSUPPORTED; }
     if (h->have_point) { msdp_set_error("comm_init must precede set_point"); return MSDP_ESTATE; }
     if (h->presharded && (nranks != h->nranks || rank != h->rank)) { msdp_set_error("comm_init: shard was created as rank %d of %d", h->rank, h->nranks); return MSDP_EINVAL; }
@@ -956,7 +956,7 @@ extern "C" int msdp_debug_shard(msdp_handle h, int32_t nranks, int32_t rank) {
     MSDP_CHECK_H(h);
     if (nranks < 1 || rank < 0 || rank >= nranks) { msdp_set_error("bad shard (%d of %d)", rank, nranks); return MSDP_EINVAL; }
     if (h->have_point || h->use_comm) { msdp_set_error("debug_shard must precede set_point / comm_init"); return MSDP_ESTATE; }
-    if (h->d.costkind == COST_BLOCK) { msdp_set_error("debug_shard: a unit-block-diagonal handle is not row-sharded"); return MSDP_EUNSUPPORTED; }
+    if (h->d.costkind == COST_BLOCK) { msdp_set_error("debug_shard: a %s handle is not row-sharded", msdp_block_kind_name(h->d.efree)); return MSDP_EUNSUPPORTED; }
     if (h->d.costkind == COST_DENSE || h->d.costkind == COST_SPLR || h->d.costkind == COST_HERM || h->kind == MSDP_KIND_MULTIBLOCK || msdp_dual_kind(h)) {
         msdp_set_error("debug_shard: sparse-C and affine (unitdiag / unittrace / generic) handles only");
         return MSDP_EUNSUPPORTED;

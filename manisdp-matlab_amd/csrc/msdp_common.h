@@ -79,6 +79,10 @@ enum { COST_SPARSE = 0, COST_DENSE = 1, COST_AFFINE = 2,
        COST_SPLR = 3,     // C = Cs + V diag(s) V': the sparse rows below plus the low-rank fields lr* (msdp_lowrank.hip)
        COST_HERM = 4,     // C = A + iB Hermitian: rowptr / colind below with the complex values hzv / hzell (msdp_hermitian.hip); cval and ellv are null
        COST_BLOCK = 5 };  // C in block CSR of block order d.blk (brp / bci / bval below, msdp_stiefel.hip); rowptr, colind, cval and the ELL copy are null
+// the name of a COST_BLOCK / MANI_STIEFEL kind in messages: efree = the free rows per block
+static inline const char* msdp_block_kind_name(int efree) { return efree ? "pose-graph" : "unit-block-diagonal"; }
+// the widest factor a COST_BLOCK handle holds
+#define MSDP_BLOCK_PMAX 256
 // the rows of the cost matrix are sparse rows (no dense n x n operand exists or is reserved)
 static inline bool msdp_cost_sparse_rows(int costkind) { return costkind == COST_SPARSE || costkind == COST_SPLR || costkind == COST_HERM || costkind == COST_BLOCK; }
 
@@ -183,7 +187,9 @@ struct Dev {
     // bval[k * d * d ..] row-major (zero where the caller's pattern is partial); Lam[slot] = the multiplier blocks
     // Lambda_i = sym((C Y)_i Y_i') of the point in that slot (nb * d * d doubles, each block row-major and symmetric); eG[slot]
     // carries their diagonals, row by row
-    int blk, nb;
+    // The pose-graph kind (msdp_pose.hip) is the same storage with efree = 1: blocks of blk = d + 1 rows, the last of them a free
+    // (Euclidean) row; Lambda stays d x d with d = blk - efree (nb * d * d doubles per slot), eG holds 0 in the free-row entries
+    int blk, nb, efree;
     const int* brp; const int* bci; const double* bval;
     double* Lam[2];
 };
@@ -469,7 +475,7 @@ int msdp_hermitian_setup(msdp_handle h, const double* val);   // the complex CSR
 int msdp_hermitian_sv(msdp_handle h, const double* z, const double* v, double* w);   // w = C v - z .* v, v and w n complex entries (re, im interleaved)
 int msdp_hermitian_jcopy(msdp_handle h, const double* v, double* w);                 // w = i * v: (re, im) -> (-im, re)
 // msdp_stiefel.hip
-int msdp_stiefel_setup(msdp_handle h, int blk, const int64_t* jc, const int64_t* ir, const double* val);   // block CSR of a COST_BLOCK handle from the caller's CSC arrays; Lam[0..1]
+int msdp_stiefel_setup(msdp_handle h, int blk, int efree, const int64_t* jc, const int64_t* ir, const double* val);   // block CSR (block order blk, of which efree free rows) of a COST_BLOCK handle from the caller's CSC arrays; Lam[0..1]
 int msdp_stiefel_costgrad(msdp_handle h, int slot);           // Y[slot] -> Gr[slot], Lam[slot], eG[slot], P_F, P_GG (gather source: d.full)
 int msdp_stiefel_hess(msdp_handle h);
 int msdp_stiefel_upd2(msdp_handle h);
@@ -477,6 +483,14 @@ int msdp_stiefel_retract(msdp_handle h);
 int msdp_stiefel_proj(msdp_handle h, const double* Y, const double* U, double* V);
 int msdp_stiefel_retr(msdp_handle h, const double* Y, const double* U, double* Z, double alpha);
 int msdp_stiefel_sv(msdp_handle h, const double* Lam, const double* v, double* w);   // w = C v - blockdiag(Lam) v for vectors of n entries (the escape's S*v)
+// msdp_pose.hip: the same steps for a COST_BLOCK handle with d.efree = 1; the msdp_stiefel_* launchers above hand such a handle on
+int msdp_pose_costgrad(msdp_handle h, int slot);
+int msdp_pose_hess(msdp_handle h);
+int msdp_pose_upd2(msdp_handle h);
+int msdp_pose_retract(msdp_handle h);
+int msdp_pose_proj(msdp_handle h, const double* Y, const double* U, double* V);
+int msdp_pose_retr(msdp_handle h, const double* Y, const double* U, double* Z, double alpha);
+int msdp_pose_sv(msdp_handle h, const double* Lam, const double* v, double* w);      // w = C v - blockdiag(Lam (+) 0) v
 // msdp_trip1.hip, msdp_trip2.hip
 int msdp_trip1_ok(msdp_handle h);                             // sharded trip with one all-reduce applies to this handle
 int msdp_launch_trip1_init(msdp_handle h);

@@ -434,6 +434,26 @@ __device__ __forceinline__ void msdp_block_symdot(const double2 (&A)[D][NCH], co
         }
 }
 
+// The same for the leading D rows of blocks that hold more (the pose-graph kind, msdp_pose.hip: D rotation rows and one free
+// row, RA / RB = D or D + 1): T = sym(A(1:D, :) B(1:D, :)'); the summation order of msdp_block_symdot
+template <int D, int LPR, int NCH, int RA, int RB>
+__device__ __forceinline__ void msdp_block_symdot_lead(const double2 (&A)[RA][NCH], const double2 (&B)[RB][NCH], double (&T)[D][D]) {
+    static_assert(RA >= D && RB >= D, "blocks of at least D rows");
+#pragma unroll
+    for (int a = 0; a < D; ++a)
+#pragma unroll
+        for (int b = a; b < D; ++b) {
+            double s = 0.0;
+#pragma unroll
+            for (int ch = 0; ch < NCH; ++ch) {
+                s += A[a][ch].x * B[b][ch].x + A[a][ch].y * B[b][ch].y;
+                if (b != a) s += A[b][ch].x * B[a][ch].x + A[b][ch].y * B[a][ch].y;
+            }
+            s = msdp_group_sum<LPR>(s);
+            T[a][b] = T[b][a] = (b != a) ? 0.5 * s : s;
+        }
+}
+
 // R = G^(-1/2) of a symmetric positive definite D x D matrix in registers (the polar retraction: G = A A' of a block A = Y + eta,
 // G = I + eta eta' >= I for tangent eta).  Symmetric eigen-decomposition by Jacobi rotations -- for D = 2 a single rotation is
 // the closed form; D = 3 runs cyclic sweeps until the off-diagonal part is below rounding (|off|^2 <= 1e-32 |diag|^2), at most

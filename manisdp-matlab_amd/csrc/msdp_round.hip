@@ -288,7 +288,7 @@ extern "C" int msdp_round_hyperplane(msdp_handle h, int32_t trials, const double
     if (h->nranks > 1 || h->use_comm || h->lgroup) { msdp_set_error("round_hyperplane: not on a handle that has joined a communicator"); return MSDP_EUNSUPPORTED; }
     Dev& d = h->d;
     if (d.costkind == COST_HERM) { msdp_set_error("round_hyperplane: not for a Hermitian handle (+1/-1 rounding is the real problem's)"); return MSDP_EUNSUPPORTED; }
-    if (d.costkind == COST_BLOCK) { msdp_set_error("round_hyperplane: not for a unit-block-diagonal handle (+1/-1 rounding is the unit-diagonal problem's; rotations are rounded on the host)"); return MSDP_EUNSUPPORTED; }
+    if (d.costkind == COST_BLOCK) { msdp_set_error("round_hyperplane: not for a %s handle (+1/-1 rounding is the unit-diagonal problem's; rotations are rounded on the host)", msdp_block_kind_name(d.efree)); return MSDP_EUNSUPPORTED; }
     if (d.costkind != COST_SPARSE && d.costkind != COST_DENSE && d.costkind != COST_SPLR) { msdp_set_error("round_hyperplane: no cost matrix"); return MSDP_EUNSUPPORTED; }
     if (!h->have_point) { msdp_set_error("round_hyperplane: no resident point"); return MSDP_ESTATE; }
     const int n = d.n, p = d.p, T = trials, W = T / 64;

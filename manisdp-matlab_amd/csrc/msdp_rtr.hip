@@ -52,8 +52,11 @@ void msdp_fill_ctl(msdp_handle h, const msdp_rtr_opts* o) {
     c->psync_backoff = h->tune.psync_backoff;
     c->psync8_backoff = h->tune.psync8_backoff;
     // trustregions.m:363-372; typicaldist: pi*sqrt(n) (ManiSDP_onlyunitdiag.m:137) or pi (spherefactory.m:111)
-    // ... or sqrt(n*p) (euclideanfactory.m:57) or sqrt(dim) = sqrt(nb (p d - d (d + 1) / 2)) (stiefelstackedfactory.m:43,53)
-    const double stf_dim = (double)h->d.nb * ((double)h->d.p * h->d.blk - 0.5 * h->d.blk * (h->d.blk + 1));
+    // ... or sqrt(n*p) (euclideanfactory.m:57) or sqrt(dim) = sqrt(nb (p d - d (d + 1) / 2)) (stiefelstackedfactory.m:43,53);
+    // with efree free rows per block d = blk - efree and the product's sqrt(nb (p d - d (d + 1) / 2) + nb efree p)
+    // (productmanifold.m:160-166 over the two)
+    const double stf_d = (double)(h->d.blk - h->d.efree);
+    const double stf_dim = (double)h->d.nb * ((double)h->d.p * stf_d - 0.5 * stf_d * (stf_d + 1.0) + (double)h->d.efree * h->d.p);
     const double typical = (h->d.manifold == MANI_OBLIQUE) ? M_PI * sqrt((double)h->d.n)
                            : (h->d.manifold == MANI_EUCLID ? sqrt((double)h->d.n * (double)h->d.p)
                            : (h->d.manifold == MANI_STIEFEL ? sqrt(std::max(stf_dim, 1.0)) : M_PI));

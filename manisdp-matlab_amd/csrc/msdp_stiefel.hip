@@ -18,6 +18,9 @@
 // 1 / d^2 of plain CSR.  Workgroup chunks are over blocks, so a block never straddles two workgroups.  Lambda lives per point
 // slot (d.Lam[slot], the slot scheme of eG), its diagonal in eG[slot] so that msdp_get_z serves the kind unchanged.
 // The kind runs the generic per-iteration path of msdp_rtr.hip (no persistent or fused trip, no row sharding).
+// SIBLINGS: msdp_pose.hip holds a copy of every kernel below for blocks of d + 1 rows whose last row is free (the pose-graph
+// kind, d.efree = 1; the launchers at the end of this file hand such a handle on).  The copies differ in B = D + 1, the a < D
+// guards and msdp_block_symdot_lead only: a fix to a kernel here belongs there too.
 #include "msdp_device.h"
 #include <algorithm>
 #include <math.h>
@@ -367,23 +370,28 @@ __global__ void k_stf_sv(int nb, const int* __restrict__ brp, const int* __restr
     } while (0)
 
 int msdp_stiefel_costgrad(msdp_handle h, int slot) {
+    if (h->d.efree) return msdp_pose_costgrad(h, slot);      // blocks with a free row: msdp_pose.hip, here and below
     if (slot < 0 || slot > 1) { msdp_set_error("unit-block-diagonal handle: point slot %d", slot); return MSDP_EINVAL; }
     STF_DISPATCH(k_stf_costgrad, h, h->d, slot);
     return 0;
 }
 int msdp_stiefel_hess(msdp_handle h) {
+    if (h->d.efree) return msdp_pose_hess(h);
     STF_DISPATCH(k_stf_hess, h, h->d);
     return 0;
 }
 int msdp_stiefel_upd2(msdp_handle h) {
+    if (h->d.efree) return msdp_pose_upd2(h);
     STF_DISPATCH(k_stf_upd2, h, h->d);
     return 0;
 }
 int msdp_stiefel_retract(msdp_handle h) {
+    if (h->d.efree) return msdp_pose_retract(h);
     STF_DISPATCH(k_stf_retract, h, h->d);
     return 0;
 }
 int msdp_stiefel_proj(msdp_handle h, const double* Y, const double* U, double* V) {
+    if (h->d.efree) return msdp_pose_proj(h, Y, U, V);
     const Dev& d = h->d;
     const dim3 gr((d.nb + 255) / 256), bl(256);
     if (d.blk == 2) hipLaunchKernelGGL(k_stf_proj_simple<2>, gr, bl, 0, h->stream, Y, U, V, d.nb, d.ld);
@@ -392,6 +400,7 @@ int msdp_stiefel_proj(msdp_handle h, const double* Y, const double* U, double* V
     return 0;
 }
 int msdp_stiefel_retr(msdp_handle h, const double* Y, const double* U, double* Z, double alpha) {
+    if (h->d.efree) return msdp_pose_retr(h, Y, U, Z, alpha);
     const Dev& d = h->d;
     const dim3 gr((d.nb + 255) / 256), bl(256);
     if (d.blk == 2) hipLaunchKernelGGL(k_stf_retr_simple<2>, gr, bl, 0, h->stream, Y, U, Z, alpha, d.nb, d.ld);
@@ -400,6 +409,7 @@ int msdp_stiefel_retr(msdp_handle h, const double* Y, const double* U, double* Z
     return 0;
 }
 int msdp_stiefel_sv(msdp_handle h, const double* Lam, const double* v, double* w) {
+    if (h->d.efree) return msdp_pose_sv(h, Lam, v, w);
     const Dev& d = h->d;
     if (d.costkind != COST_BLOCK || !d.brp) { msdp_set_error("block product: not a unit-block-diagonal handle"); return MSDP_ESTATE; }
     const dim3 gr((d.nb + 255) / 256), bl(256);
@@ -410,11 +420,13 @@ int msdp_stiefel_sv(msdp_handle h, const double* Lam, const double* v, double* w
 }
 
 // Block CSR from the caller's CSC arrays of the symmetric order-N matrix (column j is read as row j, as for the scalar kinds).
-// Block row i collects the block columns its d rows touch, ascending; a block the pattern covers only in part is zero-filled.
-int msdp_stiefel_setup(msdp_handle h, int blk, const int64_t* jc, const int64_t* ir, const double* val) {
+// Block row i collects the block columns its rows touch, ascending; a block the pattern covers only in part is zero-filled.
+// blk = the block order of the storage; efree of its rows are free (the pose-graph kind, msdp_pose.hip), and the multiplier
+// blocks Lam are of order blk - efree.
+int msdp_stiefel_setup(msdp_handle h, int blk, int efree, const int64_t* jc, const int64_t* ir, const double* val) {
     Dev& d = h->d;
-    if (h->nranks != 1 || h->use_comm || d.n_loc != d.n) { msdp_set_error("unit-block-diagonal cost: single-rank handles only"); return MSDP_EUNSUPPORTED; }
-    const int n = d.n, nb = n / blk, dd = blk * blk;
+    if (h->nranks != 1 || h->use_comm || d.n_loc != d.n) { msdp_set_error("%s cost: single-rank handles only", msdp_block_kind_name(efree)); return MSDP_EUNSUPPORTED; }
+    const int n = d.n, nb = n / blk, dd = blk * blk, ll = (blk - efree) * (blk - efree);
     std::vector<int> brp((size_t)nb + 1, 0), bci;
     std::vector<double> bval;
     std::vector<int> pos((size_t)nb, -1);               // block column -> entry of the running block row
@@ -428,7 +440,7 @@ int msdp_stiefel_setup(msdp_handle h, int blk, const int64_t* jc, const int64_t*
             }
         std::sort(cols.begin(), cols.end());
         const size_t base = bci.size();
-        if (base + cols.size() > (size_t)0x7fffffff / dd) { msdp_set_error("unit-block-diagonal cost: too many blocks in C"); return MSDP_EINVAL; }
+        if (base + cols.size() > (size_t)0x7fffffff / dd) { msdp_set_error("%s cost: too many blocks in C", msdp_block_kind_name(efree)); return MSDP_EINVAL; }
         for (size_t t = 0; t < cols.size(); ++t) { pos[cols[t]] = (int)(base + t); bci.push_back(cols[t]); }
         bval.resize((base + cols.size()) * dd, 0.0);
         for (int a = 0; a < blk; ++a)
@@ -442,10 +454,10 @@ int msdp_stiefel_setup(msdp_handle h, int blk, const int64_t* jc, const int64_t*
     const int* dbrp = nullptr; const int* dbci = nullptr; const double* dbval = nullptr;
     if ((rc = msdp_upload<int>(h, brp, &dbrp)) || (rc = msdp_upload<int>(h, bci, &dbci)) || (rc = msdp_upload<double>(h, bval, &dbval))) return rc;
     for (int s = 0; s < 2; ++s) {
-        if ((rc = msdp_dev_alloc<double>(h, &d.Lam[s], (size_t)nb * dd))) return rc;
-        HIPCHK(hipMemset(d.Lam[s], 0, (size_t)nb * dd * sizeof(double)));
+        if ((rc = msdp_dev_alloc<double>(h, &d.Lam[s], (size_t)nb * ll))) return rc;
+        HIPCHK(hipMemset(d.Lam[s], 0, (size_t)nb * ll * sizeof(double)));
     }
-    d.blk = blk; d.nb = nb; d.brp = dbrp; d.bci = dbci; d.bval = dbval;
+    d.blk = blk; d.nb = nb; d.efree = efree; d.brp = dbrp; d.bci = dbci; d.bval = dbval;
     d.nnz = (int64_t)bci.size() * dd;
     d.rowptr = nullptr; d.colind = nullptr; d.cval = nullptr;
     d.ellW = 0; d.ell_stride = 0; d.ellc = nullptr; d.ellv = nullptr;

@@ -30,6 +30,7 @@ __all__ = [
     "from_sdpa", "get_basis", "bqpmom", "qsmom", "theta_problem", "generate_hamming",
     "dense_unitdiag_cost", "vec_index",
     "rotation_synchronization", "round_rotations", "rotation_error",
+    "pose_graph", "round_poses", "pose_error",
 ]
 
 
@@ -1294,3 +1295,98 @@ def rotation_error(R, R_true):
     U, _, Vt = np.linalg.svd(np.einsum("nab,nac->bc", R, R_true))
     Q = U @ Vt
     return float(np.max(np.linalg.norm(R @ Q - R_true, axis=(1, 2))))
+
+
+# --------------------------------------------------------------------------- pose graphs (SE(d) synchronisation)
+def _sync_graph(n, degree, rng):
+    """The edge list of rotation_synchronization: the ring, then ``n (degree - 2) / 2`` chords, sorted, i < j."""
+    ring = np.stack([np.arange(n), (np.arange(n) + 1) % n], axis=1)
+    nch = max(int(n * (int(degree) - 2)) // 2, 0)
+    chords = rng.integers(0, n, size=(nch, 2))
+    e = np.concatenate([ring, chords], axis=0)
+    e = np.sort(e[e[:, 0] != e[:, 1]], axis=1)
+    return np.unique(e, axis=0)
+
+
+def pose_graph(n, d, degree, sigma_r, sigma_t, seed, kappa=1.0, omega=1.0):
+    """Pose-graph optimisation (synchronisation over SE(d)): recover poses (R_i, t_i) from noisy relative poses on a connected
+    random graph.  Returns ``(C, R_true, t_true, edges, meas_R, meas_t)``: the symmetric PSD cost (CSR, order n (d + 1)) of
+    ``min <C, X>, X PSD, (X_[ii])_{1..d,1..d} = I_d`` -- block i of the factor is the d rows Y_i (the rotation R_i in the
+    factor's frame) followed by one free row tau_i (the position t_i) --, the planted rotations (n, d, d) and positions (n, d),
+    the (m, 2) edge list with i < j and the measurements (m, d, d), (m, d).
+    Definition, in draw order from ``np.random.default_rng(seed)``: the graph of rotation_synchronization (ring, then chords);
+    ``R_true`` = the nearest rotations to ``standard_normal((n, d, d))``; ``t_true = 3 standard_normal((n, d))``; per edge
+    (sorted by (i, j)) ``M_ij`` = the nearest rotation to ``R_i R_j' + sigma_r standard_normal((m, d, d))`` (all of them before
+    any m_ij) and ``m_ij = R_i (t_j - t_i) + sigma_t standard_normal((m, d))``.  The cost is
+    ``sum_ij kappa |Y_i - M_ij Y_j|^2 + omega |tau_j - tau_i - m_ij' Y_i|^2``, as blocks
+    ``C_[ii] += [[kappa I + omega m m', omega m], [omega m', omega]]``, ``C_[jj] += [[kappa I, 0], [0, omega]]``,
+    ``C_[ij] += [[-kappa M, -omega m], [0, -omega]]``, ``C_[ji] = C_[ij]'``.  Without noise the optimum is 0 at rank d."""
+    n, d = int(n), int(d)
+    rng = np.random.default_rng(seed)
+    edges = _sync_graph(n, degree, rng)
+    m = edges.shape[0]
+    R_true = _to_so(rng.standard_normal((n, d, d)))
+    t_true = 3.0 * rng.standard_normal((n, d))
+    i, j = edges[:, 0], edges[:, 1]
+    meas_R = _to_so(R_true[i] @ np.transpose(R_true[j], (0, 2, 1)) + float(sigma_r) * rng.standard_normal((m, d, d)))
+    meas_t = np.einsum("mab,mb->ma", R_true[i], t_true[j] - t_true[i]) + float(sigma_t) * rng.standard_normal((m, d))
+    B = d + 1
+    kappa, omega = float(kappa), float(omega)
+    Cii = np.zeros((m, B, B))
+    Cii[:, :d, :d] = kappa * np.eye(d) + omega * meas_t[:, :, None] * meas_t[:, None, :]
+    Cii[:, :d, d] = Cii[:, d, :d] = omega * meas_t
+    Cii[:, d, d] = omega
+    Cjj = np.zeros((m, B, B))
+    Cjj[:, :d, :d] = kappa * np.eye(d)
+    Cjj[:, d, d] = omega
+    Cij = np.zeros((m, B, B))
+    Cij[:, :d, :d] = -kappa * meas_R
+    Cij[:, :d, d] = -omega * meas_t
+    Cij[:, d, d] = -omega
+    a, b = np.meshgrid(np.arange(B), np.arange(B), indexing="ij")
+    ra = lambda k: (k[:, None, None] * B + a[None]).ravel()
+    cb = lambda k: (k[:, None, None] * B + b[None]).ravel()
+    N = n * B
+    D = sp.coo_matrix((np.concatenate([Cii.ravel(), Cjj.ravel()]),
+                       (np.concatenate([ra(i), ra(j)]), np.concatenate([cb(i), cb(j)]))), shape=(N, N)).tocsr()
+    H = sp.coo_matrix((Cij.ravel(), (ra(i), cb(j))), shape=(N, N)).tocsr()
+    C = sp.csr_matrix(D + H + H.T)
+    C = sp.csr_matrix(0.5 * (C + C.T))                     # duplicates of a diagonal block are summed in no fixed order
+    C.eliminate_zeros()
+    C.sort_indices()
+    return C, R_true, t_true, edges, meas_R, meas_t
+
+
+def round_poses(Y, d):
+    """Poses from the factor Y (n (d + 1) x p: blocks of d orthonormal rows and one free row) of the pose-graph SDP, on the
+    host: Y is restricted to its top-d right singular subspace; the rotations come from the rotation rows as round_rotations
+    makes them (polar factors, the majority's determinant sign), the positions are the free rows in the same frame (a
+    reflection of the frame reflects them too).  Returns ``(R, t)``: (n, d, d) and (n, d)."""
+    Y = np.asarray(Y, dtype=np.float64)
+    d = int(d)
+    B = d + 1
+    n = Y.shape[0] // B
+    _, _, Vt = np.linalg.svd(Y, full_matrices=False)
+    Z = (Y @ Vt[:d].T).reshape(n, B, d)
+    U, _, Wt = np.linalg.svd(Z[:, :d, :])
+    R = U @ Wt
+    t = np.array(Z[:, d, :])
+    if np.sum(np.linalg.det(R) < 0) > n / 2:
+        R = R.copy()
+        R[:, :, -1] *= -1.0
+        t[:, -1] *= -1.0
+    return _to_so(R), t
+
+
+def pose_error(R, t, R_true, t_true):
+    """``(max_i |R_i Q - R_true_i|_F, max_i |t_i Q - s - t_true_i|)`` over the gauge of the pose-graph SDP, which sees the
+    poses up to one orthogonal Q (R_i -> R_i Q, t_i -> t_i Q) and one shift s of all positions: Q is the orthogonal Procrustes
+    alignment of the rotations (rotation_error), s the mean of ``t_i Q - t_true_i``."""
+    R, t = np.asarray(R), np.asarray(t)
+    R_true, t_true = np.asarray(R_true), np.asarray(t_true)
+    U, _, Vt = np.linalg.svd(np.einsum("nab,nac->bc", R, R_true))
+    Q = U @ Vt
+    er = float(np.max(np.linalg.norm(R @ Q - R_true, axis=(1, 2))))
+    tq = t @ Q
+    s = np.mean(tq - t_true, axis=0)
+    return er, float(np.max(np.linalg.norm(tq - s - t_true, axis=1)))

@@ -54,7 +54,7 @@ def _host_threads():
     return threadpool_limits(limits=max(1, min(ncpu, 16)))
 
 __all__ = ["ManiSDP_onlyunitdiag", "ManiSDP_unitdiag", "ManiSDP_unittrace", "ManiSDP", "ManiSDP_multiblock",
-           "ManiDSDP_unitdiag", "round_unitdiag", "ManiSDP_onlyunitblockdiag", "onlyunitblockdiag_defaults", "DEFAULTS",
+           "ManiDSDP_unitdiag", "round_unitdiag", "ManiSDP_onlyunitblockdiag", "onlyunitblockdiag_defaults", "ManiSDP_posegraph", "posegraph_defaults", "DEFAULTS",
            "DATA_FIELDS"]
 
 # Option defaults of the reference's entry points: ManiSDP_onlyunitdiag.m:8-17,
@@ -735,6 +735,179 @@ def _onlyunitblockdiag_impl(C, d, options, verbose, rng):
     data.update({"Y": Y, "S": S, "z": z, "Lambda": Lam, "dinf": dinf, "gradnorm": gradnorm, "rank": r,
                  "time": time.time() - t0, "p": Y.shape[1], "X": (Y @ Y.T if N <= dense_X_max else None)})
     if data["status"] == 0 and (dinf is None or dinf > o["tol"] or not certified):
+        data["status"] = 1
+        _say(verbose, "Iteration maximum is reached!")
+    if obj is not None:
+        _say(verbose, "ManiSDP: optimum = %0.8f, time = %0.2fs" % (obj, time.time() - t0))
+    return Y, obj, data
+
+
+# =============================================================== posegraph
+def posegraph_defaults(d):
+    """The option defaults of ManiSDP_posegraph for dimension d: those of ManiSDP_onlyunitblockdiag (p0 = d + 2, delta = d)."""
+    return onlyunitblockdiag_defaults(d)
+
+
+def _polar_rotation_rows(Y, d):
+    """The d rotation rows of every block of d + 1 rows replaced by their polar factor; the free rows as they are."""
+    A = np.array(Y.reshape(Y.shape[0] // (d + 1), d + 1, Y.shape[1]))
+    u, _, vt = np.linalg.svd(A[:, :d, :], full_matrices=False)
+    A[:, :d, :] = u @ vt
+    return np.ascontiguousarray(A.reshape(Y.shape))
+
+
+def _pad_blocks(Lam):
+    """blockdiag(Lambda_i (+) 0): the d x d multiplier blocks as a sparse matrix of order n (d + 1)."""
+    nb, d, _ = Lam.shape
+    P = np.zeros((nb, d + 1, d + 1))
+    P[:, :d, :d] = Lam
+    return sp.block_diag(list(P), format="csr")
+
+
+def ManiSDP_posegraph(C, d, options=None, verbose=True, rng=None):
+    """``min <C, X>  s.t. X PSD of order N = n (d + 1), (X_[ii])_{1..d,1..d} = I_d`` for d = 2 or 3: the SDP of pose-graph
+    optimisation (synchronisation over SE(d), the non-marginalised form of SE-Sync / Cartan-Sync; problems.pose_graph).  Block
+    i of the factor Y (N x p) is d orthonormal rows (the rotation) followed by one free row (the position): the product of
+    manopt's stiefelstackedfactory(n, d, p) and euclideanfactory(n, p).  C symmetric and bounded below on the free rows (a
+    pose-graph C is PSD).  The loop, option names and printed protocol follow ManiSDP_onlyunitblockdiag, except:
+
+    * the start has the Q factors of randn(p, d) in the rotation rows and zeros in the free rows; ``p0 = d + 2``, ``delta = d``
+      (choices, not measured);
+    * ``obj = 2 cost = <C, Y Y'>`` from the device, not the dual value ``sum tr Lambda``: the two differ by ``sum <g_i, tau_i>``
+      away from a critical point.  ``gap = |obj - dual| / (1 + |obj| + |dual|)`` is printed in the iteration line and returned
+      in ``data["gap"]`` (``data["dual"]`` the dual value);
+    * the loop stops only when ``max(dinf, gap) < tol`` and the cold check certifies.  With ``dinf < tol <= gap`` the point is
+      not stationary (the translation part is ill-conditioned: trustregions() may end at its iteration cap with S PSD already),
+      and trustregions() runs again on the same factor, without a cut or widening;
+    * the polar re-orthonormalisation after a cut or widening touches the rotation rows only.
+
+    Returns (Y, obj, data); ``data["Lambda"]`` holds the multiplier blocks (n, d, d), S = C - blockdiag(Lambda_i (+) 0).  For a
+    pose-graph C the global shift is in the null space of S, so lambda_min of a certified point is 0.
+    ``line_search = 1``, ``device_factor``, ``round`` and ``comm`` raise ValueError before the library is loaded."""
+    with _host_threads():
+        return _posegraph_impl(C, d, options, verbose, rng)
+
+
+def _posegraph_impl(C, d, options, verbose, rng):
+    d = int(d)
+    if d not in (2, 3):
+        raise ValueError(f"the dimension d must be 2 or 3, not {d}")
+    B = d + 1
+    o = dict(options or {})
+    for k, v in posegraph_defaults(d).items():
+        o.setdefault(k, v)
+    for name, what in (("round", "poses are rounded on the host (problems.round_poses)"), ("comm", "a single-rank solve is needed")):
+        if o.get(name) is not None:
+            raise ValueError(f"options[{name!r}] is not available for the pose-graph problem: {what}")
+    if o["line_search"] == 1:
+        raise ValueError("options['line_search'] = 1 is not available for the pose-graph problem")
+    if o.get("device_factor"):
+        raise ValueError("options['device_factor'] is not available for the pose-graph problem: the rank cut stays on the host")
+    if C.shape[0] != C.shape[1] or C.shape[0] % B:
+        raise ValueError(f"the cost matrix must be square of an order that is a multiple of d + 1 = {B}, not {C.shape}")
+    dense_max = int(o.get("dense_eig_max", 3000))
+    dense_default = int(o.get("dense_eig_default", 600))
+    dense_X_max = int(o.get("dense_X_max", 4000))
+    N = C.shape[0]
+    nb = N // B
+    eig_mode = o.get("eig", "host" if N <= dense_default else "device")
+    if eig_mode not in ("host", "device"):
+        raise ValueError(f"options['eig'] must be 'host' or 'device' for the pose-graph problem, not {eig_mode!r}")
+    p = int(o["p0"])
+    delta = int(o["delta"])
+    Y = o.get("Y0", None)
+    if Y is None and p < d:
+        raise ValueError(f"options['p0'] = {p} is below the dimension d = {d}")
+    Csp = sp.csr_matrix(C, dtype=np.float64)
+    rng = rng or np.random.default_rng(0)
+    _say(verbose, "ManiSDP is starting...")
+    _say(verbose, f"SDP size: n = {N}, m = {nb * d * (d + 1) // 2} ({nb} blocks of order {B}, the leading {d} x {d} part pinned)")
+    if Y is None:
+        Y = np.zeros((nb, B, p))
+        for i in range(nb):                                # stiefelstackedfactory.m:142-150; the free rows start at zero
+            Y[i, :d] = np.linalg.qr(rng.standard_normal((p, d)))[0].T
+        Y = Y.reshape(N, p)
+    Y = np.ascontiguousarray(Y, dtype=np.float64)
+    p = Y.shape[1]
+    h = _lib.Handle.posegraph(Csp, d, pcap=min(256, max(32, p + 2 * delta)))
+    for name, value in (o.get("device_options") or {}).items():
+        h.set_option(name, int(value))
+    topts = _rtr_opts(o)
+    data = {"status": 0, "hessvecs": 0, "cost_evals": 0, "rejected": 0, "rtr_seconds": 0.0, "eig_seconds": 0.0, "log": [],
+            "reruns": 0}
+    t0 = time.time()
+    dinf0 = None
+    obj = dual = gap = dinf = gradnorm = z = Lam = r = None
+    certified = True
+    Y_eval = Y
+    try:
+        for it in range(1, int(o["AL_maxiter"]) + 1):
+            h.set_point(Y)
+            st = h.rtr(topts)
+            data["rtr_seconds"] += st.seconds
+            data["hessvecs"] += st.hessvecs
+            data["cost_evals"] += st.cost_evals
+            data["rejected"] += st.rejected
+            gradnorm = st.gradnorm
+            Y = h.get_point()
+            Y_eval = Y
+            Lam = h.get_blockmult()                        # Lambda_i = sym(G_i Y_i'), d x d
+            z = h.get_z()                                  # its diagonals, 0 in the free-row entries
+            dual = float(np.sum(z))
+            obj = 2.0 * h.cost()                           # <C, Y Y'> = dual + sum <g_i, tau_i>
+            gap = abs(obj - dual) / (1.0 + abs(obj) + abs(dual))
+            t1 = time.time()
+            certified = True
+            if eig_mode == "host":
+                dS, vS, nneg = _extreme_eigs_host(Csp - _pad_blocks(Lam), delta, dense_max)
+                lam_min, lam_max = dS[0], dS[-1]
+            else:
+                lam, vS, lam_max, _, certified = _device_escape(
+                    h, lambda tol, maxit: h.escape_eigs(delta, tol=tol, maxit=maxit), o, data, 1e-9, 60000)
+                lam_min = lam[0]
+                nneg = int(np.sum(lam < 0))
+                data["escape_method"] = h.escape_method()
+            data["eig_seconds"] += time.time() - t1
+            dinf = max(0.0, -lam_min) / (1.0 + lam_max)
+            if eig_mode == "device" and certified and (max(dinf, gap) < o["tol"] or it == int(o["AL_maxiter"])):
+                lam_v, v_v, lmax_v, certified = _verify_lambda_min(
+                    h, lambda tol, maxit: h.escape_eigs(1, tol=tol, maxit=maxit), o, data, 1e-9, 60000)
+                dinf_v = max(0.0, -lam_v) / (1.0 + lmax_v)
+                if dinf_v >= o["tol"] > dinf:
+                    vS = np.hstack([v_v, vS[:, :max(delta - 1, 0)]])
+                    nneg = max(nneg, 1)
+                dinf = dinf_v
+            Q, e, r = _thin_svd_rank(Y, float(o["theta"]))
+            _say(verbose, "Iter %d, obj:%0.8f, dinf:%0.1e, gap:%0.1e, r:%d, p:%d, time:%0.2fs" % (it, obj, dinf, gap, r, p, time.time() - t0))
+            data["log"].append((it, obj, dinf, gap, r, p, time.time() - t0, st.hessvecs))
+            data["iters"] = it
+            if max(dinf, gap) < o["tol"] and certified:
+                _say(verbose, "Optimality is reached!")
+                break
+            if it % 20 == 0:
+                if it > 50 and max(dinf, gap) > dinf0:
+                    data["status"] = 2
+                    _say(verbose, "Slow progress!")
+                    break
+                dinf0 = max(dinf, gap)
+            if dinf < o["tol"] <= gap:                     # S is PSD but the point is not stationary: trustregions() again
+                data["reruns"] += 1
+                continue
+            nne = max(min(nneg, delta), 1)
+            if d <= r <= p - 1:                            # never below d: d orthonormal rows need d columns
+                Y = _polar_rotation_rows(_rank_cut(Y, Q, e, r), d)
+                p = r
+            if p + nne > 256:
+                raise RuntimeError(f"the factor width would exceed the device's 256 columns (p = {p}, {nne} more)")
+            Y = _polar_rotation_rows(np.hstack([Y, o["alpha"] * vS[:, :nne]]), d)
+            p = p + nne
+    finally:
+        h.close()
+    Y = Y_eval
+    S = (Csp - _pad_blocks(Lam)) if Lam is not None else None
+    data.update({"Y": Y, "S": S, "z": z, "Lambda": Lam, "dinf": dinf, "gap": gap, "dual": dual, "gradnorm": gradnorm, "rank": r,
+                 "time": time.time() - t0, "p": Y.shape[1], "X": (Y @ Y.T if N <= dense_X_max else None)})
+    if data["status"] == 0 and (dinf is None or max(dinf, gap) > o["tol"] or not certified):
         data["status"] = 1
         _say(verbose, "Iteration maximum is reached!")
     if obj is not None:

@@ -425,6 +425,13 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
     //       (<16, 5, 3, XRM = 2>: 44 -> 56 -> 44);
     // UMASK: the mask of lanes without columns under ONE workgroup-uniform branch per trip and no select on the rows of Hmd -- all but
     //       the fused launches at 16 lanes per row (<16, 5, 3, FUSE>: 120 -> 140 -> 108; either half alone costs it 16 bytes).
+    // BSTORE (round 8): the row stores of a trip and of the TR tail are UNCONDITIONAL and the lanes that must not store -- no row, no
+    //       columns -- are dropped by the buffer descriptor's range check instead of by EXEC (row_store below) -- the one-rank five-column
+    //       ELL instances but the fused launch at 8 lanes per row (<16, 5, 3, FUSE>: 108 -> 92; <8, 5, 2, FUSE>: 200 -> 204;
+    //       profiles/r8_trip_instruction_counts.md).  The cross-rank instances push through pointers and hold halo slots behind their own
+    //       rows: they keep the guarded stores.  The selects on the stored values stay: taking them out (UMASK here, the tail's) moves the
+    //       compiler's contractions and with them the bits of the result (same file).
+    constexpr bool BSTORE = XRM == 0 && EW == 5 && !(FUSE && LPR == 8);
     constexpr bool BOFF = !(EW == 8 && LPR == 16), ROWB_INV = !XTWO, UMASK = !(FUSE && LPR == 16);
     extern __shared__ double lds[];
     __shared__ double sh8[8 * PWAVES];
@@ -616,6 +623,20 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
     // where a trip's gather from this buffer (fine-grained memory) is done in 1.4 with its arithmetic (profiles/r6_fused_timeline_p32_*.md)
     const __amdgpu_buffer_rsrc_t rs_md = XR ? __builtin_amdgcn_make_buffer_rsrc(d.xr_rows[0], 0, 4u * half_bytes, 0x00020000)
                                             : __builtin_amdgcn_make_buffer_rsrc(d.mdx, 0, (FUSE ? 7u : 4u) * half_bytes, 0x00020000);
+    // BSTORE: this lane's 16 bytes of row slot r into region `reg` of the exchange buffer, through a descriptor of the region that ends
+    // behind this workgroup's LAST row (num_records = hi x ld x 8 bytes from the region's start): every lane, no EXEC mask.  A raw buffer
+    // access (stride 0) whose offset + size exceeds num_records is out of range, and an out-of-range store writes nothing but retires from
+    // vmcnt like any other (the drain in front of the post counts it):
+    //   - a row slot past `hi`: its 16 bytes start at or behind num_records (rows and num_records are multiples of ld x 8, ld even);
+    //   - a lane without columns: bit 31 of its offset is set -- far behind any num_records (a region is < 2^23 bytes, see cs[] above).
+    //     No wrap: rowb0 + the slot term <= (n_loc + ROWS) x ld x 8 < 2^24, so offset + 16 < 2^31 + 2^24 + 16 < 2^32.
+    // A workgroup's rows start at `lo`: nothing it stores lies below its own chunk.  Gathers keep rs_md (they read every workgroup's rows).
+    const unsigned st_records = (unsigned)hi * (unsigned)d.ld * 8u;
+    const unsigned rowbs = rowb0 | (colok ? 0u : 0x80000000u);
+    auto row_store = [&](unsigned reg, int r, double2 val) {
+        st2_sc1(__builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(d.mdx) + (size_t)reg * half_bytes, 0, st_records, 0x00020000),
+                rowbs + (unsigned)(r * RSTEP) * (unsigned)d.ld * 8u, val);
+    };
     // XR: this lane's 16 bytes of local row slot r of region `reg` also go to the members that reference the row
     bool xr_has_push = false, xr_has_push2 = false;                // wave-uniform: some row of this wave is referenced by another member / by two
     if (XR) {
@@ -836,11 +857,15 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
             if (!UMASK && !OK(r)) hq = zz;
             hmd[r] = hq;
             if (MULTI) HQs[xq * R * PB + r * PB + threadIdx.x] = hq;    // (read by the instances with local columns only)
-            if (OK(r)) st2_sc1(rs_md, xq * half_bytes + ROWB(r), hq);
+            if (BSTORE) row_store(xq, r, hq);
+            else if (OK(r)) st2_sc1(rs_md, xq * half_bytes + ROWB(r), hq);
             xr_push(r, xq, hq);
             if (pub) {
                 const double dn = msdp_group_sum_all<LPR>(rv.x * y.x + rv.y * y.y);
-                if (OK(r)) {
+                if (BSTORE) {
+                    row_store(2u, r, mdr);
+                    row_store(3u, r, make_double2(rv.x - y.x * dn, rv.y - y.y * dn));
+                } else if (OK(r)) {
                     st2_sc1(rs_md, 2u * half_bytes + ROWB(r), mdr);
                     st2_sc1(rs_md, 3u * half_bytes + ROWB(r), make_double2(rv.x - y.x * dn, rv.y - y.y * dn));
                 }
@@ -1036,7 +1061,8 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
         if (!(nn > 0.0)) nn = 1.0;                                  // empty row slot
         const double2 ypr = OK(r) ? make_double2(x.x / nn, x.y / nn) : zz;
         YPs[r * PB + threadIdx.x] = ypr;
-        if (OK(r)) st2_sc1(rs_md, yx_base + ROWB(r), ypr);
+        if (BSTORE) row_store(4u, r, ypr);
+        else if (OK(r)) st2_sc1(rs_md, yx_base + ROWB(r), ypr);
     }
     FSTAMP(3);
     // (my proposal rows are performed before the post: the wait is inside)
@@ -1054,7 +1080,8 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
             EGPs[SLOT(r)] = ROK(r) ? dot : 0.0;
             if (ROK(r)) tv[0] += 0.5 * dot;
         }
-        if (OK(r)) st2_sc1(rs_md, gx_base + ROWB(r), gpr);
+        if (BSTORE) row_store(5u + (unsigned)(cur ^ 1), r, gpr);
+        else if (OK(r)) st2_sc1(rs_md, gx_base + ROWB(r), gpr);
     };
     if (CSR) {
 #pragma unroll

@@ -8,6 +8,8 @@ Where the compiler does not see the trip loop as a loop of its own (the fused la
 of it is reported at the depth of the loop over the TR iterations), `--range FIRST:LAST` sums the blocks from label FIRST up to, not
 including, label LAST in the order of the file; the option may be given several times and the ranges are added up.  The labels are read
 off the assembly by hand: a trip's steady-state path is the chain of blocks from the target of the loop's back edge to that back edge.
+A block that is only fallen into carries no label: the compiler's `; %bb.N:` comment in front of it is read as the label .LBB<f>_N, so such a
+block can begin or end a range too.
 usage: python tools/isa_trip_counts.py FILE.hip|FILE.s FILTER [--blocks] [--range FIRST:LAST ...]"""
 import os, re, subprocess, sys, tempfile
 
@@ -66,8 +68,10 @@ def main():
         if flt in name:
             depth, label = 0, "entry"
             by_depth, blocks = {}, []
+            # a block that is only fallen into has no label of its own: the compiler's "; %bb.N:" comment stands for .LBB<f>_N
+            fn = next((m.group(1) for l in lines[i:j] for m in [re.match(r"^\.LBB(\d+)_\d+:", l)] if m), "0")
             for k in range(i, j):
-                l = lines[k]
+                l = re.sub(r"^; %bb\.(\d+):", r".LBB%s_\1:" % fn, lines[k])
                 mb = re.match(r"^(\.LBB\d+_\d+):", l)
                 if mb:
                     depth, label = 0, mb.group(1)

@@ -23,6 +23,15 @@
 //
 // Reference lines are quoted next to the statements (manopt7.0/manopt/solvers/trustregions/tCG.m);
 // cost/projection expressions are those of ManiSDP_onlyunitdiag.m:127-156.
+//
+// Floating-point contraction is pinned to the SOURCE for this whole unit (round 9): an `a * b + c` inside ONE expression is an fma,
+// a product and a sum in separate statements never are.  The compiler's default (fast-honor-pragmas) contracts in the backend, per
+// basic block and by use counts, so an edit of the control flow alone -- no arithmetic statement touched -- chose another product of an
+// `a * b + c * d` to fuse and moved the last bits of the result (profiles/r8_trip_instruction_counts.md).  With `on` the rounding of
+// every kernel here (k_tcg_persist_obl, k_tcg_pipe_obl of msdp_pipe.h) follows from its expressions, and bit identity across
+// structural edits is a check that means something.  A pragma and not a flag of the Makefile: tools/isa_trip_counts.py and
+// tools/isa_scratch_map.py compile this file themselves.
+#pragma clang fp contract(on)
 #include "msdp_device.h"
 #include <math.h>
 #include <cstdlib>

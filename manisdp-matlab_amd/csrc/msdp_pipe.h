@@ -419,20 +419,27 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
     static_assert(PSYNC_NV == 8 && PSYNC_REP * PSYNC_NV == 64, "psync8 posts one slot per lane of wave 0");
     // What each instance takes of the launch-invariant address and mask work.  Decided by the register allocation: an instance takes a
     // piece only where its scratch does not grow (bytes per lane, parent -> with everything -> as chosen; tools/isa_scratch_map.py,
-    // profiles/r7_trip_instruction_counts.md):
+    // profiles/r7_trip_instruction_counts.md, profiles/r8_trip_instruction_counts.md):
     // BOFF: cs[] holds the BYTE offset of the referenced row and the trip multiplies nothing -- all but <16, 8, 3> (68 -> 76 -> 36);
     // ROWB_INV: the row stores' offsets as one lane-invariant register + a uniform term -- all but the two-level cross-rank instances
     //       (<16, 5, 3, XRM = 2>: 44 -> 56 -> 44);
-    // UMASK: the mask of lanes without columns under ONE workgroup-uniform branch per trip and no select on the rows of Hmd -- all but
-    //       the fused launches at 16 lanes per row (<16, 5, 3, FUSE>: 120 -> 140 -> 108; either half alone costs it 16 bytes).
     // BSTORE (round 8): the row stores of a trip and of the TR tail are UNCONDITIONAL and the lanes that must not store -- no row, no
     //       columns -- are dropped by the buffer descriptor's range check instead of by EXEC (row_store below) -- the one-rank five-column
-    //       ELL instances but the fused launch at 8 lanes per row (<16, 5, 3, FUSE>: 108 -> 92; <8, 5, 2, FUSE>: 200 -> 204;
-    //       profiles/r8_trip_instruction_counts.md).  The cross-rank instances push through pointers and hold halo slots behind their own
-    //       rows: they keep the guarded stores.  The selects on the stored values stay: taking them out (UMASK here, the tail's) moves the
-    //       compiler's contractions and with them the bits of the result (same file).
+    //       ELL instances but the fused launch at 8 lanes per row (<16, 5, 3, FUSE>: 108 -> 92; <8, 5, 2, FUSE>: 200 -> 204).  The
+    //       cross-rank instances push through pointers and hold halo slots behind their own rows: they keep the guarded stores.
+    // Round 9, taken by EVERY instance (no instance's scratch grows: fused <16, 5, 3> 92 -> 64, fused <8, 5, 2> 200 -> 184, fused
+    // <8, 8, 2> 52 -> 44, <16, 8, 3> 40 -> 36, the others as before; profiles/r9_trip_instruction_counts.md), so without a switch:
+    //   - the mask of lanes without columns sits under ONE workgroup-uniform branch per trip and the rows of Hmd carry no select
+    //     (round 7's UMASK, which the fused launch at 16 lanes per row could not afford while its stores were masked by EXEC);
+    //   - the refresh rows are published in ONE block behind the row loop, on a countdown: the H md loop of a trip is one straight-line
+    //     block with R stores and no trip divides by `refresh`;
+    //   - the TR tail relies on the invariants of set-up (exact zeros in a lane without a row or without columns) instead of selects
+    //     on the proposal's rows, its gradient's rows and the slot's eG, and adds every slot's share of the cost.
+    // These move blocks, not bits: the contraction of this unit is pinned to the source (msdp_persist.hip, top), and bench.py's outputs
+    // with and without the three are bit-identical.  (Under the compiler's default, which contracts per basic block, each of them moved
+    // the last bits of the result: profiles/r8_trip_instruction_counts.md.)
     constexpr bool BSTORE = XRM == 0 && EW == 5 && !(FUSE && LPR == 8);
-    constexpr bool BOFF = !(EW == 8 && LPR == 16), ROWB_INV = !XTWO, UMASK = !(FUSE && LPR == 16);
+    constexpr bool BOFF = !(EW == 8 && LPR == 16), ROWB_INV = !XTWO;
     extern __shared__ double lds[];
     __shared__ double sh8[8 * PWAVES];
     __shared__ double shp[8 * PWAVES];
@@ -731,6 +738,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
     double z_r = gg, d_Pd = gg, e_Pd = 0.0, e_Pe = 0.0, model_value = 0.0, alpha = 0.0, beta = 0.0;
     double norm_r0 = sqrt(gg);
     int j = 0, stop = 5;
+    int pub_cd = refresh > 0 ? refresh : 0;                        // trips until the next refresh trip (0: never); restarts with every tCG
     // TRACE && FUSE (msdp_debug_persist_trace with reps <= 0): thread 0 of every workgroup stamps the phases of the first MSDP_TRACE_NJ TR
     // iterations of the call into d.trace[(workgroup * NJ + iteration) * 8 + phase]: 0 iteration starts (tCG.m:102-157), 1 first trip's
     // products and partial sums formed, 2 the tCG has ended (bits 56..63: its trips), 3 proposal rows stored and performed, 4 barrier
@@ -838,12 +846,16 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
                     cmd[r].x = fma(beta, cmd[r].x, ctr[r].x); cmd[r].y = fma(beta, cmd[r].y, ctr[r].y);  // C md' = C tangent(r') + beta C md
                 }
             };
-            if (UMASK) { if (!CSR && idle_lanes) products(std::true_type()); else products(std::false_type()); } else products(std::true_type());
+            if (!CSR && idle_lanes) products(std::true_type()); else products(std::false_type());
         }
         have_x = false;
         // every `refresh`-th trip publishes tangent(r) and md of ITS start next to Hmd (no barrier of its own: the reduction orders them
         // like the rows of Hmd); the next trip gathers all three
-        const bool pub = !first && refresh > 0 && ((j + 1) % refresh) == 0;
+        // (a countdown that restarts with every tCG, not (j + 1) % refresh: trip j publishes iff refresh > 0 divides j + 1, and never
+        // the first -- the same trips, without a division by a run-time value in every trip)
+        bool pub = --pub_cd == 0;
+        if (pub) pub_cd = refresh;
+        pub = pub && !first;
         // ---- Hmd = proj(C*md) - md.*eG (tCG.m:163, ManiSDP_onlyunitdiag.m:127-130), its rows to the neighbours, the eight partial sums
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -853,25 +865,12 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
             const double eg = eGs[SLOT(r)];
             // (a lane without a row or without columns: acc, y and mdr are exact zeros -- the invariants of set-up, kept by the masks of
             // the products -- and eg and dot are finite, so hq is +0 without a select)
-            double2 hq = make_double2(acc.x - y.x * dot - mdr.x * eg, acc.y - y.y * dot - mdr.y * eg);
-            if (!UMASK && !OK(r)) hq = zz;
+            const double2 hq = make_double2(acc.x - y.x * dot - mdr.x * eg, acc.y - y.y * dot - mdr.y * eg);
             hmd[r] = hq;
             if (MULTI) HQs[xq * R * PB + r * PB + threadIdx.x] = hq;    // (read by the instances with local columns only)
             if (BSTORE) row_store(xq, r, hq);
             else if (OK(r)) st2_sc1(rs_md, xq * half_bytes + ROWB(r), hq);
             xr_push(r, xq, hq);
-            if (pub) {
-                const double dn = msdp_group_sum_all<LPR>(rv.x * y.x + rv.y * y.y);
-                if (BSTORE) {
-                    row_store(2u, r, mdr);
-                    row_store(3u, r, make_double2(rv.x - y.x * dn, rv.y - y.y * dn));
-                } else if (OK(r)) {
-                    st2_sc1(rs_md, 2u * half_bytes + ROWB(r), mdr);
-                    st2_sc1(rs_md, 3u * half_bytes + ROWB(r), make_double2(rv.x - y.x * dn, rv.y - y.y * dn));
-                }
-                xr_push(r, 2u, mdr);
-                xr_push(r, 3u, make_double2(rv.x - y.x * dn, rv.y - y.y * dn));
-            }
             if (!SPLIT) {                                                                 // (round 5's order: all eight sums row by row)
                 const double2 g = Gs[r * PB + threadIdx.x], e0 = eta[r];
                 const double2 rg = make_double2(rv.x - g.x, rv.y - g.y);                  // Heta (:220)
@@ -883,6 +882,23 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
                 v[5] += mdr.x * rg.x + mdr.y * rg.y;                                      // <md, Heta>
                 v[6] += rv.x * rv.x + rv.y * rv.y;                                        // <r, r>      (:241 of the trip before)
                 v[7] += (e0.x * g.x + e0.y * g.y) + 0.5 * (e0.x * rg.x + e0.y * rg.y);    // model value (:227 of the trip before)
+            }
+        }
+        if (pub) {
+            // the refresh rows: md and tangent(r) of this trip's start, in a block of their own behind the rows of Hmd
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const double2 y = Ys[r * PB + threadIdx.x], mdr = md[r], rv = rr[r];
+                const double dn = msdp_group_sum_all<LPR>(rv.x * y.x + rv.y * y.y);
+                if (BSTORE) {
+                    row_store(2u, r, mdr);
+                    row_store(3u, r, make_double2(rv.x - y.x * dn, rv.y - y.y * dn));
+                } else if (OK(r)) {
+                    st2_sc1(rs_md, 2u * half_bytes + ROWB(r), mdr);
+                    st2_sc1(rs_md, 3u * half_bytes + ROWB(r), make_double2(rv.x - y.x * dn, rv.y - y.y * dn));
+                }
+                xr_push(r, 2u, mdr);
+                xr_push(r, 3u, make_double2(rv.x - y.x * dn, rv.y - y.y * dn));
             }
         }
         if (SPLIT) {
@@ -1001,6 +1017,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
         z_r = gg; d_Pd = gg; e_Pd = 0.0; e_Pe = 0.0; model_value = 0.0; alpha = 0.0; beta = 0.0;
         norm_r0 = sqrt(gg);
         j = 0; stop = 5; first = true; direct = false; have_x = false;
+        pub_cd = refresh > 0 ? refresh : 0;
     }
     first_tr = false;
     // (FUSE at 16 lanes per row: ONE instance of the trip loop -- with three of them inside the loop over the TR iterations the
@@ -1057,9 +1074,11 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
         const double2 he = make_double2(rr[r].x - g.x, rr[r].y - g.y);
         tv[2] += e0.x * (g.x + 0.5 * he.x) + e0.y * (g.y + 0.5 * he.y);
         const double2 x = make_double2(y.x + e0.x, y.y + e0.y);
-        double nn = sqrt(msdp_group_sum_all<LPR>(x.x * x.x + x.y * x.y));
-        if (!(nn > 0.0)) nn = 1.0;                                  // empty row slot
-        const double2 ypr = OK(r) ? make_double2(x.x / nn, x.y / nn) : zz;
+        // no select: a lane without columns holds x = 0 in a row whose norm is that of its live lanes, and a row slot past `hi`
+        // holds x = 0 in every lane -- its squared norm is raised from 0 to the smallest normal number, so 0 / nn is an exact zero
+        // and no NaN reaches LDS or the sums (a row that exists has the squared norm 1 + |eta|^2: the maximum changes nothing there)
+        const double nn = sqrt(fmax(msdp_group_sum_all<LPR>(x.x * x.x + x.y * x.y), 2.2250738585072014e-308));
+        const double2 ypr = make_double2(x.x / nn, x.y / nn);
         YPs[r * PB + threadIdx.x] = ypr;
         if (BSTORE) row_store(4u, r, ypr);
         else if (OK(r)) st2_sc1(rs_md, yx_base + ROWB(r), ypr);
@@ -1073,12 +1092,14 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
         if (!colok) acc = zz;
         const double2 ypr = YPs[r * PB + threadIdx.x];
         const double dot = msdp_group_sum_all<LPR>(acc.x * ypr.x + acc.y * ypr.y);
-        const double2 gpr = OK(r) ? make_double2(acc.x - ypr.x * dot, acc.y - ypr.y * dot) : zz;
+        // (no selects: a lane without a row or without columns holds acc = ypr = 0 and a finite dot -- 0 for a row slot past `hi`, whose
+        // vs[] are zero -- so its gradient row, its eG and its share of the cost are exact zeros without a select)
+        const double2 gpr = make_double2(acc.x - ypr.x * dot, acc.y - ypr.y * dot);
         GPs[r * PB + threadIdx.x] = gpr;
         tv[1] += gpr.x * gpr.x + gpr.y * gpr.y;
         if (sub == 0 && epi == 0) {
-            EGPs[SLOT(r)] = ROK(r) ? dot : 0.0;
-            if (ROK(r)) tv[0] += 0.5 * dot;
+            EGPs[SLOT(r)] = dot;
+            tv[0] += 0.5 * dot;
         }
         if (BSTORE) row_store(5u + (unsigned)(cur ^ 1), r, gpr);
         else if (OK(r)) st2_sc1(rs_md, gx_base + ROWB(r), gpr);

@@ -4,7 +4,8 @@ positions in the SDP (the non-marginalised form of SE-Sync / Cartan-Sync): ManiS
 Euclidean, d orthonormal rows and one free row per block of the factor (no multipliers, no penalty, no elimination of the
 positions).  The poses are then rounded on the host (problems.round_poses) and compared with the planted ones up to the global
 rotation and shift the problem cannot see (problems.pose_error).
-argv = [n, default 2000; d, default 3; degree, default 8; sigma_r, default 0.1; sigma_t, default 0.1; seed, default 0]."""
+argv = [n, default 2000; d, default 3; degree, default 8; sigma_r, default 0.1; sigma_t, default 0.1; seed, default 0]; --persist anywhere on the line: the tCG of every trust-region iteration as one
+persistent launch where the handle is eligible (options["block_persist"])."""
 import sys
 import time
 
@@ -13,6 +14,9 @@ import numpy as np
 import _common  # noqa: F401  (puts the repository root on sys.path)
 from manisdp_matlab_amd import problems, solvers
 
+persist = "--persist" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--persist"]
+
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
 d = int(sys.argv[2]) if len(sys.argv) > 2 else 3
 degree = int(sys.argv[3]) if len(sys.argv) > 3 else 8
@@ -20,7 +24,7 @@ sigma_r = float(sys.argv[4]) if len(sys.argv) > 4 else 0.1
 sigma_t = float(sys.argv[5]) if len(sys.argv) > 5 else 0.1
 C, R_true, t_true, edges, _, _ = problems.pose_graph(n, d, degree, sigma_r, sigma_t, int(sys.argv[6]) if len(sys.argv) > 6 else 0)
 t = time.time()
-Y, fval, data = solvers.ManiSDP_posegraph(C, d, {"tol": 1e-8})
+Y, fval, data = solvers.ManiSDP_posegraph(C, d, {"tol": 1e-8, "block_persist": persist})
 e = np.sqrt(np.maximum(np.linalg.eigvalsh(Y.T @ Y), 0.0))
 rank = int(np.sum(e >= 1e-3 * e.max()))
 R, pos = problems.round_poses(Y, d)

@@ -3,7 +3,8 @@
 unit-block-diagonal SDP: ManiSDP_onlyunitblockdiag runs it on the stacked Stiefel manifold of the factor (no multipliers, no
 penalty).  The rotations are then rounded on the host (problems.round_rotations) and compared with the planted ones up to the
 global rotation the problem cannot see (problems.rotation_error).
-argv = [n, default 2000; d, default 3; degree, default 8; sigma, default 0.5; seed, default 0]."""
+argv = [n, default 2000; d, default 3; degree, default 8; sigma, default 0.5; seed, default 0]; --persist anywhere on the line: the tCG of every trust-region iteration as one
+persistent launch where the handle is eligible (options["block_persist"])."""
 import sys
 import time
 
@@ -12,13 +13,16 @@ import numpy as np
 import _common  # noqa: F401  (puts the repository root on sys.path)
 from manisdp_matlab_amd import problems, solvers
 
+persist = "--persist" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--persist"]
+
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
 d = int(sys.argv[2]) if len(sys.argv) > 2 else 3
 degree = int(sys.argv[3]) if len(sys.argv) > 3 else 8
 sigma = float(sys.argv[4]) if len(sys.argv) > 4 else 0.5
 C, R_true, edges = problems.rotation_synchronization(n, d, degree, sigma, int(sys.argv[5]) if len(sys.argv) > 5 else 0)
 t = time.time()
-Y, fval, data = solvers.ManiSDP_onlyunitblockdiag(C, d, {"tol": 1e-8})
+Y, fval, data = solvers.ManiSDP_onlyunitblockdiag(C, d, {"tol": 1e-8, "block_persist": persist})
 e = np.sqrt(np.maximum(np.linalg.eigvalsh(Y.T @ Y), 0.0))
 rank = int(np.sum(e >= 1e-3 * e.max()))
 R = problems.round_rotations(Y, d)

@@ -651,18 +651,35 @@ int msdp_block_reshape(msdp_handle h, int32_t nb, const int64_t* row0, const int
  *                       bit-reproducible run to run)
  *   "timing", "esc_debug"  1/0  diagnostics on stderr                                (env MSDP_TIMING, MSDP_ESC_DEBUG)
  *   "debug_fail_persist"   1    test hook: the next persistent launch reports a synchronisation time-out
+ *   "block_persist"  1/0  unit-block-diagonal and pose-graph handles: the tCG of a trust-region iteration runs as ONE persistent
+ *                       launch (msdp_blockpersist.hip: the vectors of a block in registers, two grid reductions and one barrier per
+ *                       trip) where a plan exists -- width p <= 32, every block in one of at most two row slots of at most
+ *                       min(256, CUs) workgroups -- and "persist" is on; retraction, cost / gradient, decision and one host
+ *                       synchronisation per iteration as before.  Default 0: the three launches per trip of the generic path.
+ *                       Same tCG.m:95-292; sums in another order (results agree to rounding).  A launch whose workgroups cannot
+ *                       synchronise gives up and the call is repeated on the generic path, as for "persist"
+ *   "block_persist_grid"  n  cap on the workgroups of that launch (0 = planned; tests and tuning: a small grid takes the two-slot
+ *                       instances at a few hundred blocks)
+ *   "block_persist_wide"  1/0  A/B switch of that launch: 1 = the largest grid the plan allows at its row slots (the blocks spread
+ *                       over more compute units), 0 (default) = the fewest workgroups that need those row slots
  * The environment variables are read once, when the handle is created.  Unknown names -> MSDP_EINVAL. */
 int msdp_set_option(msdp_handle h, const char* name, int32_t value);
 
 /* Which implementation msdp_rtr uses for the tCG inner loop at the resident point:
  * 1 = persistent single-launch kernel (working set in registers/LDS, sparse C, oblique,
- * one rank, n and p small enough to stay on chip), 0 = chunked hipGraph of three kernels
+ * one rank, n and p small enough to stay on chip; or a block kind with the option "block_persist"), 0 = chunked hipGraph of three kernels
  * per trip.  Both follow tCG.m:95-292; the choice is a speed matter only. */
 int msdp_tcg_path(msdp_handle h, int32_t* path);
 /* (test / diagnostic) The trip form of the persistent kernel at the resident point: 2 = ONE grid reduction per trip (option
  * "persist_pipe", rows of <= 8 entries or shared CSR rows, p <= 32, every vector in registers), 1 = the "persist_early" form, 0 = two reductions per
  * trip (tCG.m:166 and :227-241 separately); -1 = the tCG is not persistent.  All forms follow tCG.m:95-292. */
 int msdp_debug_persist_form(msdp_handle h, int32_t* form);
+/* The same for the persistent kernel of the block kinds (option "block_persist"): 0 = two reductions per trip where it applies to
+ * the handle at its resident width, else -1. */
+int msdp_debug_block_persist_form(msdp_handle h, int32_t* form);
+/* (test / diagnostic) Its plan at the resident width: out[0] 1 = the kernel applies (option on, plan, co-residency), out[1] lanes
+ * per block, out[2] workgroups, out[3] row slots per lane group, out[4] dynamic LDS bytes; out[1..4] = 0 where no plan exists. */
+int msdp_debug_block_persist_plan(msdp_handle h, int32_t* out);
 /* (test / diagnostic) What the set-up of a primal affine handle (MSDP_KIND_UNITDIAG, _UNITTRACE, _GENERIC) planned from the constraint
  * data, and which branch the last calls took.  Host only: no launch, the handle is not modified.  out[0..15]:
  *    0 usym      1 = c and every A_k are symmetric entry by entry (upper view, tiled adjoint, B route possible)

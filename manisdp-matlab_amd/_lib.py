@@ -140,6 +140,8 @@ SIGNATURES = {
     "msdp_debug_shard": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "msdp_tcg_path": (C.c_int, [C.c_void_p, _P(C.c_int32)]),
     "msdp_debug_persist_form": (C.c_int, [C.c_void_p, _P(C.c_int32)]),
+    "msdp_debug_block_persist_form": (C.c_int, [C.c_void_p, _P(C.c_int32)]),
+    "msdp_debug_block_persist_plan": (C.c_int, [C.c_void_p, _P(C.c_int32)]),
     "msdp_debug_affine_plan": (C.c_int, [C.c_void_p, _P(C.c_int32)]),
     "msdp_point_snapshot": (C.c_int, [C.c_void_p]),
     "msdp_point_restore": (C.c_int, [C.c_void_p]),
@@ -921,7 +923,15 @@ class Handle:
         """Trip form of the persistent tCG kernel: 2 one grid reduction per trip, 1 early gather, 0 two reductions, -1 not persistent."""
         v = C.c_int32()
         _check(self._lib.msdp_debug_persist_form(self._h, C.byref(v)))
+        if v.value < 0:                                    # the block kinds' kernel (option "block_persist") is a unit of its own
+            _check(self._lib.msdp_debug_block_persist_form(self._h, C.byref(v)))
         return v.value
+
+    def block_persist_plan(self):
+        """Plan of the block kinds' persistent tCG at the resident width (msdp_debug_block_persist_plan), as a dict."""
+        v = (C.c_int32 * 5)()
+        _check(self._lib.msdp_debug_block_persist_plan(self._h, v))
+        return dict(zip(("eligible", "lpr", "grid", "slots", "lds"), (int(x) for x in v)))
 
     def affine_plan(self):
         """What the set-up of a primal affine handle planned and which branch the last Hess-vec / A(.) took, as a dict

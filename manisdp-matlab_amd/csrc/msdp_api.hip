@@ -1041,6 +1041,9 @@ extern "C" int msdp_set_option(msdp_handle h, const char* name, int32_t value) {
     else if (!strcmp(name, "dense_sym_len")) { t.dense_sym_len = value > 0 ? value : 0; h->chunk_len = 0; return dense_rereserve(h); }
     else if (!strcmp(name, "blk_groups")) t.blk_groups = value > 0 ? (value > 16 ? 16 : value) : 0;
     else if (!strcmp(name, "debug_fail_persist")) t.fail_persist = value != 0;
+    else if (!strcmp(name, "block_persist")) { if (value < 0 || value > 1) { msdp_set_error("block_persist: 0 or 1"); return MSDP_EINVAL; } t.block_persist = value; }
+    else if (!strcmp(name, "block_persist_grid")) t.block_persist_grid = value > 0 ? value : 0;
+    else if (!strcmp(name, "block_persist_wide")) t.block_persist_wide = value != 0;
     else if (!strcmp(name, "debug_xr_skip")) t.fail_xr = value != 0;
     else if (!strcmp(name, "debug_fail_block")) t.fail_block = value != 0;
     else if (!strcmp(name, "grid")) { t.grid = value > 0 ? value : 0; choose_grid(h); h->chunk_len = 0; }

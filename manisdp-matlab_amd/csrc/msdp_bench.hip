@@ -218,6 +218,37 @@ extern "C" int msdp_bench_tcg_trip(msdp_handle h, int32_t reps, double* avg_ms) 
         if (perr) { msdp_set_error("persistent tCG: grid synchronisation timed out"); return MSDP_EHIP; }
         return rc ? rc : rc2;
     }
+    if (msdp_blockpersist_eligible(h)) {
+        // block kinds, option "block_persist": the same measurement of msdp_blockpersist.hip (run twice, time the second)
+        h->h_ctl->maxinner = reps;
+        if ((rc = msdp_push_ctl(h))) return rc;
+        if ((rc = msdp_launch_costgrad(h, msdp_host_cur(h)))) return rc;
+        if ((rc = msdp_launch_rtr_begin(h))) return rc;
+        rc = msdp_launch_tcg_blockpersist(h, 1);
+        if (!rc) {
+            hipError_t e1 = hipEventRecord(h->ev0, h->stream);
+            rc = msdp_launch_tcg_blockpersist(h, 0);
+            hipError_t e2 = hipEventRecord(h->ev1, h->stream);
+            hipError_t e3 = hipEventSynchronize(h->ev1);
+            float ms = 0.f;
+            hipError_t e4 = hipEventElapsedTime(&ms, h->ev0, h->ev1);
+            if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess) { msdp_set_error("bench events failed"); rc = MSDP_EHIP; }
+            *avg_ms = (double)ms / reps;
+        }
+        h->h_ctl->bench_mode = 0;
+        h->h_ctl->done = 0;
+        int rc2 = msdp_push_ctl(h);
+        HIPCHK(hipStreamSynchronize(h->stream));
+        h->state_valid = false;
+        int perr = 0;
+        HIPCHK(msdp_memcpy(&perr, h->psync_err, sizeof(int), hipMemcpyDeviceToHost));
+        if (perr) {
+            HIPCHK(hipMemset(h->psync_err, 0, sizeof(int)));
+            msdp_set_error("persistent tCG (%s kind): grid synchronisation timed out", msdp_block_kind_name(h->d.efree));
+            return MSDP_EHIP;
+        }
+        return rc ? rc : rc2;
+    }
     if (h->use_comm && h->lgroup && h->nranks > 1 && h->d.costkind == COST_SPARSE) {
         // in-process ranks: the cross-rank persistent tCG when every member can run it (`reps` trips, exits disabled, one launch per
         // member; run twice, time the second) -- every member calls this function together

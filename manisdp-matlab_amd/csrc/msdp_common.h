@@ -274,6 +274,10 @@ struct Tuning {
     int fail_xr = 0;       // test hook ("debug_xr_skip"): this member skips its next cross-rank persistent launch
     int fail_persist = 0;  // test hook (msdp_set_option "debug_fail_persist"): the next persistent launch reports a
                            //   grid-synchronisation time-out without running, to exercise the recovery path
+    int block_persist = 0;       // block kinds (MANI_STIEFEL / COST_BLOCK): the tCG of a TR iteration in one persistent launch
+                                 //   (msdp_blockpersist.hip) where a plan exists; 0 (default): the generic three-launch trips
+    int block_persist_grid = 0;  // ... cap on its workgroups (0: planned; tests and tuning: a small grid takes the two-slot instances)
+    int block_persist_wide = 0;  // ... A/B: 1 = the largest grid the plan allows at its row slots, not the fewest workgroups
 };
 
 struct msdp_handle_s {
@@ -372,6 +376,9 @@ struct msdp_handle_s {
     int persist_sig_lpr = 0, persist_sig_ew = 0, persist_sig_r = 0, persist_sig_G = 0, persist_sig_ok = 0;
     const void* persist_sig_fn = nullptr; const void* fused_sig_fn = nullptr;     // the kernel instance the cached answers are for
     int fused_sig_lpr = 0, fused_sig_ew = 0, fused_sig_G = 0, fused_sig_ok = 0;
+    // persistent tCG kernel of the block kinds (msdp_blockpersist.hip): cached eligibility, the slot region of the next launch
+    const void* blkpersist_sig_fn = nullptr; int blkpersist_sig_G = 0, blkpersist_sig_ok = 0; size_t blkpersist_sig_lds = 0;
+    int blkpersist_region = 0;
 };
 
 #define MSDP_CHECK_H(h)                                     \
@@ -517,6 +524,10 @@ int msdp_launch_tcg_xpersist_one(hipStream_t stream, const Dev& dv, const int* p
 size_t msdp_xr2_block_bytes();
 size_t msdp_xr2_err_offset();
 int msdp_xr2_reset(hipStream_t stream, unsigned long long* blk);
+// msdp_blockpersist.hip
+int msdp_blockpersist_eligible(msdp_handle h);                // the persistent tCG of the block kinds applies (option "block_persist")
+int msdp_blockpersist_plan_of(msdp_handle h, int* lpr, int* G, int* R, size_t* lds);   // its plan at the resident width (returns 0: none)
+int msdp_launch_tcg_blockpersist(msdp_handle h, int reset_slots);   // whole tCG of the current TR iteration, one launch
 // msdp_trtail.hip
 int msdp_launch_tr_tail(msdp_handle h);                       // retract + cost/grad at the proposal + accept/reject, one launch
 int msdp_launch_tr_tail_xr(hipStream_t stream, const Dev& dv, unsigned long long* slots, int* err);

@@ -415,6 +415,67 @@ __device__ __forceinline__ void spmm_block(const Dev& d, int blk, int sub, const
     }
 }
 
+// The same gather (one double2 per lane and row, NCH = 1) where the rows of X are read through an accessor of the caller:
+// ldx(byte offset) -> double2.  The persistent kernel of the block kinds (msdp_blockpersist.hip) gathers rows that other
+// workgroups stored during the same launch and passes the agent-coherent load of msdp_psync.h; a plain ld2 may see an XCD's
+// stale L2 line there.  [k0, k1) = the entries of the block row (empty for a lane group without a block), col_bytes = the byte
+// offset of the lane's columns in a row, ld = the row stride in doubles.  Entries and products in the order of spmm_block.
+// CB entries are in flight together: their CB column indices are loaded first, then their CB * D rows, and only then the
+// values row by row -- a chain of two dependent round trips per BATCH where a loop over single entries pays them per entry (the
+// caller holds the vectors of its blocks in registers and runs two waves per SIMD: nothing else hides the latency).  The tail
+// of the last batch reads the row's last entry again and leaves it out of the sums.
+typedef double msdp_d2u __attribute__((ext_vector_type(2), aligned(8)));      // two doubles at an 8-byte aligned address
+template <int D, int CB, class LoadX>
+__device__ __forceinline__ void spmm_block_via(const Dev& d, int k0, int k1, unsigned col_bytes, unsigned ld, LoadX ldx, double2 (&acc)[D]) {
+    const int* __restrict__ ci = d.bci;
+    const double* __restrict__ cv = d.bval;
+    for (int k = k0; k < k1; k += CB) {
+        int j[CB];
+#pragma unroll
+        for (int u = 0; u < CB; ++u) j[u] = ci[k + u < k1 ? k + u : k1 - 1];
+        double2 x[CB][D];
+#pragma unroll
+        for (int u = 0; u < CB; ++u)
+#pragma unroll
+            for (int b = 0; b < D; ++b) x[u][b] = ldx(((unsigned)j[u] * (unsigned)D + (unsigned)b) * ld * 8u + col_bytes);
+#pragma unroll
+        for (int u = 0; u < CB; ++u) {
+            if (k + u < k1) {
+                // the D * D values of the entry, two doubles per load: every lane of a group reads the same addresses, and a wave
+                // of 64 / LPR groups touches as many lines per load instruction -- the count of these instructions is what the
+                // gather costs.  Even D: row by row (the caller's registers are full), 16-byte aligned pairs; odd D: the entry's
+                // values as one run of D * D doubles, 8-byte aligned pairs and a last single
+                const double* __restrict__ ce = cv + (int64_t)(k + u) * (D * D);
+                if (D % 2 == 0) {
+#pragma unroll
+                    for (int a = 0; a < D; ++a) {
+                        double c[D];
+#pragma unroll
+                        for (int b = 0; b < D; b += 2) { const double2 cc = ld2(ce + a * D + b); c[b] = cc.x; c[b + 1 < D ? b + 1 : b] = cc.y; }
+#pragma unroll
+                        for (int b = 0; b < D; ++b) {
+                            acc[a].x = fma(c[b], x[u][b].x, acc[a].x);
+                            acc[a].y = fma(c[b], x[u][b].y, acc[a].y);
+                        }
+                    }
+                } else {
+                    double c[D * D];
+#pragma unroll
+                    for (int q = 0; q + 1 < D * D; q += 2) { const msdp_d2u cc = *reinterpret_cast<const msdp_d2u*>(ce + q); c[q] = cc.x; c[q + 1] = cc.y; }
+                    c[D * D - 1] = ce[D * D - 1];
+#pragma unroll
+                    for (int a = 0; a < D; ++a)
+#pragma unroll
+                        for (int b = 0; b < D; ++b) {
+                            acc[a].x = fma(c[a * D + b], x[u][b].x, acc[a].x);
+                            acc[a].y = fma(c[a * D + b], x[u][b].y, acc[a].y);
+                        }
+                }
+            }
+        }
+    }
+}
+
 // T = sym(A B') of two D-row blocks held by a lane group: T[a][b] = (<A_a, B_b> + <A_b, B_a>) / 2, D (D + 1) / 2 group sums;
 // the same bits in every lane of the group
 template <int D, int LPR, int NCH>

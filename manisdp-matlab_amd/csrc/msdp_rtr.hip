@@ -19,7 +19,7 @@ extern "C" int msdp_tcg_path(msdp_handle h, int32_t* path) {
     MSDP_CHECK_H(h);
     if (!path) return MSDP_EINVAL;
     if (!h->have_point) { msdp_set_error("tcg_path: no resident point"); return MSDP_ESTATE; }
-    *path = msdp_persist_eligible(h) ? 1 : ((h->use_comm && h->lgroup && h->xpersist_last) ? 2 : 0);   // 2: the last call ran the cross-rank persistent tCG
+    *path = (msdp_persist_eligible(h) || msdp_blockpersist_eligible(h)) ? 1 : ((h->use_comm && h->lgroup && h->xpersist_last) ? 2 : 0);   // 2: the last call ran the cross-rank persistent tCG
     return 0;
 }
 
@@ -439,6 +439,15 @@ static int rtr_core(msdp_handle h, const msdp_rtr_opts* opts, bool* timed_out) {
             if (xp && (rc = msdp_xr_begin(h, &xp))) return rc;
         }
         h->xpersist_last = xp;
+        // block kinds with the option "block_persist": the tCG of an iteration is ONE launch (msdp_blockpersist.hip) in place of the
+        // chunked trips; retraction, cost / gradient, decision and the host synchronisation stay as they are
+        const bool bp = msdp_blockpersist_eligible(h) != 0;
+        if (bp && h->tune.fail_persist) {                            // test hook: behave as if the launch had timed out
+            h->tune.fail_persist = 0;
+            *timed_out = true;
+            return 0;
+        }
+        bool bp_first = true;
         while (!h->h_ctl->done) {                                     // trustregions.m:441
             cur = h->h_ctl->cur;
             const auto ta = std::chrono::steady_clock::now();
@@ -447,6 +456,7 @@ static int rtr_core(msdp_handle h, const msdp_rtr_opts* opts, bool* timed_out) {
                 rc = msdp_xr_launch(h);
                 msdp_restore_status_ptr(h);
             }
+            else if (bp) { rc = msdp_launch_tcg_blockpersist(h, bp_first ? 1 : 0); bp_first = false; }
             else if (h->use_comm) rc = run_tcg_lockstep(h, opts->maxinner);
             else rc = run_tcg(h, opts->maxinner, h->h_ctl->k);        // :495
             if (rc) return rc;
@@ -469,7 +479,10 @@ static int rtr_core(msdp_handle h, const msdp_rtr_opts* opts, bool* timed_out) {
                 if ((rc = msdp_launch_costgrad(h, cur ^ 1))) return rc;   // :544
                 if ((rc = msdp_launch_rtr_decide(h))) return rc;          // :548-729
             }
-            if ((rc = pull_ctl(h))) return rc;
+            if (bp) {
+                if ((rc = pull_ctl_and_err(h, timed_out))) return rc;
+                if (*timed_out) return 0;
+            } else if ((rc = pull_ctl(h))) return rc;
             if (xp && (rc = msdp_xr_check(h))) return rc;
             const auto tc = std::chrono::steady_clock::now();
             t_tcg += std::chrono::duration<double>(tb - ta).count();
@@ -479,7 +492,7 @@ static int rtr_core(msdp_handle h, const msdp_rtr_opts* opts, bool* timed_out) {
     if (timing) {
         fprintf(stderr, "[msdp_rtr] enqueue total %.3f ms, slowest %.3f ms\n", t_enq_sum * 1e3, t_enq_max * 1e3);
         fprintf(stderr, "[msdp_rtr] p=%d ld=%d G=%d path=%d k=%d hessvecs=%d acc=%d rej=%d  tCG phase %.3f ms  (retract+cost+decide+sync) %.3f ms\n",
-                h->d.p, h->d.ld, h->d.G, persist ? 1 : 0, h->h_ctl->k, h->h_ctl->hessvecs,
+                h->d.p, h->d.ld, h->d.G, (persist || msdp_blockpersist_eligible(h)) ? 1 : 0, h->h_ctl->k, h->h_ctl->hessvecs,
                 h->h_ctl->accepted, h->h_ctl->rejected, t_tcg * 1e3, t_rest * 1e3);
     }
     return 0;
@@ -499,7 +512,7 @@ extern "C" int msdp_rtr(msdp_handle h, const msdp_rtr_opts* opts, msdp_rtr_stats
     // bounded spin.  Keep a copy of the start point so that the call can be repeated on the chunked path.
     const int cur0 = h->h_ctl->cur;
     const size_t cnt = (size_t)msdp_rows_capacity(h) * h->ldcap;
-    const bool guard = h->d.costkind == COST_SPARSE && !h->use_comm && msdp_persist_eligible(h);
+    const bool guard = (h->d.costkind == COST_SPARSE && !h->use_comm && msdp_persist_eligible(h)) || msdp_blockpersist_eligible(h);
     if (guard) {
         if (h->rtr_start_cap < cnt) {
             if (h->rtr_start) msdp_dev_free(h, h->rtr_start);

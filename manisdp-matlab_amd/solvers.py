@@ -616,6 +616,8 @@ def ManiSDP_onlyunitblockdiag(C, d, options=None, verbose=True, rng=None):
     from the device escape, with the independent cold check before "Optimality is reached!", above that (options["eig"]).
     The rank decision is that of the reference (Y'Y); the factor is cut to r columns only when d <= r <= p - 1, widened by
     [Y, alpha V(:, 1:nne)], and after either step every block is re-orthonormalised on the host by its polar factor.
+    ``options["block_persist"] = True`` runs the tCG of every trust-region iteration as one persistent launch where the handle
+    is eligible (p <= 32; msdp_set_option "block_persist"), the generic trips elsewhere; default False.
     ``line_search = 1``, ``device_factor``, ``round`` and ``comm`` raise ValueError before the library is loaded."""
     with _host_threads():
         return _onlyunitblockdiag_impl(C, d, options, verbose, rng)
@@ -663,6 +665,8 @@ def _onlyunitblockdiag_impl(C, d, options, verbose, rng):
     Y = np.ascontiguousarray(Y, dtype=np.float64)
     p = Y.shape[1]
     h = _lib.Handle.onlyunitblockdiag(Csp, d, pcap=min(256, max(32, p + 2 * delta)))
+    if o.get("block_persist"):                             # the tCG of a TR iteration in one persistent launch where it applies
+        h.set_option("block_persist", 1)
     for name, value in (o.get("device_options") or {}).items():
         h.set_option(name, int(value))
     topts = _rtr_opts(o)
@@ -783,6 +787,7 @@ def ManiSDP_posegraph(C, d, options=None, verbose=True, rng=None):
 
     Returns (Y, obj, data); ``data["Lambda"]`` holds the multiplier blocks (n, d, d), S = C - blockdiag(Lambda_i (+) 0).  For a
     pose-graph C the global shift is in the null space of S, so lambda_min of a certified point is 0.
+    ``options["block_persist"]`` as for ManiSDP_onlyunitblockdiag.
     ``line_search = 1``, ``device_factor``, ``round`` and ``comm`` raise ValueError before the library is loaded."""
     with _host_threads():
         return _posegraph_impl(C, d, options, verbose, rng)
@@ -830,6 +835,8 @@ def _posegraph_impl(C, d, options, verbose, rng):
     Y = np.ascontiguousarray(Y, dtype=np.float64)
     p = Y.shape[1]
     h = _lib.Handle.posegraph(Csp, d, pcap=min(256, max(32, p + 2 * delta)))
+    if o.get("block_persist"):                             # the tCG of a TR iteration in one persistent launch where it applies
+        h.set_option("block_persist", 1)
     for name, value in (o.get("device_options") or {}).items():
         h.set_option(name, int(value))
     topts = _rtr_opts(o)

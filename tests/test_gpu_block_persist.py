@@ -2,7 +2,9 @@
 per-iteration path of the same handle and the NumPy restatements (tests/blockdiag_ref.py, tests/posegraph_ref.py): counts,
 points and tCG invariants over every lanes-per-block instance and both row-slot counts, the pose rows, ineligible handles,
 the fall-back after a time-out, whole solves and the benchmark hook.  tests/test_block_persist_cases_host.py shows on the CPU
-that the counts of every case used here do not move under 1e-14 perturbations of the start.
+that the counts of every case used here do not move under 1e-14 perturbations of the start.  Every run that is meant to be
+persistent asserts the kernel instance the plan selects (K.plan_of, the ledger of tests/block_persist_cases.py) before and
+tcg_path() == 1 after it: a launch that timed out and was repeated on the chunked path would leave 0 there.
 
 The yardstick of a rounding-level figure is the EXISTING path: with e_gen and e_per the errors of the generic and of the
 persistent path against the restatement, e_per <= max(10 e_gen, 1e-12) -- the factor for another summation order of two
@@ -56,6 +58,15 @@ def _rtr(lib, h, Y0, maxiter, maxinner=K.MAXINNER, tol=K.TOLGRADNORM, **more):
     return st, h.get_point()
 
 
+def _planned(h, kind, n, d, p, grid, wide=0):
+    """The handle is on the persistent path with exactly the plan of the ledger: lanes per block, row slots and grid."""
+    assert h.tcg_path() == 1 and h.persist_form() == 0, (kind, n, d, p, grid)
+    plan, want = h.block_persist_plan(), K.plan_of(kind, n, d, p, grid, wide=wide)
+    assert want is not None and plan["eligible"] == 1, (kind, n, d, p, grid, plan)
+    assert {k: plan[k] for k in ("lpr", "slots", "grid", "lds")} == {k: want[k] for k in ("lpr", "slots", "grid", "lds")}, (kind, n, d, p, grid, plan, want)
+    return plan
+
+
 # ------------------------------------------------------------------ 1. counts
 @pytest.mark.parametrize("kind", ["stiefel", "pose"])
 def test_count_case_on_the_persistent_path(lib, kind):
@@ -81,13 +92,13 @@ def test_count_case_on_the_persistent_path(lib, kind):
 
 
 # ------------------------------------------------------------------ 2. shape sweep
-@pytest.mark.parametrize("kind", ["stiefel", "pose"])
-@pytest.mark.parametrize("n,d", K.SHAPES)
-def test_sweep_against_the_generic_path_and_the_restatement(lib, kind, n, d):
+def _sweep(lib, kind, n, d, ps):
+    """Three iterations from K.start at every width of ps on the generic path, the planned grid and the grid capped at 8:
+    counts against the restatement, cost, point and the tCG invariants by the rule."""
     C = K.matrix(kind, n, d)
     h = _handle(lib, kind, C, d)
     try:
-        for p in K.widths(d):
+        for p in ps:
             Y0 = K.start(kind, n, d, p)
             Y_ref, f_ref, info = K.restatement(kind, n, d, p)
             _select(h, False)
@@ -105,16 +116,17 @@ def test_sweep_against_the_generic_path_and_the_restatement(lib, kind, n, d):
             for grid in (0, 8):
                 _select(h, True, grid)
                 h.set_point(Y0)
-                assert h.tcg_path() == 1 and h.persist_form() == 0, (p, grid)
-                plan = h.block_persist_plan()
-                assert plan["eligible"] == 1 and plan["grid"] % 8 == 0 and plan["slots"] in (1, 2)
+                plan = _planned(h, kind, n, d, p, grid)
+                assert plan["grid"] % 8 == 0 and plan["slots"] in (1, 2)
                 if grid == 8:
                     assert plan["grid"] == 8
                     if n == 343 and p >= 17:
                         assert plan["slots"] == 2 and plan["lpr"] == 16      # 343 blocks on 8 workgroups of 32 per slot
                 st_p, Y_p = _rtr(lib, h, Y0, K.MAXITER)
+                assert h.tcg_path() == 1, (p, grid)
                 e_per = _relerr(Y_p, Y_ref)
                 _rtr(lib, h, Y0, 1)
+                assert h.tcg_path() == 1, (p, grid)
                 eta, heta = h.debug_get_tcg_step()
                 _select(h, False)
                 h.set_point(Y0)
@@ -129,6 +141,12 @@ def test_sweep_against_the_generic_path_and_the_restatement(lib, kind, n, d):
                 assert _rule(tan_p, tan_g), (p, grid, tan_p, tan_g)
     finally:
         h.close()
+
+
+@pytest.mark.parametrize("kind", ["stiefel", "pose"])
+@pytest.mark.parametrize("n,d", K.SHAPES)
+def test_sweep_against_the_generic_path_and_the_restatement(lib, kind, n, d):
+    _sweep(lib, kind, n, d, K.widths(d))
 
 
 @pytest.mark.parametrize("case", K.LONG_CASES)
@@ -147,10 +165,11 @@ def test_long_cases_counts_and_cost(lib, case):
             _select(h, True, grid)
             h.set_option("block_persist_wide", wide)
             h.set_point(Y0)
-            assert h.tcg_path() == 1
+            plan = _planned(h, kind, n, d, p, grid, wide)
             if wide:
-                assert h.block_persist_plan()["grid"] >= 64                  # more workgroups than blocks per slot need: empty chunks too
+                assert plan["grid"] >= 64                                    # more workgroups than blocks per slot need: empty chunks too
             st_p, Y_p = _rtr(lib, h, Y0, maxiter)
+            assert h.tcg_path() == 1, (grid, wide)
             print(case, "grid", grid, "wide", wide, "device", _dev_counts(st_p), st_p.cost, "restatement", K.counts(info), f_ref)
             assert _dev_counts(st_p) == K.counts(info)
             assert abs(st_p.cost - f_ref) <= 1e-11 * abs(f_ref)
@@ -183,6 +202,9 @@ def test_zero_free_rows_equal_the_persistent_stiefel_kind(lib, n, d, degree):
         for on in (False, True):
             for hh in (h, hs):
                 _select(hh, on, 8 if on else 0)
+            if on:
+                h.set_point(Y); hs.set_point(Yr)
+                _planned(h, "pose", n, d, p, 8); _planned(hs, "stiefel", n, d, p, 8)
             st, Yp = _rtr(lib, h, Y, K.MAXITER, **radius)
             eta, heta = h.debug_get_tcg_step()
             sts, Ys = _rtr(lib, hs, Yr, K.MAXITER, **radius)
@@ -286,10 +308,14 @@ def test_bench_hook_leaves_the_handle_usable(lib, kind):
             _select(h, on)
             h.set_point(Y0)
             assert h.tcg_path() == (1 if on else 0)
+            if on:
+                _planned(h, kind, n, d, p, 0)
             t = h.bench_tcg_trip(64)
+            assert h.tcg_path() == (1 if on else 0)
             print("%s trip, block_persist %d: %.2f us" % (kind, on, t * 1e3))
             assert t > 0
             st, _ = _rtr(lib, h, Y0, K.MAXITER)
+            assert h.tcg_path() == (1 if on else 0)
             assert _dev_counts(st) == K.counts(info)
     finally:
         h.close()

@@ -4,6 +4,7 @@
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Imanisdp-matlab_amd/csrc
 //       tools/block_persist_plan_selftest.cpp -o $OUT/block_persist_plan_selftest && $OUT/block_persist_plan_selftest
 #include <cstdio>
+#include <string>
 #include <vector>
 #include "msdp_blockpersist_plan.h"
 
@@ -36,7 +37,19 @@ static int brute_slots(int nb, int B, int efree, int lpr, int gmax) {
     return 0;
 }
 
-int main() {
+// --plans: the header's answer to the queries "nb B efree p cus cap wide" of the standard input, one line "ok lpr G R rstep lds"
+// each (tests/test_block_persist_cases_host.py holds the Python restatement of the plan to them)
+static int print_plans() {
+    int nb, B, ef, p, cus, cap, wide;
+    while (std::scanf("%d %d %d %d %d %d %d", &nb, &B, &ef, &p, &cus, &cap, &wide) == 7) {
+        const BlockPersistPlan pl = msdp_blockpersist_plan(nb, B, ef, p, cus, cap, wide);
+        std::printf("%d %d %d %d %d %zu\n", pl.ok, pl.lpr, pl.G, pl.R, pl.rstep, pl.lds);
+    }
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1 && std::string(argv[1]) == "--plans") return print_plans();
     const int Bs[4] = {2, 3, 3, 4}, EFs[4] = {0, 0, 1, 1};
     const int CUs[3] = {64, 256, 304}, CAPs[3] = {0, 8, 16};
     std::vector<int> nbs;

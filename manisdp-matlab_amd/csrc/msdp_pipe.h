@@ -533,6 +533,19 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
     const unsigned gld = (unsigned)d.ld;
     constexpr bool LOC = !CSR && R * EW <= 15;                     // (four row slots: the source selection costs registers that spill)
     constexpr bool MULTI = LOC && !(FUSE && LPR >= 16);            // three instances of the trip loop (per-wave local columns), see below
+    // PARK (round 10): the fused launch at 16 lanes per row keeps the two product recurrences in LDS between trips.  cmd[] and ctr[] are
+    // touched once per trip (the products block and the H md loop) and are dead weight -- 24 registers -- from the row stores through the
+    // reduction and the new direction to the next trip's products: exactly the stretch over which the 15 gathered rows of the NEXT trip
+    // (X[3][5], 60 registers) are in flight once the gather is requested from the reduction on (SPREAD below): held in registers they
+    // cost the trip spills (152 bytes of scratch with the requests in one batch, rounds 6 and 10).  Their home is the space of
+    // HQs, which only the MULTI instances use: element r * PB + threadIdx.x of two [R][PB] arrays.  A lane reads only what it wrote
+    // (LDS accesses of one wave are performed in order): no barrier.  Every trip writes both slots at the top of its H md loop -- the
+    // first trip of a tCG what its gather formed, a refresh trip what its direct gathers formed -- and only a trip that is neither
+    // reads them, so neither set-up nor the reset at the start of a tCG has anything to write there.
+    constexpr bool PARK = FUSE && LPR == 16 && EW == 5 && R == 3;        // (a FUSE instance is one-rank: static_assert above)
+    static_assert(!PARK || !MULTI, "the parked recurrences live in HQs: the instance must not keep its rows of H md there");
+    double2* CTs = HQs;                                            // PARK: [R][PB] C tangent(r)
+    double2* CMs = HQs + R * PB;                                   // PARK: [R][PB] C md
     double2 eta[R], rr[R], md[R], hmd[R], cmd[R], ctr[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -737,6 +750,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
 
     double z_r = gg, d_Pd = gg, e_Pd = 0.0, e_Pe = 0.0, model_value = 0.0, alpha = 0.0, beta = 0.0;
     double norm_r0 = sqrt(gg);
+    double nr0t_tcg = norm_r0;                                     // PARK: norm_r0 ^ theta of the running tCG (set where the tCG starts)
     int j = 0, stop = 5;
     int pub_cd = refresh > 0 ? refresh : 0;                        // trips until the next refresh trip (0: never); restarts with every tCG
     // TRACE && FUSE (msdp_debug_persist_trace with reps <= 0): thread 0 of every workgroup stamps the phases of the first MSDP_TRACE_NJ TR
@@ -759,14 +773,28 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
   auto trips = [&](auto nlc) {
     constexpr int NL = decltype(nlc)::value;                       // columns [0, NL) from LDS, [NL, EW) through the buffer
     constexpr int NG = EW - NL;
-    // the next trip's rows requested inside the reduction: where they are few enough to stay in flight across the trip's arithmetic
-#ifndef MSDP_PIPE_VARIANT
-#define MSDP_PIPE_VARIANT 0
-#endif
-    constexpr bool PREF = !CSR && R * NG <= ((FUSE && MSDP_PIPE_VARIANT == 0) ? 9 : 15);
-    // SPLIT: the four sums without H md under the gather, the other four behind the row stores (A/B builds: variant 1 = the gather
-    // prefetched in the fused launch too, round 5's order; variant 2 = prefetched AND split)
-    constexpr bool SPLIT = (MSDP_PIPE_VARIANT == 2 && FUSE) ? true : !PREF;
+    // the next trip's rows requested inside the reduction, in ONE batch: where they are few enough to stay in flight across the trip's
+    // arithmetic (the fused launch: 9 rows)
+    constexpr bool PREF = !CSR && R * NG <= (FUSE ? 9 : 15);
+    // SPREAD (round 10, the parked instance: all 15 rows through the buffer): the next trip's requests go out in five batches of three
+    // between the reduction and the loop's back edge -- behind the barrier that says every workgroup has posted (on_ready), behind the
+    // boundary test, behind the model test, in front of the new direction and behind it.  A wave is BLOCKED while its loads issue (the
+    // texture path takes a 16-byte-per-lane load every 16 cycles, 8 waves share it): all 15 in on_ready cost the reduction's tail what
+    // the top of the trip saves and more (192 500 Hess-vec/s against 210 150), all in the arithmetic likewise (205 500); three at a
+    // time with 15 to 70 VALU instructions between the batches 214 900 (medians of six alternating runs; the runs themselves are in
+    // profiles/r10_trip_instruction_counts.md).  One or two requests per place (a branch and an LDS read of the offset each) lose to
+    // batches of three.  Every batch is skipped in front of a refresh trip.
+    constexpr bool SPREAD = PARK;
+    // SPLIT: the four sums without H md under the gather, the other four behind the row stores: the instances whose gather is not
+    // requested in one batch inside the reduction
+    constexpr bool SPLIT = !PREF;
+    constexpr int NGD = NG > 0 ? NG : 1;
+    // requests ka .. kb - 1 of the R x NG of a trip, row slot by row slot, from region `base` of the exchange buffer
+#define PIPE_ISSUE_PART(base, ka, kb) do { \
+            _Pragma("unroll") for (int k = (ka); k < (kb); ++k) { \
+                const unsigned coff = (unsigned)cs[(NL + k % NGD) * ROWS + SLOT(k / NGD)]; \
+                X[k / NGD][k % NGD] = ld2_cp<XTWO ? 17 : MSDP_CPOL_SC1>(rs_md, (base) + (BOFF ? coff + gcol8 : (coff * gld + gcol) * 8u)); } } while (0)
+#define PIPE_SPREAD(ka, kb) do { if (SPREAD && !pub) PIPE_ISSUE_PART(xq * half_bytes, ka, kb); } while (0)
     double2 X[R][NG > 0 ? NG : 1];                                 // the gathered rows (in flight across the end of a trip)
     for (;;) {
         PTSTAMP(0);
@@ -797,8 +825,9 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
                 PIPE_ISSUE(rs, base, w0); \
                 _Pragma("unroll") for (int r = 0; r < R; ++r) PIPE_FOLDX(r, (dst)[r], w0); } \
             if (!colok) { _Pragma("unroll") for (int r = 0; r < R; ++r) (dst)[r] = zz; } } while (0)
-        // the eight partial sums of this trip's reduction.  Round 6, the instances that do NOT have the next gather requested inside the
-        // reduction (!PREF: the fused launch at 16 lanes per row): four sums -- <md, g>, <md, Heta>, <r, r>, the model value -- do not
+        // the eight partial sums of this trip's reduction.  Round 6, the instances that do NOT have the next gather requested in one
+        // batch inside the reduction (!PREF: the fused launch at 16 lanes per row, whose requests are spread from the reduction to the
+        // loop's back edge since round 10 -- the last rows are still on their way at the top of the trip): four sums -- <md, g>, <md, Heta>, <r, r>, the model value -- do not
         // involve H md and are formed while the gathers of this trip are in flight, the other four behind the rows of H md and their
         // stores (whose drain they run under): G81 p = 32, the fused launch 5 426 -> 5 137 us per call, 182 100 -> 192 400 Hess-vec/s.
         // With the gather prefetched the same order LOSES (the per-iteration <16, 5, 3> instance 4.82 -> 4.98 us per trip, <8, 5, 2>
@@ -832,6 +861,11 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
             // the neighbours' rows of last trip's Hmd: requested inside that trip's reduction already (have_x), except behind a refresh
             if (!CSR && !have_x) PIPE_ISSUE(rs_md, (xq ^ 1u) * half_bytes, NL);
             pre_sums();
+            // PARK: the two recurrences come back from LDS while the gathers are in flight (a refresh trip has just formed both afresh)
+            if (PARK && !direct) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) { ctr[r] = CTs[r * PB + threadIdx.x]; cmd[r] = CMs[r * PB + threadIdx.x]; }
+            }
             // (a lane without columns gathers column 0 of the rows: its product is masked -- under ONE workgroup-uniform branch per trip, so
             // that a launch whose lanes all have columns, ld = 2 LPR, pays nothing for it; CSR rows mask inside csr_gather.  A row slot
             // past `hi` needs no mask: its vs[] are zero, set-up)
@@ -860,6 +894,9 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const double2 acc = cmd[r];
+            // PARK: this is the last use of cmd[r] in the trip (ctr[r]'s was in the products) -- both to their slots, on every path
+            // (first trip, refresh, recurrence)
+            if (PARK) { CTs[r * PB + threadIdx.x] = ctr[r]; CMs[r * PB + threadIdx.x] = acc; }
             const double2 y = Ys[r * PB + threadIdx.x], mdr = md[r], rv = rr[r];
             const double dot = msdp_group_sum_all<LPR>(acc.x * y.x + acc.y * y.y);
             const double eg = eGs[SLOT(r)];
@@ -917,7 +954,10 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
         // (my rows of Hmd are performed before I post: the wait sits inside psync8, behind the wave reduction)
         // (the next trip's gather goes out as soon as this wave has seen every workgroup's post: its latency runs under the rest of the
         // reduction and the arithmetic behind it.  Not behind a refresh trip: that one's two direct gathers come first.)
-        auto next_gather = [&]() { if (PREF && !pub) { PIPE_ISSUE(rs_md, xq * half_bytes, NL); have_x = true; } };
+        auto next_gather = [&]() {
+            if (SPREAD) { PIPE_SPREAD(0, 3); }
+            else if (PREF && !pub) { PIPE_ISSUE(rs_md, xq * half_bytes, NL); have_x = true; }
+        };
         if (XTWO) {
             if (!psync2_8(d.xr2_blk, shpeer, d.xr2_n, d.xr2_me, xri, gen++, GS + d.xr2_skip, v, sh8, shb8, err, bid, backoff, next_gather)) { failed = true; break; }
         } else
@@ -942,11 +982,13 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
             ++j;
             break;
         }
+        PIPE_SPREAD(3, 6);
         // the trial step's three inner products (tCG.m:215-241), expanded in alpha
         const double new_model = model_value - alpha * v[3] - 0.5 * alpha * (v[4] + v[5]) + 0.5 * alpha * alpha * d_Hd;   // :227
         const double r_r = fmax(z_r - 2.0 * alpha * v[1] + alpha * alpha * v[2], 0.0);                                    // :241
         e_Pe = e_Pe_new;
         if (!bench && new_model >= model_value) { stop = 6; ++j; break; }                 // :228 (eta, Heta stay)
+        PIPE_SPREAD(6, 9);
 #pragma unroll
         for (int r = 0; r < R; ++r) {                                                     // :233-238
             eta[r].x -= alpha * md[r].x; eta[r].y -= alpha * md[r].y;
@@ -955,7 +997,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
         model_value = new_model;
         ++j;
         const double norm_r = sqrt(r_r);
-        const double nr0t = (theta == 1.0) ? norm_r0 : pow(norm_r0, theta);
+        const double nr0t = PARK ? nr0t_tcg : ((theta == 1.0) ? norm_r0 : pow(norm_r0, theta));
         if (!bench && j >= mininner && norm_r <= norm_r0 * fmin(nr0t, kappa)) {           // :249
             stop = (kappa < nr0t) ? 3 : 4;
             break;
@@ -965,6 +1007,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
         e_Pd = beta * (e_Pd + alpha * d_Pd);                                              // :286
         d_Pd = r_r + beta * beta * d_Pd;                                                  // :287
         z_r = r_r;
+        PIPE_SPREAD(9, 12);
         // ---- mdelta = tangent(r + beta*mdelta)  (:273,283)
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -973,12 +1016,16 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
             const double dot = msdp_group_sum_all<LPR>(vv.x * y.x + vv.y * y.y);
             md[r] = make_double2(vv.x - y.x * dot, vv.y - y.y * dot);
         }
+        PIPE_SPREAD(12, 15);
+        if (SPREAD) have_x = !pub;                                        // (all R x NG are on their way)
         direct = pub;
         first = false;
         xq ^= 1u;
         { --j; PTSTAMP(6); ++j; }
     }
 #undef PIPE_ISSUE
+#undef PIPE_ISSUE_PART
+#undef PIPE_SPREAD
 #undef PIPE_FOLDX
 #undef PIPE_FOLDL
 #undef PIPE_GATHER_ALL
@@ -1020,6 +1067,13 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
         pub_cd = refresh > 0 ? refresh : 0;
     }
     first_tr = false;
+    // PARK: the stopping test's norm_r0 ^ theta (tCG.m:249), the same expression as inside the trip, formed HERE once per tCG and only
+    // where theta != 1 (the empty asm keeps the compiler from evaluating pow() speculatively).  Left inside the trip it is hoisted to
+    // this place anyway and evaluated for every tCG whatever theta is; with the registers of this instance the thirteen coefficients of
+    // its polynomials were then parked in scratch in front of the loop over the TR iterations and reloaded one behind the other, each
+    // waited for, at the start of every TR iteration: 3 us (profiles/r10_trip_instruction_counts.md).
+    nr0t_tcg = norm_r0;
+    if (PARK && theta != 1.0) { asm volatile("" ::: "memory"); nr0t_tcg = pow(norm_r0, theta); }
     // (FUSE at 16 lanes per row: ONE instance of the trip loop -- with three of them inside the loop over the TR iterations the
     // register allocation spills 400 bytes per lane into the trips, 103 000 Hess-vec/s on G81 at p = 32 against 170 000 with one.
     // Round 6: an instance with its local columns fixed for the whole KERNEL -- two columns of every row from LDS, three through the

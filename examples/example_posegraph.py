@@ -5,7 +5,8 @@ Euclidean, d orthonormal rows and one free row per block of the factor (no multi
 positions).  The poses are then rounded on the host (problems.round_poses) and compared with the planted ones up to the global
 rotation and shift the problem cannot see (problems.pose_error).
 argv = [n, default 2000; d, default 3; degree, default 8; sigma_r, default 0.1; sigma_t, default 0.1; seed, default 0]; --persist anywhere on the line: the tCG of every trust-region iteration as one
-persistent launch where the handle is eligible (options["block_persist"])."""
+persistent launch where the handle is eligible (options["block_persist"]); --precon anywhere on the line: block-Jacobi preconditioned tCG
+(options["precon"] = "blockjacobi": the diagonal blocks of C; the handle then runs the generic trips)."""
 import sys
 import time
 
@@ -15,7 +16,8 @@ import _common  # noqa: F401  (puts the repository root on sys.path)
 from manisdp_matlab_amd import problems, solvers
 
 persist = "--persist" in sys.argv
-sys.argv = [a for a in sys.argv if a != "--persist"]
+precon = "--precon" in sys.argv
+sys.argv = [a for a in sys.argv if a not in ("--persist", "--precon")]
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
 d = int(sys.argv[2]) if len(sys.argv) > 2 else 3
@@ -24,11 +26,11 @@ sigma_r = float(sys.argv[4]) if len(sys.argv) > 4 else 0.1
 sigma_t = float(sys.argv[5]) if len(sys.argv) > 5 else 0.1
 C, R_true, t_true, edges, _, _ = problems.pose_graph(n, d, degree, sigma_r, sigma_t, int(sys.argv[6]) if len(sys.argv) > 6 else 0)
 t = time.time()
-Y, fval, data = solvers.ManiSDP_posegraph(C, d, {"tol": 1e-8, "block_persist": persist})
+Y, fval, data = solvers.ManiSDP_posegraph(C, d, {"tol": 1e-8, "block_persist": persist, "precon": "blockjacobi" if precon else None})
 e = np.sqrt(np.maximum(np.linalg.eigvalsh(Y.T @ Y), 0.0))
 rank = int(np.sum(e >= 1e-3 * e.max()))
 R, pos = problems.round_poses(Y, d)
-print("ManiSDP: optimum = %.8f, gap = %.1e, dinf = %.1e, time = %.2fs (rank %d, factor width %d, %d edges)"
-      % (fval, data["gap"], data["dinf"], time.time() - t, rank, Y.shape[1], len(edges)))
+print("ManiSDP: optimum = %.8f, gap = %.1e, dinf = %.1e, time = %.2fs (rank %d, factor width %d, %d edges, %d Hess-vecs)"
+      % (fval, data["gap"], data["dinf"], time.time() - t, rank, Y.shape[1], len(edges), data["hessvecs"]))
 print("rounded poses: max_i |R_i Q - R_true_i|_F = %.3e, max_i |t_i Q - s - t_true_i| = %.3e"
       % problems.pose_error(R, pos, R_true, t_true))

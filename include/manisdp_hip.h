@@ -662,8 +662,22 @@ int msdp_block_reshape(msdp_handle h, int32_t nb, const int64_t* row0, const int
  *                       instances at a few hundred blocks)
  *   "block_persist_wide"  1/0  A/B switch of that launch: 1 = the largest grid the plan allows at its row slots (the blocks spread
  *                       over more compute units), 0 (default) = the fewest workgroups that need those row slots
+ *   "precon"       1/0  pose-graph handles: block-Jacobi preconditioned tCG (msdp_pose_precon.hip).  M_i = sym(C_[ii]), the diagonal
+ *                       block of order d + 1 of pose i (fixed, unscaled, independent of the point), is inverted once on the host in
+ *                       fp64 through its Cholesky factor; precon(x, r) = tangent_x(blockdiag(M_i^-1) r).  The tCG then follows the
+ *                       preconditioned branch of tCG.m: z = precon(r) at :117-125 and :260-268, z_r = <z, r> (:126, :270),
+ *                       beta = z_r / zold_rold (:272), mdelta = tangent(z + beta mdelta) (:273-283), e_Pd and d_Pd by :286-287; the
+ *                       stop test :249 stays on sqrt(<r, r>).  The trust region is measured in the M-norm, Delta_bar and Delta0
+ *                       keep their values.  Default 0: nothing changes, no device work.  With 1 the handle runs the generic
+ *                       three-launch trips also when "block_persist" is on (msdp_tcg_path reports 0).  MSDP_EUNSUPPORTED, the
+ *                       handle left as it was: a block with a non-positive or non-finite pivot (the message names the first),
+ *                       a unit-block-diagonal handle (its diagonal blocks are zero) and every other kind (the message names it)
  * The environment variables are read once, when the handle is created.  Unknown names -> MSDP_EINVAL. */
 int msdp_set_option(msdp_handle h, const char* name, int32_t value);
+/* (parity tests) Z = tangent_Y(blockdiag(M_i^-1) R) at the resident point Y of a pose-graph handle with the option "precon" set:
+ * the preconditioner of its tCG applied to a host array R (N x p row-major, tangent or not).  MSDP_ESTATE without the option or
+ * without a point. */
+int msdp_precon_apply(msdp_handle h, const double* R, double* Z);
 
 /* Which implementation msdp_rtr uses for the tCG inner loop at the resident point:
  * 1 = persistent single-launch kernel (working set in registers/LDS, sparse C, oblique,

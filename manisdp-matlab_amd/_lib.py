@@ -86,6 +86,7 @@ SIGNATURES = {
     "msdp_rgrad": (C.c_int, [C.c_void_p, _dp]),
     "msdp_hessvec": (C.c_int, [C.c_void_p, _dp, _dp]),
     "msdp_proj": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "msdp_precon_apply": (C.c_int, [C.c_void_p, _dp, _dp]),
     "msdp_retr": (C.c_int, [C.c_void_p, _dp, _dp]),
     "msdp_get_z": (C.c_int, [C.c_void_p, _dp]),
     "msdp_linesearch_cost": (C.c_int, [C.c_void_p, _dp, C.c_double, _dp]),
@@ -653,6 +654,11 @@ class Handle:
 
     def retr(self, U):
         return self._vec_op(self._lib.msdp_retr, U)
+
+    def precon_apply(self, R):
+        """tangent_Y(blockdiag(M_i^-1) R) at the resident point of a posegraph handle with set_option("precon", 1): the
+        preconditioner of its tCG (msdp_precon_apply), M_i = sym(C_[ii])."""
+        return self._vec_op(self._lib.msdp_precon_apply, R)
 
     def round_hyperplane(self, R, sweeps=0, masks=False):
         """Hyperplane rounding of the resident point on the device (msdp_round_hyperplane): x_t = sign(Y r_t) for the rows r_t

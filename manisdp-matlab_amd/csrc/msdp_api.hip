@@ -98,6 +98,7 @@ int msdp_alloc_vectors(msdp_handle h, int pcap) {
     }
     h->pcap = pcap;
     h->ldcap = ldcap;
+    if (h->pc_z) return msdp_pose_precon_vectors(h);               // option "precon" (msdp_pose_precon.hip): its vector follows the capacity
     return 0;
 }
 
@@ -1044,6 +1045,10 @@ extern "C" int msdp_set_option(msdp_handle h, const char* name, int32_t value) {
     else if (!strcmp(name, "block_persist")) { if (value < 0 || value > 1) { msdp_set_error("block_persist: 0 or 1"); return MSDP_EINVAL; } t.block_persist = value; }
     else if (!strcmp(name, "block_persist_grid")) t.block_persist_grid = value > 0 ? value : 0;
     else if (!strcmp(name, "block_persist_wide")) t.block_persist_wide = value != 0;
+    else if (!strcmp(name, "precon")) {
+        if (value < 0 || value > 1) { msdp_set_error("precon: 0 or 1"); return MSDP_EINVAL; }
+        return msdp_pose_precon_set(h, value);             // (d.pcM is part of the chunk graph's signature: the graph is captured again)
+    }
     else if (!strcmp(name, "debug_xr_skip")) t.fail_xr = value != 0;
     else if (!strcmp(name, "debug_fail_block")) t.fail_block = value != 0;
     else if (!strcmp(name, "grid")) { t.grid = value > 0 ? value : 0; choose_grid(h); h->chunk_len = 0; }
@@ -1118,6 +1123,18 @@ extern "C" int msdp_proj(msdp_handle h, const double* U, double* V) {
     else rc = msdp_sphere_proj(h, h->d.Y[msdp_host_cur(h)], h->d.W0, h->d.W1);
     if (rc) return rc;
     return download_rows(h, h->d.W1, V);
+}
+
+// Z = tangent_Y(blockdiag(M_i^-1) R) at the resident point of a pose-graph handle with the option "precon" set
+extern "C" int msdp_precon_apply(msdp_handle h, const double* R, double* Z) {
+    MSDP_CHECK_H(h);
+    if (!R || !Z) { msdp_set_error("precon_apply: null array"); return MSDP_EINVAL; }
+    if (!h->d.pcM) { msdp_set_error("precon_apply: the option \"precon\" is not set on this handle"); return MSDP_ESTATE; }
+    if (!h->have_point) { msdp_set_error("no resident point"); return MSDP_ESTATE; }
+    int rc = upload_rows(h, R, h->d.W0);
+    if (rc) return rc;
+    if ((rc = msdp_pose_precon_apply(h, h->d.Y[msdp_host_cur(h)], h->d.W0, h->d.W1))) return rc;
+    return download_rows(h, h->d.W1, Z);
 }
 
 extern "C" int msdp_retr(msdp_handle h, const double* U, double* Z) {

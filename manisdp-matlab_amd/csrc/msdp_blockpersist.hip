@@ -375,6 +375,7 @@ int msdp_blockpersist_eligible(msdp_handle h) {
     const Dev& d = h->d;
     if (!h->tune.block_persist || !h->tune.persist || h->persist_failed || h->use_comm || h->nranks != 1) return 0;
     if (d.manifold != MANI_STIEFEL || d.costkind != COST_BLOCK) return 0;
+    if (d.pcM) return 0;                                  // option "precon": the kernel above has no preconditioner, the generic trips run
     if (!h->psync_slots || !h->psync_err || !d.mdx) return 0;
     const BlockPersistPlan pl = blk_plan(h);
     if (!pl.ok) return 0;

@@ -192,6 +192,10 @@ struct Dev {
     int blk, nb, efree;
     const int* brp; const int* bci; const double* bval;
     double* Lam[2];
+    // pose-graph kind, option "precon" (msdp_pose_precon.hip): pcM = the inverses M_i^-1 of the diagonal blocks sym(C_[ii]) (nb * blk * blk
+    // doubles, each block row-major and symmetric), pcz = the preconditioned residual z of the running tCG (n_loc x ld).  Both null
+    // while the option is off: pcM != nullptr is what selects the preconditioned launchers
+    const double* pcM; double* pcz;
 };
 #define MSDP_LR_PARTS 128         // workgroups (= partial sums per entry of T) of the low-rank projection
 
@@ -379,6 +383,9 @@ struct msdp_handle_s {
     // persistent tCG kernel of the block kinds (msdp_blockpersist.hip): cached eligibility, the slot region of the next launch
     const void* blkpersist_sig_fn = nullptr; int blkpersist_sig_G = 0, blkpersist_sig_ok = 0; size_t blkpersist_sig_lds = 0;
     int blkpersist_region = 0;
+    // option "precon" of the pose-graph kind (msdp_pose_precon.hip): the buffers behind Dev::pcM / Dev::pcz, allocated when the option is
+    // first set and kept while it is off
+    double* pc_minv = nullptr; double* pc_z = nullptr; size_t pc_z_cap = 0;
 };
 
 #define MSDP_CHECK_H(h)                                     \
@@ -498,6 +505,13 @@ int msdp_pose_retract(msdp_handle h);
 int msdp_pose_proj(msdp_handle h, const double* Y, const double* U, double* V);
 int msdp_pose_retr(msdp_handle h, const double* Y, const double* U, double* Z, double alpha);
 int msdp_pose_sv(msdp_handle h, const double* Lam, const double* v, double* w);      // w = C v - blockdiag(Lam (+) 0) v
+// msdp_pose_precon.hip: the block-Jacobi preconditioned tCG of a pose-graph handle (option "precon"; d.pcM != nullptr selects it)
+int msdp_pose_precon_set(msdp_handle h, int on);              // the option: M_i^-1 on the host, once; MSDP_EUNSUPPORTED names the kind or the block
+int msdp_pose_precon_vectors(msdp_handle h);                  // (re)allocates z for the handle's row capacity
+int msdp_pose_precon_init(msdp_handle h);                     // tCG.m:102-157 with z = precon(r)
+int msdp_pose_precon_upd1(msdp_handle h);                     // tCG.m:166-241, z = precon(r_new), <z, r_new>
+int msdp_pose_precon_upd2(msdp_handle h);                     // tCG.m:227-287 with beta = z_r_new / z_r
+int msdp_pose_precon_apply(msdp_handle h, const double* Y, const double* R, double* Z);   // Z = tangent_Y(blockdiag(M_i^-1) R)
 // msdp_trip1.hip, msdp_trip2.hip
 int msdp_trip1_ok(msdp_handle h);                             // sharded trip with one all-reduce applies to this handle
 int msdp_launch_trip1_init(msdp_handle h);

@@ -84,7 +84,7 @@ int msdp_tcg_begin(msdp_handle h) {
         int rc = msdp_launch_trip2_init(h);
         return rc ? rc : msdp_launch_trip2_head(h);
     }
-    return msdp_launch_tcg_init(h);
+    return h->d.pcM ? msdp_pose_precon_init(h) : msdp_launch_tcg_init(h);   // (option "precon" of the pose-graph kind: msdp_pose_precon.hip)
 }
 int msdp_enqueue_trips(msdp_handle h, int cnt) {
     int rc;
@@ -115,10 +115,11 @@ int msdp_enqueue_trips(msdp_handle h, int cnt) {
         }
         return 0;
     }
+    const bool pc = h->d.pcM != nullptr;                  // pose-graph kind, option "precon": the preconditioned updates (msdp_pose_precon.hip)
     for (int t = 0; t < cnt; ++t) {
         if ((rc = msdp_launch_hess(h))) return rc;        // tCG.m:163
-        if ((rc = msdp_launch_upd1(h))) return rc;        // tCG.m:166-241
-        if ((rc = msdp_launch_upd2(h))) return rc;        // tCG.m:249-287
+        if ((rc = pc ? msdp_pose_precon_upd1(h) : msdp_launch_upd1(h))) return rc;        // tCG.m:166-241
+        if ((rc = pc ? msdp_pose_precon_upd2(h) : msdp_launch_upd2(h))) return rc;        // tCG.m:249-287
     }
     return 0;
 }

@@ -618,7 +618,7 @@ def ManiSDP_onlyunitblockdiag(C, d, options=None, verbose=True, rng=None):
     [Y, alpha V(:, 1:nne)], and after either step every block is re-orthonormalised on the host by its polar factor.
     ``options["block_persist"] = True`` runs the tCG of every trust-region iteration as one persistent launch where the handle
     is eligible (p <= 32; msdp_set_option "block_persist"), the generic trips elsewhere; default False.
-    ``line_search = 1``, ``device_factor``, ``round`` and ``comm`` raise ValueError before the library is loaded."""
+    ``line_search = 1``, ``device_factor``, ``round``, ``comm`` and ``precon`` raise ValueError before the library is loaded."""
     with _host_threads():
         return _onlyunitblockdiag_impl(C, d, options, verbose, rng)
 
@@ -636,6 +636,9 @@ def _onlyunitblockdiag_impl(C, d, options, verbose, rng):
             raise ValueError(f"options[{name!r}] is not available for the unit-block-diagonal problem: {what}")
     if o["line_search"] == 1:
         raise ValueError("options['line_search'] = 1 is not available for the unit-block-diagonal problem")
+    if o.get("precon") is not None:
+        raise ValueError("options['precon'] is not available for the unit-block-diagonal problem: the diagonal blocks of its cost "
+                         "matrix are zero (block-Jacobi preconditioning is ManiSDP_posegraph's)")
     if o.get("device_factor"):
         raise ValueError("options['device_factor'] is not available for the unit-block-diagonal problem: the rank cut stays on the host")
     if C.shape[0] != C.shape[1] or C.shape[0] % d:
@@ -788,6 +791,10 @@ def ManiSDP_posegraph(C, d, options=None, verbose=True, rng=None):
     Returns (Y, obj, data); ``data["Lambda"]`` holds the multiplier blocks (n, d, d), S = C - blockdiag(Lambda_i (+) 0).  For a
     pose-graph C the global shift is in the null space of S, so lambda_min of a certified point is 0.
     ``options["block_persist"]`` as for ManiSDP_onlyunitblockdiag.
+    ``options["precon"] = "blockjacobi"`` runs every tCG with the block-Jacobi preconditioner M_i = sym(C_[ii]) of the diagonal
+    blocks (msdp_set_option "precon": the preconditioned branch of tCG.m, the trust region in the M-norm); default None, the
+    identity.  With it the handle runs the generic trips also under ``block_persist``.  Any other value raises ValueError
+    before the library is loaded; a block the library cannot invert surfaces as its own MsdpError.
     ``line_search = 1``, ``device_factor``, ``round`` and ``comm`` raise ValueError before the library is loaded."""
     with _host_threads():
         return _posegraph_impl(C, d, options, verbose, rng)
@@ -806,6 +813,8 @@ def _posegraph_impl(C, d, options, verbose, rng):
             raise ValueError(f"options[{name!r}] is not available for the pose-graph problem: {what}")
     if o["line_search"] == 1:
         raise ValueError("options['line_search'] = 1 is not available for the pose-graph problem")
+    if o.get("precon") not in (None, "blockjacobi"):
+        raise ValueError(f"options['precon'] must be None or 'blockjacobi' for the pose-graph problem, not {o.get('precon')!r}")
     if o.get("device_factor"):
         raise ValueError("options['device_factor'] is not available for the pose-graph problem: the rank cut stays on the host")
     if C.shape[0] != C.shape[1] or C.shape[0] % B:
@@ -835,10 +844,16 @@ def _posegraph_impl(C, d, options, verbose, rng):
     Y = np.ascontiguousarray(Y, dtype=np.float64)
     p = Y.shape[1]
     h = _lib.Handle.posegraph(Csp, d, pcap=min(256, max(32, p + 2 * delta)))
-    if o.get("block_persist"):                             # the tCG of a TR iteration in one persistent launch where it applies
-        h.set_option("block_persist", 1)
-    for name, value in (o.get("device_options") or {}).items():
-        h.set_option(name, int(value))
+    try:
+        if o.get("block_persist"):                         # the tCG of a TR iteration in one persistent launch where it applies
+            h.set_option("block_persist", 1)
+        if o.get("precon") == "blockjacobi":               # block-Jacobi preconditioned tCG (msdp_set_option "precon"); a refusal
+            h.set_option("precon", 1)                      # (a diagonal block without a Cholesky factor) is the library's own error
+        for name, value in (o.get("device_options") or {}).items():
+            h.set_option(name, int(value))
+    except Exception:
+        h.close()
+        raise
     topts = _rtr_opts(o)
     data = {"status": 0, "hessvecs": 0, "cost_evals": 0, "rejected": 0, "rtr_seconds": 0.0, "eig_seconds": 0.0, "log": [],
             "reruns": 0}

@@ -694,6 +694,10 @@ int msdp_debug_block_persist_form(msdp_handle h, int32_t* form);
 /* (test / diagnostic) Its plan at the resident width: out[0] 1 = the kernel applies (option on, plan, co-residency), out[1] lanes
  * per block, out[2] workgroups, out[3] row slots per lane group, out[4] dynamic LDS bytes; out[1..4] = 0 where no plan exists. */
 int msdp_debug_block_persist_plan(msdp_handle h, int32_t* out);
+/* (test / diagnostic) Which trip the chunked path takes at the resident point: 1 = the linear-product trip (option "trip1"), 2 = the
+ * two-launch trip (option "trip2"), 3 = three launches per trip (every other kind and storage, the option "precon" included);
+ * 0 = the tCG is persistent (msdp_tcg_path reports 1 or 2).  Read-only: no launch, the handle is not modified. */
+int msdp_debug_trip_form(msdp_handle h, int32_t* form);
 /* (test / diagnostic) What the set-up of a primal affine handle (MSDP_KIND_UNITDIAG, _UNITTRACE, _GENERIC) planned from the constraint
  * data, and which branch the last calls took.  Host only: no launch, the handle is not modified.  out[0..15]:
  *    0 usym      1 = c and every A_k are symmetric entry by entry (upper view, tiled adjoint, B route possible)

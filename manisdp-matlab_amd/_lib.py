@@ -144,6 +144,7 @@ SIGNATURES = {
     "msdp_debug_block_persist_form": (C.c_int, [C.c_void_p, _P(C.c_int32)]),
     "msdp_debug_block_persist_plan": (C.c_int, [C.c_void_p, _P(C.c_int32)]),
     "msdp_debug_affine_plan": (C.c_int, [C.c_void_p, _P(C.c_int32)]),
+    "msdp_debug_trip_form": (C.c_int, [C.c_void_p, _P(C.c_int32)]),
     "msdp_point_snapshot": (C.c_int, [C.c_void_p]),
     "msdp_point_restore": (C.c_int, [C.c_void_p]),
     "msdp_al_primal": (C.c_int, [C.c_void_p, _dp, _dp]),
@@ -931,6 +932,13 @@ class Handle:
         _check(self._lib.msdp_debug_persist_form(self._h, C.byref(v)))
         if v.value < 0:                                    # the block kinds' kernel (option "block_persist") is a unit of its own
             _check(self._lib.msdp_debug_block_persist_form(self._h, C.byref(v)))
+        return v.value
+
+    def trip_form(self):
+        """Trip of the chunked tCG at the resident point (msdp_debug_trip_form): 1 the linear-product trip, 2 the two-launch trip,
+        3 three launches per trip, 0 a persistent path."""
+        v = C.c_int32()
+        _check(self._lib.msdp_debug_trip_form(self._h, C.byref(v)))
         return v.value
 
     def block_persist_plan(self):

@@ -23,6 +23,18 @@ extern "C" int msdp_tcg_path(msdp_handle h, int32_t* path) {
     return 0;
 }
 
+// Which of the chunked trips msdp_tcg_begin / msdp_enqueue_trips take for the resident point, in their order of tests: 1 the
+// linear-product trip (msdp_trip1.hip), 2 the two-launch trip (msdp_trip2.hip), 3 three launches per trip; 0: a persistent path
+extern "C" int msdp_debug_trip_form(msdp_handle h, int32_t* form) {
+    MSDP_CHECK_H(h);
+    if (!form) return MSDP_EINVAL;
+    int32_t path = 0;
+    const int rc = msdp_tcg_path(h, &path);
+    if (rc) return rc;
+    *form = path ? 0 : (msdp_trip1_ok(h) ? 1 : (msdp_trip2_ok(h) ? 2 : 3));
+    return 0;
+}
+
 // ------------------------------------------------------------------ RTR driver
 int msdp_push_ctl(msdp_handle h) {
     HIPCHK(msdp_memcpy_async(h->d.ctl, h->h_ctl, sizeof(Ctl), hipMemcpyHostToDevice, h->stream));

@@ -165,7 +165,7 @@ __global__ __launch_bounds__(PB) void k_tcg_persist_blk(Dev d, unsigned long lon
     unsigned gen = 0, nbar = 0;
     double z_r = gg, d_Pd = gg, e_Pd = 0.0, e_Pe = 0.0, model_value = 0.0, alpha = 0.0, beta = 0.0;
     const double norm_r0 = sqrt(gg);
-    const double nr0t = (theta == 1.0) ? norm_r0 : pow(norm_r0, theta);    // norm_r0^theta of :249, the same in every trip
+    const double nr0t = tcg_nr0t(norm_r0, theta);                          // the same in every trip
     int j = 0, stop = 5;
     bool failed = false;
     for (;;) {
@@ -218,9 +218,9 @@ __global__ __launch_bounds__(PB) void k_tcg_persist_blk(Dev d, unsigned long lon
         if (!psync(slots, gen++, G, 1, pd, u1, u2, sh, shb, err, -1, backoff, false)) { failed = true; break; }
         const double d_Hd = pd;                                                        // :166
         alpha = z_r / d_Hd;                                                            // :170
-        const double e_Pe_new = e_Pe + 2.0 * alpha * e_Pd + alpha * alpha * d_Pd;      // :173
-        if (!bench && (d_Hd <= 0.0 || e_Pe_new >= Delta * Delta)) {                    // :183
-            const double tau = (-e_Pd + sqrt(e_Pd * e_Pd + d_Pd * (Delta * Delta - e_Pe))) / d_Pd;   // :188
+        const double e_Pe_new = tcg_e_Pe_new(e_Pe, alpha, e_Pd, d_Pd);
+        if (!bench && !tcg_step_inside(d_Hd, e_Pe_new, Delta)) {
+            const double tau = tcg_tau(e_Pd, d_Pd, e_Pe, Delta);
 #pragma unroll
             for (int r = 0; r < R; ++r)
 #pragma unroll
@@ -229,7 +229,7 @@ __global__ __launch_bounds__(PB) void k_tcg_persist_blk(Dev d, unsigned long lon
                     if (HDER) rr[r][a] = make_double2(rr[r][a].x - tau * hm[r][a].x, rr[r][a].y - tau * hm[r][a].y);
                     else BP_HE(r, a) = make_double2(BP_HE(r, a).x - tau * hm[r][a].x, BP_HE(r, a).y - tau * hm[r][a].y);   // :198
                 }
-            stop = (d_Hd <= 0.0) ? 1 : 2;
+            stop = tcg_boundary_stop(d_Hd);
             ++j;
             break;
         }
@@ -253,7 +253,7 @@ __global__ __launch_bounds__(PB) void k_tcg_persist_blk(Dev d, unsigned long lon
         e_Pe = e_Pe_new;
         const double new_model = s1 + 0.5 * s2;                                        // :227
         const double r_r = s3;
-        if (!bench && new_model >= model_value) { stop = 6; ++j; break; }              // :228 (eta, Heta stay)
+        if (!bench && !tcg_model_decreased(new_model, model_value)) { stop = 6; ++j; break; }   // (eta, Heta stay)
 #pragma unroll
         for (int r = 0; r < R; ++r)                                                    // :233-238 commit (the trial's expressions)
 #pragma unroll
@@ -265,15 +265,12 @@ __global__ __launch_bounds__(PB) void k_tcg_persist_blk(Dev d, unsigned long lon
         model_value = new_model;
         ++j;
         const double norm_r = sqrt(r_r);
-        if (!bench && j >= mininner && norm_r <= norm_r0 * fmin(nr0t, kappa)) {       // :249
-            stop = (kappa < nr0t) ? 3 : 4;
+        if (!bench && !tcg_unconverged(j, mininner, norm_r, norm_r0, nr0t, kappa)) {
+            stop = tcg_converged_stop(kappa, nr0t);
             break;
         }
         if (j >= maxinner) break;                                                      // :160 (stop stays 5)
-        beta = r_r / z_r;                                                              // :272
-        e_Pd = beta * (e_Pd + alpha * d_Pd);                                           // :286
-        d_Pd = r_r + beta * beta * d_Pd;                                               // :287
-        z_r = r_r;
+        beta = tcg_recurrences(r_r, alpha, z_r, e_Pd, d_Pd);
         // ---- 10: mdelta = tangent(r + beta mdelta) (:273, :283); the free row of the projection is the row itself
 #pragma unroll
         for (int r = 0; r < R; ++r) {

@@ -72,6 +72,8 @@ struct Frame {
 enum { P_F = 0, P_GG = 1, P_DHD = 2, P_S1 = 3, P_S2 = 4, P_S3 = 5, P_RD = 6, P_AUX = 7, P_AXB = 8,
        // sphere Hess-vec, fused form (msdp_affine.hip, k_sddmm1 mode 2): <U, G>, <U, Y>, sum_k w_k (A x)_k
        P_T1 = 9, P_T2 = 10, P_T3 = 11 };
+// preconditioned tCG (msdp_pose_precon.hip): <z, r> of the init launch and of an upd1 launch, in arrays its kind leaves free
+enum { P_ZR0 = P_AUX, P_ZRN = P_AXB };
 
 enum { MANI_OBLIQUE = 0, MANI_SPHERE = 1, MANI_EUCLID = 2,
        MANI_STIEFEL = 3 };   // stacked Stiefel manifold: the d rows of a block are orthonormal (msdp_stiefel.hip)

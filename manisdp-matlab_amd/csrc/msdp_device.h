@@ -6,6 +6,7 @@
 // streaming kernel); the DPP forms are plain VALU moves.
 #pragma once
 #include "msdp_common.h"
+#include "msdp_tr_rules.h"
 
 // Windowed row traversal for gather kernels on vectors larger than the L2s (sweep != 0).  With msdp_chunk_rows every workgroup
 // streams through its own chunk: the 64 workgroups of an XCD walk 64 windows that lie one chunk apart, and a row a neighbour
@@ -578,10 +579,13 @@ __device__ __forceinline__ void msdp_sym_invsqrt(const double (&G)[D][D], double
         }
 }
 
-// tCG.m:227-287, the scalar part of the second update of a trip (everything k_tcg_upd2_obl decides before it touches a row):
-// model check, convergence test, loop bound, the new frame.  Returns true when a new direction mdelta = tangent(r + beta mdelta)
-// is due, with beta; false when the tCG has ended (or was not running) -- the frame and the progress word are written either
-// way.  Called by every thread of the launch; shb: 4 doubles of LDS.
+// tCG.m:227-287, the scalar part of the second update of a three-launch trip (everything an upd2 kernel decides before it
+// touches a row): model check, convergence test, loop bound, the new frame -- the rules of msdp_tr_rules.h on the frame F[1]
+// -> F[0].  The single reader of F[1] and writer of F[0] of these trips.  Returns true when a new direction
+// mdelta = tangent(z + beta mdelta) is due, with beta; false when the tCG has ended (or was not running) -- the frame and the
+// progress word are written either way.  PRECON: the fourth sum <z, r> of the preconditioned upd1 (P_ZRN) takes the place of
+// r_r in the recurrences (tCG.m:270-287).  Called by every thread of the launch; shb: 4 doubles of LDS.
+template <bool PRECON = false>
 __device__ __forceinline__ bool msdp_tcg_upd2_scalars(const Dev& d, double* shb, double& beta_out) {
     const Frame* fi = &d.F[1];
     const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
@@ -599,11 +603,22 @@ __device__ __forceinline__ bool msdp_tcg_upd2_scalars(const Dev& d, double* shb,
     }
     const Ctl* c = d.ctl;
     const bool bench = c->bench_mode != 0;
-    double s1, s2, r_r;
-    msdp_sum_partials3_block(d.P, P_S1, P_S2, P_S3, d.G, shb, s1, s2, r_r);
+    double s1, s2, r_r, z_r_new;
+    if (PRECON) {
+        if (threadIdx.x < 64) {
+            const double a = msdp_sum_partials(d.P, P_S1, d.G), b = msdp_sum_partials(d.P, P_S2, d.G);
+            const double e = msdp_sum_partials(d.P, P_S3, d.G), f = msdp_sum_partials(d.P, P_ZRN, d.G);
+            if (threadIdx.x == 0) { shb[0] = a; shb[1] = b; shb[2] = e; shb[3] = f; }
+        }
+        __syncthreads();
+        s1 = shb[0]; s2 = shb[1]; r_r = shb[2]; z_r_new = shb[3];
+    } else {
+        msdp_sum_partials3_block(d.P, P_S1, P_S2, P_S3, d.G, shb, s1, s2, r_r);
+        z_r_new = r_r;
+    }
     const double new_model = s1 + 0.5 * s2;                 // :227
     const int j = j0 + 1;
-    if (!bench && new_model >= model_value) {               // :228
+    if (!bench && !tcg_model_decreased(new_model, model_value)) {
         if (lead) {
             frame_store(&d.F[0], z_r, d_Pd, e_Pd, e_Pe, model_value, norm_r0, alpha, beta0, 0, j, 6, ix);
             d.ctl->tcg_running = 0;
@@ -613,10 +628,10 @@ __device__ __forceinline__ bool msdp_tcg_upd2_scalars(const Dev& d, double* shb,
     }
     const int nix = ix ^ 1;                                 // :233-235 commit new_eta/new_Heta
     const double norm_r = sqrt(r_r);
-    const double nr0t = (c->theta == 1.0) ? norm_r0 : pow(norm_r0, c->theta);   // norm_r0^theta
-    if (!bench && j >= c->mininner && norm_r <= norm_r0 * fmin(nr0t, c->kappa)) {   // :249
+    const double nr0t = tcg_nr0t(norm_r0, c->theta);
+    if (!bench && !tcg_unconverged(j, c->mininner, norm_r, norm_r0, nr0t, c->kappa)) {
         if (lead) {
-            frame_store(&d.F[0], z_r, d_Pd, e_Pd, e_Pe, new_model, norm_r0, alpha, beta0, 0, j, (c->kappa < nr0t) ? 3 : 4, nix);
+            frame_store(&d.F[0], z_r, d_Pd, e_Pd, e_Pe, new_model, norm_r0, alpha, beta0, 0, j, tcg_converged_stop(c->kappa, nr0t), nix);
             d.ctl->tcg_running = 0;
             msdp_publish(d, c->k, j, 0);
         }
@@ -630,12 +645,34 @@ __device__ __forceinline__ bool msdp_tcg_upd2_scalars(const Dev& d, double* shb,
         }
         return false;
     }
-    const double beta = r_r / z_r;                          // :272
+    double n_z_r = z_r, n_e_Pd = e_Pd, n_d_Pd = d_Pd;
+    const double beta = tcg_recurrences(z_r_new, alpha, n_z_r, n_e_Pd, n_d_Pd);
     if (lead) {
-        frame_store(&d.F[0], r_r, r_r + beta * beta * d_Pd /* :287 */, beta * (e_Pd + alpha * d_Pd) /* :286 */, e_Pe,
-                    new_model, norm_r0, alpha, beta, 1, j, stop0, nix);
+        frame_store(&d.F[0], n_z_r, n_d_Pd, n_e_Pd, e_Pe, new_model, norm_r0, alpha, beta, 1, j, stop0, nix);
         msdp_publish(d, c->k, j, 1);
     }
     beta_out = beta;
     return true;
+}
+
+// trustregions.m:548-729 of the routes whose RTR scalars live in Ctl: rho, the radius, accept or reject, the counters, the
+// stopping test.  One thread.  fp, ggp, prd: cost and squared gradient norm at the proposal, <eta, grad + .5 Heta>.
+__device__ __forceinline__ void msdp_rtr_decide(Ctl* c, const Frame& f, double fp, double ggp, double prd) {
+    const int f_stop = f.stop, f_j = f.j;
+    double Delta = c->Delta, rho, rhonum, rhoden;
+    const bool accept = rtr_outcome(c->fx, fp, prd, c->rho_reg, c->rho_prime, c->Delta_bar, f_stop, Delta, rho, rhonum, rhoden);
+    c->Delta = Delta;
+    if (accept) {
+        c->cur ^= 1;
+        c->fx = fp; c->gg = ggp; c->norm_grad = sqrt(ggp);
+        c->accepted++;
+    } else {
+        c->rejected++;
+    }
+    c->rho = rho; c->rhonum = rhonum; c->rhoden = rhoden; c->fx_prop = fp; c->gg_prop = ggp;
+    c->k++;                                                              // :729
+    c->hessvecs += f_j;
+    c->cost_evals++;
+    c->last_stop_inner = f_stop;
+    c->done = rtr_done(c->norm_grad, c->tolgradnorm, c->k, c->maxiter);
 }

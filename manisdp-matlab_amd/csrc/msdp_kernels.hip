@@ -310,9 +310,9 @@ __global__ __launch_bounds__(MSDP_BLOCK) void k_tcg_upd1(Dev d) {
     }
     const double d_Hd = msdp_sum_partials_block(d.P, P_DHD, d.G, shb);       // :166
     const double alpha = z_r / d_Hd;                                 // :170
-    const double e_Pe_new = e_Pe + 2.0 * alpha * e_Pd + alpha * alpha * d_Pd;  // :173
-    if (!bench && (d_Hd <= 0.0 || e_Pe_new >= Delta * Delta)) {         // :183
-        const double tau = (-e_Pd + sqrt(e_Pd * e_Pd + d_Pd * (Delta * Delta - e_Pe))) / d_Pd;  // :188
+    const double e_Pe_new = tcg_e_Pe_new(e_Pe, alpha, e_Pd, d_Pd);
+    if (!bench && !tcg_step_inside(d_Hd, e_Pe_new, Delta)) {
+        const double tau = tcg_tau(e_Pd, d_Pd, e_Pe, Delta);
         for (int64_t ib = i0; ib < e1; ib += 2 * STEP) {
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
@@ -326,7 +326,7 @@ __global__ __launch_bounds__(MSDP_BLOCK) void k_tcg_upd1(Dev d) {
         }
         if (lead) {
             frame_store(&d.F[1], z_r, d_Pd, e_Pd, e_Pe, model_value, norm_r0, alpha0, beta0, 0, j + 1,
-                        (d_Hd <= 0.0) ? 1 : 2, ix ^ 1, mi, 0);
+                        tcg_boundary_stop(d_Hd), ix ^ 1, mi, 0);
         }
         return;
     }
@@ -362,30 +362,15 @@ __global__ __launch_bounds__(MSDP_BLOCK) void k_tcg_upd1(Dev d) {
 template <int LPR, int NCH>
 __global__ __launch_bounds__(MSDP_BLOCK) void k_tcg_upd2_obl(Dev d) {
     __shared__ double shb[4];
-    const Frame* fi = &d.F[1];
-    const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
-    const int active = fi->active;
-    const double z_r = fi->z_r, d_Pd = fi->d_Pd, e_Pd = fi->e_Pd, e_Pe = fi->e_Pe;
-    const double model_value = fi->model_value, norm_r0 = fi->norm_r0, beta0 = fi->beta, alpha = fi->alpha;
-    const int j0 = fi->j, stop0 = fi->stop, ix = fi->eta_idx;
-    if (!active) {
-        if (lead) {
-            frame_store(&d.F[0], z_r, d_Pd, e_Pd, e_Pe, model_value, norm_r0, alpha, beta0, 0, j0, stop0, ix);
-            d.ctl->tcg_running = 0;
-            msdp_publish(d, d.ctl->k, j0, 0);
-        }
-        return;
-    }
-    const Ctl* c = d.ctl;
-    const bool bench = c->bench_mode != 0;
     int lo, hi;
     msdp_chunk_rows(d.n_loc, d.G, lo, hi);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     constexpr int RPW = 64 / LPR;
     const int sub = lane & (LPR - 1), rsub = lane / LPR;
-    const double* __restrict__ Yl = c->cur ? d.Y[1] : d.Y[0];
-    // rows of the first pass (two rows per lane group when NCH == 1) are loaded before the partial sums
-    // are re-reduced: one memory round trip instead of {partials} -> {rows, pass 1} -> {rows, pass 2}
+    const double* __restrict__ Yl = d.ctl->cur ? d.Y[1] : d.Y[0];
+    // rows of the first pass (two rows per lane group when NCH == 1) are loaded before the frame is read and the partial
+    // sums are re-reduced: one memory round trip instead of {partials} -> {rows, pass 1} -> {rows, pass 2}.  (A launch
+    // behind the end of the tCG loads them for nothing.)
     constexpr int R = (NCH == 1) ? 2 : 1;
     constexpr int RSTEP = MSDP_WAVES * RPW;
     const int rowf = lo + wave * RPW;
@@ -403,44 +388,8 @@ __global__ __launch_bounds__(MSDP_BLOCK) void k_tcg_upd2_obl(Dev d) {
             }
         }
     }
-    double s1, s2, r_r;
-    msdp_sum_partials3_block(d.P, P_S1, P_S2, P_S3, d.G, shb, s1, s2, r_r);
-    const double new_model = s1 + 0.5 * s2;                 // :227
-    const int j = j0 + 1;
-    if (!bench && new_model >= model_value) {               // :228
-        if (lead) {
-            frame_store(&d.F[0], z_r, d_Pd, e_Pd, e_Pe, model_value, norm_r0, alpha, beta0, 0, j, 6, ix);
-            d.ctl->tcg_running = 0;
-            msdp_publish(d, c->k, j, 0);
-        }
-        return;
-    }
-    const int nix = ix ^ 1;                                 // :233-235 commit new_eta/new_Heta
-    const double norm_r = sqrt(r_r);
-    const double nr0t = (c->theta == 1.0) ? norm_r0 : pow(norm_r0, c->theta);   // norm_r0^theta
-    if (!bench && j >= c->mininner && norm_r <= norm_r0 * fmin(nr0t, c->kappa)) {   // :249
-        if (lead) {
-            frame_store(&d.F[0], z_r, d_Pd, e_Pd, e_Pe, new_model, norm_r0, alpha, beta0, 0, j,
-                        (c->kappa < nr0t) ? 3 : 4, nix);
-            d.ctl->tcg_running = 0;
-            msdp_publish(d, c->k, j, 0);
-        }
-        return;
-    }
-    if (j >= c->maxinner) {                                 // loop bound :160 (stop stays 5)
-        if (lead) {
-            frame_store(&d.F[0], z_r, d_Pd, e_Pd, e_Pe, new_model, norm_r0, alpha, beta0, 0, j, stop0, nix);
-            d.ctl->tcg_running = 0;
-            msdp_publish(d, c->k, j, 0);
-        }
-        return;
-    }
-    const double beta = r_r / z_r;                          // :272
-    if (lead) {
-        frame_store(&d.F[0], r_r, r_r + beta * beta * d_Pd /* :287 */, beta * (e_Pd + alpha * d_Pd) /* :286 */, e_Pe,
-                    new_model, norm_r0, alpha, beta, 1, j, stop0, nix);
-        msdp_publish(d, c->k, j, 1);
-    }
+    double beta;
+    if (!msdp_tcg_upd2_scalars(d, shb, beta)) return;
     // mdelta = tangent(z + beta*mdelta), z = r   :273,283
     for (int row0 = rowf; row0 < hi; row0 += R * RSTEP) {
 #pragma unroll
@@ -534,7 +483,7 @@ __global__ __launch_bounds__(MSDP_BLOCK) void k_rtr_begin(Dev d) {
         c->Delta = c->Delta0;
         c->k = 0; c->hessvecs = 0; c->accepted = 0; c->rejected = 0; c->cost_evals = 1;
         c->last_stop_inner = 0;
-        c->done = (c->norm_grad < c->tolgradnorm) || (c->k >= c->maxiter);   // stoppingcriterion.m:51-72
+        c->done = rtr_done(c->norm_grad, c->tolgradnorm, c->k, c->maxiter);
         c->tcg_running = 0;
     }
 }
@@ -545,35 +494,7 @@ __global__ __launch_bounds__(MSDP_BLOCK) void k_rtr_decide(Dev d) {
     const double fp = msdp_sum_partials(d.P, P_F, d.G);
     const double ggp = msdp_sum_partials(d.P, P_GG, d.G);
     const double rd = msdp_sum_partials(d.P, P_RD, d.G);
-    if (threadIdx.x == 0) {
-        Ctl* c = d.ctl;
-        const int f_stop = d.F[0].stop, f_j = d.F[0].j;
-        double rhonum = c->fx - fp;                                          // :548
-        double rhoden = -rd;                                                 // :550
-        const double rho_reg = fmax(1.0, fabs(c->fx)) * 2.220446049250313e-16 * c->rho_reg;   // :579
-        rhonum += rho_reg;
-        rhoden += rho_reg;
-        const bool model_decreased = rhoden >= 0.0;                          // :614
-        const double rho = rhonum / rhoden;                                  // :621
-        if (rho < 0.25 || !model_decreased || isnan(rho)) {                  // :653
-            c->Delta = c->Delta / 4.0;
-        } else if (rho > 0.75 && (f_stop == 1 || f_stop == 2)) {             // :669
-            c->Delta = fmin(2.0 * c->Delta, c->Delta_bar);
-        }
-        if (model_decreased && rho > c->rho_prime) {                         // :688
-            c->cur ^= 1;
-            c->fx = fp; c->gg = ggp; c->norm_grad = sqrt(ggp);
-            c->accepted++;
-        } else {
-            c->rejected++;
-        }
-        c->rho = rho; c->rhonum = rhonum; c->rhoden = rhoden; c->fx_prop = fp; c->gg_prop = ggp;
-        c->k++;                                                              // :729
-        c->hessvecs += f_j;
-        c->cost_evals++;
-        c->last_stop_inner = f_stop;
-        c->done = (c->norm_grad < c->tolgradnorm) || (c->k >= c->maxiter);
-    }
+    if (threadIdx.x == 0) msdp_rtr_decide(d.ctl, d.F[0], fp, ggp, rd);
 }
 
 // ------------------------------------------------------------------ utilities

@@ -20,14 +20,12 @@
 // Lane layout and instances are those of msdp_pose.hip: LPR lanes own a block, NCH double2 per row and lane, widths up to 256
 // (workgroup sizes: PcBlock / PcUpd1Block below).  Only r_new, z and the D rotation rows of Y are resident per block; eta, Heta, mdelta, H mdelta and the
 // gradient stream through.  No instance uses scratch (DESIGN.md lists the registers per instance).
-// The kernels of msdp_pose.hip, msdp_kernels.hip and msdp_tcg_upd2_scalars are not touched: what selects these launchers is
+// The kernels of msdp_pose.hip and msdp_kernels.hip are not touched (msdp_tcg_upd2_scalars serves both, by a compile-time switch): what selects these launchers is
 // d.pcM != nullptr, a field of Dev, so the chunk graph (whose signature is the Dev) is captured again when the option flips.
 #include "msdp_device.h"
 #include <math.h>
 #include <cmath>
 #include <vector>
-
-enum { P_ZR0 = P_AUX, P_ZRN = P_AXB };
 
 // workgroup sizes: those of msdp_pose.hip (16 waves at one chunk per lane, 8 at two) for all but the d = 3 first update.  That one
 // holds four rows of the new r and of z, three of y and the 4 x 4 values of M_i^-1 beside the six streamed operands: its one-chunk
@@ -208,9 +206,9 @@ __global__ __launch_bounds__((PcUpd1Block<D, NCH>::threads)) void k_pose_pc_upd1
     const double d_Hd = shb[0];
     if (fresh) { z_r = shb[1]; d_Pd = z_r; }
     const double alpha = z_r / d_Hd;                                           // :170
-    const double e_Pe_new = e_Pe + 2.0 * alpha * e_Pd + alpha * alpha * d_Pd;  // :173
-    if (!bench && (d_Hd <= 0.0 || e_Pe_new >= Delta * Delta)) {                // :183
-        const double tau = (-e_Pd + sqrt(e_Pd * e_Pd + d_Pd * (Delta * Delta - e_Pe))) / d_Pd;  // :188
+    const double e_Pe_new = tcg_e_Pe_new(e_Pe, alpha, e_Pd, d_Pd);
+    if (!bench && !tcg_step_inside(d_Hd, e_Pe_new, Delta)) {
+        const double tau = tcg_tau(e_Pd, d_Pd, e_Pe, Delta);
         for (int b0 = lo + wave * BPW; b0 < hi; b0 += WAVES * BPW) {
             const int blk = b0 + rsub;
             if (blk < hi) {
@@ -228,7 +226,7 @@ __global__ __launch_bounds__((PcUpd1Block<D, NCH>::threads)) void k_pose_pc_upd1
                     }
             }
         }
-        if (lead) frame_store(&d.F[1], z_r, d_Pd, e_Pd, e_Pe, model_value, norm_r0, alpha0, beta0, 0, j + 1, (d_Hd <= 0.0) ? 1 : 2, ix ^ 1, mi, 0);
+        if (lead) frame_store(&d.F[1], z_r, d_Pd, e_Pd, e_Pe, model_value, norm_r0, alpha0, beta0, 0, j + 1, tcg_boundary_stop(d_Hd), ix ^ 1, mi, 0);
         return;
     }
     double s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0;
@@ -278,78 +276,13 @@ __global__ __launch_bounds__((PcUpd1Block<D, NCH>::threads)) void k_pose_pc_upd1
         frame_store(&d.F[1], z_r, d_Pd, e_Pd, e_Pe_new, model_value, norm_r0, alpha, beta0, 1, j, stop0, ix, mi, 0);
 }
 
-// msdp_tcg_upd2_scalars with the preconditioned recurrences (tCG.m:270-287): beta = z_r_new / z_r with z_r_new = <z, r> of the
-// upd1 launch (P_ZRN); the frame takes z_r := z_r_new, d_Pd := z_r_new + beta^2 d_Pd, e_Pd := beta (e_Pd + alpha d_Pd).  Model
-// check, convergence test (on norm_r = sqrt(r_r) and norm_r0) and loop bound as there.  shb: 4 doubles of LDS.
-__device__ __forceinline__ bool pc_tcg_upd2_scalars(const Dev& d, double* shb, double& beta_out) {
-    const Frame* fi = &d.F[1];
-    const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
-    const int active = fi->active;
-    const double z_r = fi->z_r, d_Pd = fi->d_Pd, e_Pd = fi->e_Pd, e_Pe = fi->e_Pe;
-    const double model_value = fi->model_value, norm_r0 = fi->norm_r0, beta0 = fi->beta, alpha = fi->alpha;
-    const int j0 = fi->j, stop0 = fi->stop, ix = fi->eta_idx;
-    if (!active) {
-        if (lead) {
-            frame_store(&d.F[0], z_r, d_Pd, e_Pd, e_Pe, model_value, norm_r0, alpha, beta0, 0, j0, stop0, ix);
-            d.ctl->tcg_running = 0;
-            msdp_publish(d, d.ctl->k, j0, 0);
-        }
-        return false;
-    }
-    const Ctl* c = d.ctl;
-    const bool bench = c->bench_mode != 0;
-    if (threadIdx.x < 64) {
-        const double a = msdp_sum_partials(d.P, P_S1, d.G), b = msdp_sum_partials(d.P, P_S2, d.G);
-        const double e = msdp_sum_partials(d.P, P_S3, d.G), f = msdp_sum_partials(d.P, P_ZRN, d.G);
-        if (threadIdx.x == 0) { shb[0] = a; shb[1] = b; shb[2] = e; shb[3] = f; }
-    }
-    __syncthreads();
-    const double s1 = shb[0], s2 = shb[1], r_r = shb[2], z_r_new = shb[3];
-    const double new_model = s1 + 0.5 * s2;                 // :227
-    const int j = j0 + 1;
-    if (!bench && new_model >= model_value) {               // :228
-        if (lead) {
-            frame_store(&d.F[0], z_r, d_Pd, e_Pd, e_Pe, model_value, norm_r0, alpha, beta0, 0, j, 6, ix);
-            d.ctl->tcg_running = 0;
-            msdp_publish(d, c->k, j, 0);
-        }
-        return false;
-    }
-    const int nix = ix ^ 1;                                 // :233-235 commit new_eta/new_Heta
-    const double norm_r = sqrt(r_r);
-    const double nr0t = (c->theta == 1.0) ? norm_r0 : pow(norm_r0, c->theta);   // norm_r0^theta
-    if (!bench && j >= c->mininner && norm_r <= norm_r0 * fmin(nr0t, c->kappa)) {   // :249
-        if (lead) {
-            frame_store(&d.F[0], z_r, d_Pd, e_Pd, e_Pe, new_model, norm_r0, alpha, beta0, 0, j, (c->kappa < nr0t) ? 3 : 4, nix);
-            d.ctl->tcg_running = 0;
-            msdp_publish(d, c->k, j, 0);
-        }
-        return false;
-    }
-    if (j >= c->maxinner) {                                 // loop bound :160 (stop stays 5)
-        if (lead) {
-            frame_store(&d.F[0], z_r, d_Pd, e_Pd, e_Pe, new_model, norm_r0, alpha, beta0, 0, j, stop0, nix);
-            d.ctl->tcg_running = 0;
-            msdp_publish(d, c->k, j, 0);
-        }
-        return false;
-    }
-    const double beta = z_r_new / z_r;                      // :272
-    if (lead) {
-        frame_store(&d.F[0], z_r_new, z_r_new + beta * beta * d_Pd /* :287 */, beta * (e_Pd + alpha * d_Pd) /* :286 */, e_Pe,
-                    new_model, norm_r0, alpha, beta, 1, j, stop0, nix);
-        msdp_publish(d, c->k, j, 1);
-    }
-    beta_out = beta;
-    return true;
-}
-
-// tCG.m:227-287: the scalar decisions above, then mdelta = tangent(z + beta mdelta) block by block (:273, :283)
+// tCG.m:227-287: the scalar decisions (msdp_tcg_upd2_scalars in its preconditioned form: beta = z_r_new / z_r with z_r_new = <z, r>
+// of the upd1 launch, P_ZRN), then mdelta = tangent(z + beta mdelta) block by block (:273, :283)
 template <int D, int LPR, int NCH>
 __global__ __launch_bounds__((PcBlock<D, NCH>::threads)) void k_pose_pc_upd2(Dev d) {
     __shared__ double shb[4];
     double beta;
-    if (!pc_tcg_upd2_scalars(d, shb, beta)) return;
+    if (!msdp_tcg_upd2_scalars<true>(d, shb, beta)) return;
     constexpr int B = D + 1, WAVES = PcBlock<D, NCH>::threads / 64, BPW = 64 / LPR;
     int lo, hi;
     msdp_chunk_rows(d.nb, d.G, lo, hi);

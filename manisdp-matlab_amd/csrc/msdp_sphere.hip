@@ -8,72 +8,13 @@
 #include "msdp_device.h"
 #include <math.h>
 
-__device__ __forceinline__ void sph_frame_store(Frame* o, double z_r, double d_Pd, double e_Pd, double e_Pe,
-                                                double model_value, double norm_r0, double alpha, double beta,
-                                                int active, int j, int stop, int eta_idx) {
-    o->z_r = z_r; o->d_Pd = d_Pd; o->e_Pd = e_Pd; o->e_Pe = e_Pe; o->model_value = model_value;
-    o->norm_r0 = norm_r0; o->alpha = alpha; o->beta = beta;
-    o->active = active; o->j = j; o->stop = stop; o->eta_idx = eta_idx;
-}
-
-// tCG.m:227-273 (decisions identical to k_tcg_upd2_obl); v = r + beta*mdelta -> md, partial <Y, v> -> P_AUX
+// tCG.m:227-273 (the decisions: msdp_tcg_upd2_scalars); v = r + beta*mdelta -> md, partial <Y, v> -> P_AUX
 __global__ __launch_bounds__(MSDP_BLOCK) void k_sph_upd2a(Dev d) {
     __shared__ double sh[3 * MSDP_WAVES];
     __shared__ double shb[4];
-    const Frame* fi = &d.F[1];
-    const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
-    const int active = fi->active;
-    const double z_r = fi->z_r, d_Pd = fi->d_Pd, e_Pd = fi->e_Pd, e_Pe = fi->e_Pe;
-    const double model_value = fi->model_value, norm_r0 = fi->norm_r0, beta0 = fi->beta, alpha = fi->alpha;
-    const int j0 = fi->j, stop0 = fi->stop, ix = fi->eta_idx;
-    if (!active) {
-        if (lead) {
-            sph_frame_store(&d.F[0], z_r, d_Pd, e_Pd, e_Pe, model_value, norm_r0, alpha, beta0, 0, j0, stop0, ix);
-            d.ctl->tcg_running = 0;
-            msdp_publish(d, d.ctl->k, j0, 0);
-        }
-        return;
-    }
+    double beta;
+    if (!msdp_tcg_upd2_scalars(d, shb, beta)) return;
     const Ctl* c = d.ctl;
-    const bool bench = c->bench_mode != 0;
-    double s1, s2, r_r;
-    msdp_sum_partials3_block(d.P, P_S1, P_S2, P_S3, d.G, shb, s1, s2, r_r);
-    const double new_model = s1 + 0.5 * s2;                 // tCG.m:227
-    const int j = j0 + 1;
-    if (!bench && new_model >= model_value) {               // :228
-        if (lead) {
-            sph_frame_store(&d.F[0], z_r, d_Pd, e_Pd, e_Pe, model_value, norm_r0, alpha, beta0, 0, j, 6, ix);
-            d.ctl->tcg_running = 0;
-            msdp_publish(d, c->k, j, 0);
-        }
-        return;
-    }
-    const int nix = ix ^ 1;
-    const double norm_r = sqrt(r_r);
-    const double nr0t = (c->theta == 1.0) ? norm_r0 : pow(norm_r0, c->theta);
-    if (!bench && j >= c->mininner && norm_r <= norm_r0 * fmin(nr0t, c->kappa)) {   // :249
-        if (lead) {
-            sph_frame_store(&d.F[0], z_r, d_Pd, e_Pd, e_Pe, new_model, norm_r0, alpha, beta0, 0, j,
-                            (c->kappa < nr0t) ? 3 : 4, nix);
-            d.ctl->tcg_running = 0;
-            msdp_publish(d, c->k, j, 0);
-        }
-        return;
-    }
-    if (j >= c->maxinner) {
-        if (lead) {
-            sph_frame_store(&d.F[0], z_r, d_Pd, e_Pd, e_Pe, new_model, norm_r0, alpha, beta0, 0, j, stop0, nix);
-            d.ctl->tcg_running = 0;
-            msdp_publish(d, c->k, j, 0);
-        }
-        return;
-    }
-    const double beta = r_r / z_r;                          // :272
-    if (lead) {
-        sph_frame_store(&d.F[0], r_r, r_r + beta * beta * d_Pd, beta * (e_Pd + alpha * d_Pd), e_Pe, new_model, norm_r0,
-                        alpha, beta, 1, j, stop0, nix);
-        msdp_publish(d, c->k, j, 1);
-    }
     int lo, hi;
     msdp_chunk_rows(d.n_loc, d.G, lo, hi);
     const double* __restrict__ Yl = c->cur ? d.Y[1] : d.Y[0];

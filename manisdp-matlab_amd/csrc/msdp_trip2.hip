@@ -120,13 +120,13 @@ __global__ __launch_bounds__(MSDP_BLOCK) void k_tcg2_head(Dev d) {
         j = j0 + 1;
         int fin = 0, fstop = stop0, fix = ix;
         double fmodel = model_value;
-        if (!bench && new_model >= model_value) { fin = 1; fstop = 6; }                     // :228 (the old eta, Heta stay)
+        if (!bench && !tcg_model_decreased(new_model, model_value)) { fin = 1; fstop = 6; }  // (the old eta, Heta stay)
         else {
             nix = ix ^ 1;                                   // :233-235 commit new_eta / new_Heta
             const double norm_r = sqrt(r_r);
-            const double nr0t = (c->theta == 1.0) ? norm_r0 : pow(norm_r0, c->theta);
-            if (!bench && j >= c->mininner && norm_r <= norm_r0 * fmin(nr0t, c->kappa)) {   // :249
-                fin = 1; fstop = (c->kappa < nr0t) ? 3 : 4; fix = nix; fmodel = new_model;
+            const double nr0t = tcg_nr0t(norm_r0, c->theta);
+            if (!bench && !tcg_unconverged(j, c->mininner, norm_r, norm_r0, nr0t, c->kappa)) {
+                fin = 1; fstop = tcg_converged_stop(c->kappa, nr0t); fix = nix; fmodel = new_model;
             } else if (j >= c->maxinner) {                  // loop bound :160 (stop stays 5)
                 fin = 1; fix = nix; fmodel = new_model;
             }
@@ -147,10 +147,10 @@ __global__ __launch_bounds__(MSDP_BLOCK) void k_tcg2_head(Dev d) {
             }
             return;
         }
-        beta = r_r / z_r;                                   // :272
+        double n_z_r = z_r, n_e_Pd = e_Pd, n_d_Pd = d_Pd;
+        beta = tcg_recurrences(r_r, alpha, n_z_r, n_e_Pd, n_d_Pd);
         if (lead) {
-            frame_store(&d.F[0], r_r, r_r + beta * beta * d_Pd /* :287 */, beta * (e_Pd + alpha * d_Pd) /* :286 */, e_Pe,
-                        new_model, norm_r0, alpha, beta, 1, j, stop0, nix, mi ^ 1, 0);
+            frame_store(&d.F[0], n_z_r, n_d_Pd, n_e_Pd, e_Pe, new_model, norm_r0, alpha, beta, 1, j, stop0, nix, mi ^ 1, 0);
             msdp_publish(d, c->k, j, 1);
         }
     } else if (lead) {
@@ -276,9 +276,9 @@ __global__ __launch_bounds__(MSDP_BLOCK) void k_tcg2_upd(Dev d) {
     }
     const double d_Hd = msdp_sum_partials_block(d.P, P_DHD, d.G, shb);        // :166
     const double alpha = z_r / d_Hd;                                          // :170
-    const double e_Pe_new = e_Pe + 2.0 * alpha * e_Pd + alpha * alpha * d_Pd; // :173
-    if (!bench && (d_Hd <= 0.0 || e_Pe_new >= Delta * Delta)) {               // :183
-        const double tau = (-e_Pd + sqrt(e_Pd * e_Pd + d_Pd * (Delta * Delta - e_Pe))) / d_Pd;   // :188
+    const double e_Pe_new = tcg_e_Pe_new(e_Pe, alpha, e_Pd, d_Pd);
+    if (!bench && !tcg_step_inside(d_Hd, e_Pe_new, Delta)) {
+        const double tau = tcg_tau(e_Pd, d_Pd, e_Pe, Delta);
         double* __restrict__ Hout = ix ? d.Heta[0] : d.Heta[1];
         for (int64_t ib = i0; ib < e1; ib += 2 * STEP) {
 #pragma unroll
@@ -293,7 +293,7 @@ __global__ __launch_bounds__(MSDP_BLOCK) void k_tcg2_upd(Dev d) {
             }
         }
         if (lead) {
-            frame_store(&d.F[1], z_r, d_Pd, e_Pd, e_Pe, model_value, norm_r0, alpha0, beta0, 0, j + 1, (d_Hd <= 0.0) ? 1 : 2, ix ^ 1, mi, 0);
+            frame_store(&d.F[1], z_r, d_Pd, e_Pd, e_Pe, model_value, norm_r0, alpha0, beta0, 0, j + 1, tcg_boundary_stop(d_Hd), ix ^ 1, mi, 0);
             d.ctl->tcg_running = 0;
         }
         return;

@@ -201,35 +201,7 @@ __global__ __launch_bounds__(PB) void k_tr_tail_obl(Dev d, unsigned long long* s
     }
     if (two) { if (!psync2(d.xr2_blk, shpeer, d.xr2_n, d.xr2_me, xri, 1, GS, 3, pf, pgg, prd, sh, shb, err, bid, backoff)) return; }
     else if (!psync(sb, 0, GS, 3, pf, pgg, prd, sh, shb, err, bid, backoff)) return;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {                 // trustregions.m:548-729 (same arithmetic as k_rtr_decide)
-        const int f_stop = d.F[0].stop, f_j = d.F[0].j;
-        const double fp = pf, ggp = pgg;
-        double rhonum = c->fx - fp;                                          // :548
-        double rhoden = -prd;                                                // :550
-        const double rho_reg = fmax(1.0, fabs(c->fx)) * 2.220446049250313e-16 * c->rho_reg;   // :579
-        rhonum += rho_reg;
-        rhoden += rho_reg;
-        const bool model_decreased = rhoden >= 0.0;                          // :614
-        const double rho = rhonum / rhoden;                                  // :621
-        if (rho < 0.25 || !model_decreased || isnan(rho)) {                  // :653
-            c->Delta = c->Delta / 4.0;
-        } else if (rho > 0.75 && (f_stop == 1 || f_stop == 2)) {             // :669
-            c->Delta = fmin(2.0 * c->Delta, c->Delta_bar);
-        }
-        if (model_decreased && rho > c->rho_prime) {                         // :688
-            c->cur ^= 1;
-            c->fx = fp; c->gg = ggp; c->norm_grad = sqrt(ggp);
-            c->accepted++;
-        } else {
-            c->rejected++;
-        }
-        c->rho = rho; c->rhonum = rhonum; c->rhoden = rhoden; c->fx_prop = fp; c->gg_prop = ggp;
-        c->k++;                                                              // :729
-        c->hessvecs += f_j;
-        c->cost_evals++;
-        c->last_stop_inner = f_stop;
-        c->done = (c->norm_grad < c->tolgradnorm) || (c->k >= c->maxiter);
-    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) msdp_rtr_decide(c, d.F[0], pf, pgg, prd);   // trustregions.m:548-729, as k_rtr_decide
 }
 
 static int tail_lpr(const Dev& d) {

@@ -1,4 +1,4 @@
-"""Every exit of the truncated CG and every outcome of the trust-region update, iteration by iteration, in every copy of the decision
+"""Every exit of the truncated CG and every outcome of the trust-region update, iteration by iteration, in every route through the decision
 code (the routing table ROUTES of tests/tr_decisions_ref.py).
 
 For each (route, case, option set) and each k = 1 ... K, K = tr_decisions_ref.prefix (the decided prefix of the case under the set, cut

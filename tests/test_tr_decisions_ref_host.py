@@ -2,7 +2,7 @@
 case table against the coverage tests/test_gpu_tr_decisions.py relies on.  A case that misses a check here is replaced; the cut-off
 DECIDED = 1e-9 is not moved.
 
-Per route row (a copy of the decision code), the compared prefixes of its cases (T.prefix: the decided prefix, cut where the
+Per route row (a route through the decision code), the compared prefixes of its cases (T.prefix: the decided prefix, cut where the
 reference's own cost stops being reproducible to the device's bound) together must contain the stop codes 1 to 5, the
 outcomes accept-double, accept-double_capped, accept-keep, accept-quarter and reject-quarter, and a stop on tolgradnorm at an
 iteration 0 < k < MAXITER.

@@ -21,7 +21,7 @@ every operator to, the headroom for what accumulates over a tCG of a few dozen t
 a tolerance on the device: a case is compared with the device up to its first undecided iteration and no further
 (`decided_prefix`).  tests/test_tr_decisions_ref_host.py holds this file to the oracle and the case table to its coverage.
 
-The case table: ROUTES names every copy of the decision code in the device sources with the handle options that
+The case table: ROUTES names every route through the decision code in the device sources with the handle options that
 reach it and what the path queries must report; `case(name)` builds the problems, at the smallest shapes each route accepts;
 OPTION_SETS are the option sets every case runs under for MAXITER trust-region iterations."""
 import functools
@@ -444,7 +444,7 @@ def ends_in_mid_run(name, opt):
 
 
 # ------------------------------------------------------------------ the routes
-# Every copy of the decision code (row), the handle options that reach it (set in this order before the point), what tcg_path(),
+# Every route through the decision code (row), the handle options that reach it (set in this order before the point), what tcg_path(),
 # persist_form() and trip_form() must report after every call, whether the chunked trips run with "graph" 1 and 0, and its cases.
 _TORUS = ("torus:7x11:4", "torus:7x11:8", "torus:5x10:5", "torus:33x37:17")
 _BLOCK = ("stiefel:67:3:6:5", "stiefel:101:2:4:4", "pose:41:2:4:4", "pose:67:3:6:5")
@@ -473,7 +473,7 @@ ROUTES = {
                    cases=("theta:1:3", "theta:1:6", "generic:mcp100:5")),
     # msdp_tcg_upd2_scalars (msdp_device.h)
     "block": dict(row="block", opts=(), path=0, trip=3, graphs=(1, 0), cases=_BLOCK),
-    # pc_tcg_upd2_scalars (msdp_pose_precon.hip)
+    # msdp_tcg_upd2_scalars<true>, the preconditioned form (k_pose_pc_upd2, msdp_pose_precon.hip)
     "pose_precon": dict(row="pose_precon", opts=(("precon", 1),), path=0, trip=3, graphs=(1, 0),
                         cases=("posepc:41:2:4:4", "posepc:67:3:6:5", "posepc:67:3:6:5:w12", "posepc:67:3:6:5:w20")),
     # k_tcg_persist_blk (msdp_blockpersist.hip)

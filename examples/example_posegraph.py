@@ -6,7 +6,9 @@ positions).  The poses are then rounded on the host (problems.round_poses) and c
 rotation and shift the problem cannot see (problems.pose_error).
 argv = [n, default 2000; d, default 3; degree, default 8; sigma_r, default 0.1; sigma_t, default 0.1; seed, default 0]; --persist anywhere on the line: the tCG of every trust-region iteration as one
 persistent launch where the handle is eligible (options["block_persist"]); --precon anywhere on the line: block-Jacobi preconditioned tCG
-(options["precon"] = "blockjacobi": the diagonal blocks of C; the handle then runs the generic trips)."""
+(options["precon"] = "blockjacobi": the diagonal blocks of C; the handle then runs the generic trips); --device-factor anywhere on the
+line: the factor stays on the device between the trustregions() calls and the poses are rounded there too
+(options["block_factor"] = "device", options["round_blocks"]: data["R"] and data["t"], which the printed errors are then taken from)."""
 import sys
 import time
 
@@ -17,7 +19,8 @@ from manisdp_matlab_amd import problems, solvers
 
 persist = "--persist" in sys.argv
 precon = "--precon" in sys.argv
-sys.argv = [a for a in sys.argv if a not in ("--persist", "--precon")]
+device_factor = "--device-factor" in sys.argv
+sys.argv = [a for a in sys.argv if a not in ("--persist", "--precon", "--device-factor")]
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
 d = int(sys.argv[2]) if len(sys.argv) > 2 else 3
@@ -26,10 +29,11 @@ sigma_r = float(sys.argv[4]) if len(sys.argv) > 4 else 0.1
 sigma_t = float(sys.argv[5]) if len(sys.argv) > 5 else 0.1
 C, R_true, t_true, edges, _, _ = problems.pose_graph(n, d, degree, sigma_r, sigma_t, int(sys.argv[6]) if len(sys.argv) > 6 else 0)
 t = time.time()
-Y, fval, data = solvers.ManiSDP_posegraph(C, d, {"tol": 1e-8, "block_persist": persist, "precon": "blockjacobi" if precon else None})
+Y, fval, data = solvers.ManiSDP_posegraph(C, d, {"tol": 1e-8, "block_persist": persist, "precon": "blockjacobi" if precon else None,
+                                               "block_factor": "device" if device_factor else "host", "round_blocks": device_factor})
 e = np.sqrt(np.maximum(np.linalg.eigvalsh(Y.T @ Y), 0.0))
 rank = int(np.sum(e >= 1e-3 * e.max()))
-R, pos = problems.round_poses(Y, d)
+R, pos = (data["R"], data["t"]) if "R" in data else problems.round_poses(Y, d)
 print("ManiSDP: optimum = %.8f, gap = %.1e, dinf = %.1e, time = %.2fs (rank %d, factor width %d, %d edges, %d Hess-vecs)"
       % (fval, data["gap"], data["dinf"], time.time() - t, rank, Y.shape[1], len(edges), data["hessvecs"]))
 print("rounded poses: max_i |R_i Q - R_true_i|_F = %.3e, max_i |t_i Q - s - t_true_i| = %.3e"

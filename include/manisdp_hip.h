@@ -336,6 +336,28 @@ int msdp_get_point_all(msdp_handle h, double* Y);
 int msdp_factor_gram(msdp_handle h, double* G);
 int msdp_factor_rotate(msdp_handle h, int32_t r, const double* Q);
 int msdp_factor_append(msdp_handle h, int32_t k, const double* V, double alpha, int32_t normalize);
+
+/* The same steps for the block kinds (msdp_create_onlyunitblockdiag_csc / msdp_create_posegraph_csc; the three calls above
+ * stay refused for them), and the rounding to rotations / poses.  Any other handle: MSDP_EUNSUPPORTED, the message names the
+ * call.  No resident point: MSDP_ESTATE.
+ * msdp_blockfactor_gram: G (p x p) = Y'Y of the resident factor, free rows included.
+ * msdp_blockfactor_rotate: Y <- polar_blocks(Y*Q), Q p x r ROW-major, d <= r <= p (else MSDP_EINVAL).
+ * msdp_blockfactor_append: Y <- polar_blocks([Y, alpha*V]), V N x k column-major; MSDP_EUNSUPPORTED when p + k exceeds the
+ *   allocated capacity (re-enter through msdp_set_point).
+ *   polar_blocks: the d orthonormal rows of every block are replaced by their polar factor (A A')^(-1/2) A, applied twice so
+ *   that ill-conditioned blocks end orthonormal to rounding; the free row of a pose-graph block is the plain product /
+ *   concatenation.  A block whose Gram matrix A A' has lambda_min <= 1e-12 lambda_max is degenerate: *ndeg counts them, and
+ *   with *ndeg > 0 the call returns 0 WITHOUT changing the resident point, its width or the handle's state (take that step
+ *   on the host).
+ * msdp_blockfactor_round: W p x d ROW-major (the caller passes the top-d eigenvectors of Y'Y).  Z_i = Y_i*W (rotation rows),
+ *   t_i = tau_i*W (pose-graph handles).  Where more than half of det Z_i are negative the last column of every Z_i and the
+ *   last entry of every t_i change sign (*flipped = 1).  R_i = the nearest rotation to Z_i.  R: (n, d, d) row-major; t:
+ *   (n, d), NULL for a unit-block-diagonal handle and non-NULL for a pose-graph handle (else MSDP_EINVAL).  The degenerate
+ *   rule applies to Z_i Z_i': with *ndeg > 0 R and t are not to be used. */
+int msdp_blockfactor_gram(msdp_handle h, double* G);
+int msdp_blockfactor_rotate(msdp_handle h, int32_t r, const double* Q, int32_t* ndeg);
+int msdp_blockfactor_append(msdp_handle h, int32_t k, const double* V, double alpha, int32_t* ndeg);
+int msdp_blockfactor_round(msdp_handle h, const double* W, double* R, double* t, int32_t* flipped, int32_t* ndeg);
 int msdp_get_p(msdp_handle h, int32_t* p);
 /* MSDP_KIND_* of the handle: tells a binding which factor layout the handle expects at the boundary
  * (p x n for ONLYUNITDIAG / UNITDIAG, n x p for UNITTRACE / GENERIC) without guessing from array shapes. */

@@ -125,6 +125,10 @@ SIGNATURES = {
     "msdp_factor_gram": (C.c_int, [C.c_void_p, _dp]),
     "msdp_factor_rotate": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
     "msdp_factor_append": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.c_double, C.c_int32]),
+    "msdp_blockfactor_gram": (C.c_int, [C.c_void_p, _dp]),
+    "msdp_blockfactor_rotate": (C.c_int, [C.c_void_p, C.c_int32, _dp, _i32p]),
+    "msdp_blockfactor_append": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.c_double, _i32p]),
+    "msdp_blockfactor_round": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _i32p, _i32p]),
     "msdp_create_dual_unitdiag": (C.c_int, [C.c_int64, C.c_int64, _i64p, _i64p, _dp, _dp, _dp, _dp, C.c_int32, _i64p, _i64p, _dp,
                                             _dp, C.c_int32, C.POINTER(C.c_void_p)]),
     "msdp_create_dual": (C.c_int, [C.c_int64, C.c_int64, _i64p, _i64p, _dp, _dp, _dp, _dp, C.c_int32, _i64p, _i64p, _dp,
@@ -619,6 +623,57 @@ class Handle:
         assert Vf.shape[0] == self.n
         _check(self._lib.msdp_factor_append(self._h, Vf.shape[1], _dptr(Vf), float(alpha), 1 if normalize else 0))
         self.p += Vf.shape[1]
+
+    # ---- the block kinds' factor between two trustregions() calls, and their rounding (msdp_blockfactor_*)
+    def blockfactor_gram(self):
+        """p x p Gram matrix Y'Y of the resident factor of an onlyunitblockdiag / posegraph handle (computed on the device)."""
+        G = np.zeros((self.p, self.p))
+        _check(self._lib.msdp_blockfactor_gram(self._h, _dptr(G)))
+        return G
+
+    def blockfactor_rotate(self, Q):
+        """Resident factor <- polar_blocks(factor @ Q) (Q: p x r, d <= r <= p), on the device.  Returns the number of degenerate
+        blocks; when it is not 0 the resident point and its width are unchanged (msdp_blockfactor_rotate)."""
+        Q = np.ascontiguousarray(Q, dtype=np.float64)
+        if Q.ndim != 2 or (self.p and Q.shape[0] != self.p):      # (no point yet: the library refuses the call)
+            raise ValueError(f"blockfactor_rotate: Q must be p x r with p = {self.p}, not {Q.shape}")
+        ndeg = C.c_int32()
+        _check(self._lib.msdp_blockfactor_rotate(self._h, Q.shape[1], _dptr(Q), C.byref(ndeg)))
+        if ndeg.value == 0:
+            self.p = Q.shape[1]
+        return ndeg.value
+
+    def blockfactor_append(self, V, alpha):
+        """Resident factor <- polar_blocks([factor, alpha * V]) (V: N x k), on the device.  Returns the number of degenerate
+        blocks; when it is not 0 the resident point and its width are unchanged (msdp_blockfactor_append)."""
+        Vf = np.asfortranarray(V, dtype=np.float64)
+        if Vf.ndim != 2 or Vf.shape[0] != self.n:
+            raise ValueError(f"blockfactor_append: V must be N x k with N = {self.n}, not {Vf.shape}")
+        ndeg = C.c_int32()
+        _check(self._lib.msdp_blockfactor_append(self._h, Vf.shape[1], _dptr(Vf), float(alpha), C.byref(ndeg)))
+        if ndeg.value == 0:
+            self.p += Vf.shape[1]
+        return ndeg.value
+
+    def round_blocks(self, W=None):
+        """Rotations (and positions, posegraph) from the resident factor, on the device (msdp_blockfactor_round): Z_i = Y_i W for
+        W p x d -- None: the top-d eigenvectors of blockfactor_gram() --, the determinant sign by the majority of the blocks,
+        R_i the nearest rotation to Z_i.  Returns (R, t, flipped, ndeg): R (n, d, d), t (n, d) or None, flipped 1 when the global
+        reflection was applied, ndeg the number of degenerate blocks (not 0: R and t are not to be used)."""
+        d = max(self.blk - self.efree, 1)                 # (a handle without blocks: the library refuses the call)
+        if W is None:
+            w, Q = np.linalg.eigh(self.blockfactor_gram())
+            W = Q[:, np.argsort(w)[::-1][:d]]
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        if self.blk and self.p and W.shape != (self.p, d):
+            raise ValueError(f"round_blocks: W must be p x d = {self.p} x {d}, not {W.shape}")
+        nb = self.n // self.blk if self.blk else 0
+        R = np.zeros((max(nb, 1), d, d))
+        t = np.zeros((max(nb, 1), d)) if self.efree else None
+        flipped, ndeg = C.c_int32(), C.c_int32()
+        _check(self._lib.msdp_blockfactor_round(self._h, _dptr(W), _dptr(R), _dptr(t) if self.efree else None,
+                                                C.byref(flipped), C.byref(ndeg)))
+        return R, t, flipped.value, ndeg.value
 
     def set_multipliers(self, y, sigma):
         y = np.ascontiguousarray(y, dtype=np.float64)

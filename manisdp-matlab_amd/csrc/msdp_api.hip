@@ -800,6 +800,8 @@ static int adopt_point(msdp_handle h, int slot, int p) {
     h->gradnorm_valid = false;
     return 0;
 }
+// (for the re-shaping calls of the block kinds, msdp_blockfactor.hip)
+int msdp_adopt_point(msdp_handle h, int slot, int p) { return adopt_point(h, slot, p); }
 
 extern "C" int msdp_factor_gram(msdp_handle h, double* G) {
     MSDP_CHECK_H(h);

@@ -408,6 +408,7 @@ int msdp_alloc_vectors(msdp_handle h, int pcap);
 int msdp_alloc_common(msdp_handle h);
 int msdp_upload_sparse_rows(msdp_handle h);
 int msdp_ensure_state(msdp_handle h);
+int msdp_adopt_point(msdp_handle h, int slot, int p);         // the resident point now stands in Y[slot] with width p: width, stride, grid, flags
 // msdp_mem.hip
 int msdp_dev_alloc_bytes(msdp_handle h, void** out, size_t bytes);            // freed with the handle, or by msdp_dev_free
 int msdp_dev_alloc_uncached_bytes(msdp_handle h, void** out, size_t bytes);   // from the pool of exchange memory (plain memory when that fails)

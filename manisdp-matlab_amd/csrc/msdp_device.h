@@ -579,6 +579,76 @@ __device__ __forceinline__ void msdp_sym_invsqrt(const double (&G)[D][D], double
         }
 }
 
+// The sibling of msdp_sym_invsqrt for a G that is only positive SEMI-definite in exact arithmetic (msdp_blockfactor.hip: the
+// Gram matrix of a block after a rank cut, of a d x d block Y_i W): the same Jacobi iteration (a copy, so that the function
+// above and its callers keep their bits), and beside R the eigenvalues lam[] in no particular order -- the caller decides from
+// them whether R means anything.  R = V diag(s_k / sqrt(max(lam_k, tiny))) V': never a division by zero; s_k = -1 on the
+// smallest eigenvalue when flip_smallest (the nearest ROTATION to a block of negative determinant), 1 elsewhere.
+template <int D>
+__device__ __forceinline__ void msdp_sym_invsqrt_eig(const double (&G)[D][D], double (&R)[D][D], double (&lam)[D], bool flip_smallest) {
+    double A[D][D], V[D][D];
+#pragma unroll
+    for (int a = 0; a < D; ++a)
+#pragma unroll
+        for (int b = 0; b < D; ++b) { A[a][b] = G[a][b]; V[a][b] = (a == b) ? 1.0 : 0.0; }
+    for (int sweep = 0; sweep < (D == 2 ? 1 : MSDP_JACOBI_SWEEPS); ++sweep) {
+        if (D > 2) {
+            double off = 0.0, dg = 0.0;
+#pragma unroll
+            for (int a = 0; a < D; ++a) {
+                dg += A[a][a] * A[a][a];
+#pragma unroll
+                for (int b = a + 1; b < D; ++b) off += A[a][b] * A[a][b];
+            }
+            if (!(off > 1e-32 * dg)) break;                 // (also leaves on a NaN)
+        }
+#pragma unroll
+        for (int p = 0; p < D; ++p)
+#pragma unroll
+            for (int q = p + 1; q < D; ++q) {
+                const double apq = A[p][q];
+                if (apq != 0.0) {
+                    const double th = (A[q][q] - A[p][p]) / (2.0 * apq);
+                    const double t = copysign(1.0, th) / (fabs(th) + sqrt(th * th + 1.0));
+                    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+                    A[p][p] -= t * apq; A[q][q] += t * apq;
+                    A[p][q] = A[q][p] = 0.0;
+#pragma unroll
+                    for (int r = 0; r < D; ++r) {
+                        if (r != p && r != q) {
+                            const double arp = A[r][p], arq = A[r][q];
+                            A[r][p] = A[p][r] = c * arp - s * arq;
+                            A[r][q] = A[q][r] = s * arp + c * arq;
+                        }
+                        const double vrp = V[r][p], vrq = V[r][q];
+                        V[r][p] = c * vrp - s * vrq;
+                        V[r][q] = s * vrp + c * vrq;
+                    }
+                }
+            }
+    }
+    double lmin = A[0][0];
+#pragma unroll
+    for (int k = 1; k < D; ++k) lmin = fmin(lmin, A[k][k]);
+    double is[D];
+    bool flipped = !flip_smallest;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        lam[k] = A[k][k];
+        is[k] = 1.0 / sqrt(fmax(A[k][k], 2.2250738585072014e-308));
+        if (!flipped && A[k][k] == lmin) { is[k] = -is[k]; flipped = true; }      // the first of equal smallest ones
+    }
+#pragma unroll
+    for (int a = 0; a < D; ++a)
+#pragma unroll
+        for (int b = a; b < D; ++b) {
+            double s = 0.0;
+#pragma unroll
+            for (int k = 0; k < D; ++k) s += V[a][k] * is[k] * V[b][k];
+            R[a][b] = R[b][a] = s;
+        }
+}
+
 // tCG.m:227-287, the scalar part of the second update of a three-launch trip (everything an upd2 kernel decides before it
 // touches a row): model check, convergence test, loop bound, the new frame -- the rules of msdp_tr_rules.h on the frame F[1]
 // -> F[0].  The single reader of F[1] and writer of F[0] of these trips.  Returns true when a new direction

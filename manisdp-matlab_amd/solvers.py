@@ -603,6 +603,65 @@ def _polar_blocks(Y, d):
     return np.ascontiguousarray((u @ vt).reshape(Y.shape))
 
 
+def _block_factor_option(o, what):
+    """options["block_factor"] of the two block kinds: "host" (default) or "device"; anything else is a ValueError."""
+    mode = o.get("block_factor", "host")
+    if mode not in ("host", "device"):
+        raise ValueError(f"options['block_factor'] must be 'host' or 'device' for the {what} problem, not {mode!r}")
+    return mode
+
+
+def _block_reshape_device(h, d, polar, Q, e, r, p, vS, nne, alpha, data):
+    """The re-shape of a block kind's factor between two trustregions() calls on the device (msdp_blockfactor_rotate /
+    _append): the cut to r columns where d <= r <= p - 1, then the widening by alpha vS(:, 1:nne), the blocks re-orthonormalised
+    by the same launches.  Returns (None, p) with the new point resident.  A call that reports degenerate blocks (it has not
+    changed the point) or exceeds the handle's capacity hands this iteration to the host: the factor comes down as the device
+    holds it (cut or not), takes today's host steps with `polar`, and (Y, p) is returned for set_point."""
+    cut = d <= r <= p - 1
+    cut_done = False
+    ok = True
+    try:
+        if cut:
+            ok = h.blockfactor_rotate(Q[:, :r]) == 0
+            if ok:
+                cut_done = True
+                p = r
+                data["factor_device_calls"] += 1
+        if ok:
+            if p + nne > 256:
+                raise RuntimeError(f"the factor width would exceed the device's 256 columns (p = {p}, {nne} more)")
+            ok = h.blockfactor_append(vS[:, :nne], alpha) == 0
+            if ok:
+                data["factor_device_calls"] += 1
+                return None, p + nne
+    except _lib.MsdpError as err:                          # wider than the handle's buffers: re-enter through set_point
+        if "allocated capacity" not in str(err):
+            raise
+    data["factor_host_fallbacks"] += 1
+    Y = h.get_point()
+    if cut and not cut_done:
+        Y = polar(_rank_cut(Y, Q, e, r), d)
+    Y = polar(np.hstack([Y, alpha * vS[:, :nne]]), d)
+    return Y, Y.shape[1]
+
+
+def _round_blocks_option(h, d, Y_eval, data):
+    """options["round_blocks"]: data["R"] (and data["t"] of a pose-graph handle) from Handle.round_blocks at the evaluated
+    point, which both settings of block_factor leave resident when their loop ends; the host functions of problems.py where
+    the device reports degenerate blocks (data["round_fallback"] = True)."""
+    from . import problems
+    R, t, _, ndeg = h.round_blocks()
+    data["round_fallback"] = ndeg > 0
+    if ndeg > 0:
+        if h.efree:
+            R, t = problems.round_poses(Y_eval, d)
+        else:
+            R = problems.round_rotations(Y_eval, d)
+    data["R"] = R
+    if h.efree:
+        data["t"] = t
+
+
 def ManiSDP_onlyunitblockdiag(C, d, options=None, verbose=True, rng=None):
     """``min <C, X>  s.t. X PSD of order N = n d, X_[ii] = I_d`` for d = 2 or 3 (synchronisation over O(d) / SO(d): rotation
     averaging, pose graphs; problems.rotation_synchronization), on the stacked Stiefel manifold of the factor: blocks of d
@@ -618,6 +677,14 @@ def ManiSDP_onlyunitblockdiag(C, d, options=None, verbose=True, rng=None):
     [Y, alpha V(:, 1:nne)], and after either step every block is re-orthonormalised on the host by its polar factor.
     ``options["block_persist"] = True`` runs the tCG of every trust-region iteration as one persistent launch where the handle
     is eligible (p <= 32; msdp_set_option "block_persist"), the generic trips elsewhere; default False.
+    ``options["block_factor"] = "device"`` keeps the factor on the device between the trustregions() calls: the rank decision
+    from Handle.blockfactor_gram, the cut, the widening and the re-orthonormalisation by blockfactor_rotate / _append, one
+    set_point per solve; an iteration whose call reports degenerate blocks or exceeds the handle's capacity takes the host
+    steps (``data["factor_host_fallbacks"]``; ``data["factor_device_calls"]`` counts the device calls).  Default ``"host"``.
+    ``data["factor_seconds"]`` is the wall time of the re-shapes on either path: rank decision, cut, widening, polar factors
+    and the transfers only that path needs (host: get_point and the next set_point; device: the Gram matrix).
+    ``options["round_blocks"] = True`` fills ``data["R"]`` (n, d, d) from Handle.round_blocks at the evaluated point before the
+    handle closes (problems.round_rotations where the device reports degenerate blocks: ``data["round_fallback"]``).
     ``line_search = 1``, ``device_factor``, ``round``, ``comm`` and ``precon`` raise ValueError before the library is loaded."""
     with _host_threads():
         return _onlyunitblockdiag_impl(C, d, options, verbose, rng)
@@ -641,6 +708,7 @@ def _onlyunitblockdiag_impl(C, d, options, verbose, rng):
                          "matrix are zero (block-Jacobi preconditioning is ManiSDP_posegraph's)")
     if o.get("device_factor"):
         raise ValueError("options['device_factor'] is not available for the unit-block-diagonal problem: the rank cut stays on the host")
+    device = _block_factor_option(o, "unit-block-diagonal") == "device"
     if C.shape[0] != C.shape[1] or C.shape[0] % d:
         raise ValueError(f"the cost matrix must be square of an order that is a multiple of d = {d}, not {C.shape}")
     dense_max = int(o.get("dense_eig_max", 3000))
@@ -673,25 +741,40 @@ def _onlyunitblockdiag_impl(C, d, options, verbose, rng):
     for name, value in (o.get("device_options") or {}).items():
         h.set_option(name, int(value))
     topts = _rtr_opts(o)
-    data = {"status": 0, "hessvecs": 0, "cost_evals": 0, "rejected": 0, "rtr_seconds": 0.0, "eig_seconds": 0.0, "log": []}
+    data = {"status": 0, "hessvecs": 0, "cost_evals": 0, "rejected": 0, "rtr_seconds": 0.0, "eig_seconds": 0.0, "log": [],
+            "factor_device_calls": 0, "factor_host_fallbacks": 0, "factor_seconds": 0.0}
     t0 = time.time()
     dinf0 = None
     obj = dinf = gradnorm = z = Lam = r = None
     certified = True
     Y_eval = Y
+    # options["block_factor"] = "device": the factor stays resident between the trustregions() calls (msdp_blockfactor_gram /
+    # _rotate / _append) and comes to the host once, when the loop ends -- the device_factor branch of _onlyunitdiag_impl
+    resident = False
+    last_it = int(o["AL_maxiter"])
     try:
-        for it in range(1, int(o["AL_maxiter"]) + 1):
-            h.set_point(Y)
+        for it in range(1, last_it + 1):
+            if not resident:
+                tf = time.time()
+                h.set_point(Y)
+                if it > 1:                                 # part of a re-shape on the host
+                    data["factor_seconds"] += time.time() - tf
             st = h.rtr(topts)
             data["rtr_seconds"] += st.seconds
             data["hessvecs"] += st.hessvecs
             data["cost_evals"] += st.cost_evals
             data["rejected"] += st.rejected
             gradnorm = st.gradnorm
-            Y = h.get_point()
-            Y_eval = Y
-            Lam = h.get_blockmult()                        # Lambda_i = sym((C Y)_i Y_i')
-            z = np.ascontiguousarray(np.diagonal(Lam, axis1=1, axis2=2)).ravel()
+            if not device:
+                tf = time.time()
+                Y = h.get_point()
+                data["factor_seconds"] += time.time() - tf
+                Y_eval = Y
+            if not device or eig_mode == "host":
+                Lam = h.get_blockmult()                    # Lambda_i = sym((C Y)_i Y_i')
+                z = np.ascontiguousarray(np.diagonal(Lam, axis1=1, axis2=2)).ravel()
+            else:
+                z = h.get_z()                              # the diagonals alone; the blocks once, at the end
             obj = float(np.sum(z))
             t1 = time.time()
             certified = True
@@ -714,7 +797,12 @@ def _onlyunitblockdiag_impl(C, d, options, verbose, rng):
                     vS = np.hstack([v_v, vS[:, :max(delta - 1, 0)]])
                     nneg = max(nneg, 1)
                 dinf = dinf_v
-            Q, e, r = _thin_svd_rank(Y, float(o["theta"]))
+            tf = time.time()
+            if device:
+                Q, e, r = _thin_svd_rank(None, float(o["theta"]), gram=h.blockfactor_gram())
+            else:
+                Q, e, r = _thin_svd_rank(Y, float(o["theta"]))
+            data["factor_seconds"] += time.time() - tf
             _say(verbose, "Iter %d, obj:%0.8f, dinf:%0.1e, r:%d, p:%d, time:%0.2fs" % (it, obj, dinf, r, p, time.time() - t0))
             data["log"].append((it, obj, dinf, r, p, time.time() - t0, st.hessvecs))
             data["iters"] = it
@@ -727,7 +815,15 @@ def _onlyunitblockdiag_impl(C, d, options, verbose, rng):
                     _say(verbose, "Slow progress!")
                     break
                 dinf0 = dinf
+            if device and it == last_it:                   # last pass: the evaluated point stays resident, nothing to re-shape for
+                break
             nne = max(min(nneg, delta), 1)
+            tf = time.time()
+            if device:
+                Y, p = _block_reshape_device(h, d, _polar_blocks, Q, e, r, p, vS, nne, float(o["alpha"]), data)
+                resident = Y is None
+                data["factor_seconds"] += time.time() - tf
+                continue
             if d <= r <= p - 1:                            # never below the block order: d orthonormal rows need d columns
                 Y = _polar_blocks(_rank_cut(Y, Q, e, r), d)
                 p = r
@@ -735,6 +831,11 @@ def _onlyunitblockdiag_impl(C, d, options, verbose, rng):
                 raise RuntimeError(f"the factor width would exceed the device's 256 columns (p = {p}, {nne} more)")
             Y = _polar_blocks(np.hstack([Y, o["alpha"] * vS[:, :nne]]), d)
             p = p + nne
+            data["factor_seconds"] += time.time() - tf
+        if device and obj is not None:
+            Y_eval, Lam = h.get_point(), h.get_blockmult()
+        if o.get("round_blocks") and obj is not None:
+            _round_blocks_option(h, d, Y_eval, data)
     finally:
         h.close()
     Y = Y_eval
@@ -795,6 +896,9 @@ def ManiSDP_posegraph(C, d, options=None, verbose=True, rng=None):
     blocks (msdp_set_option "precon": the preconditioned branch of tCG.m, the trust region in the M-norm); default None, the
     identity.  With it the handle runs the generic trips also under ``block_persist``.  Any other value raises ValueError
     before the library is loaded; a block the library cannot invert surfaces as its own MsdpError.
+    ``options["block_factor"]`` and ``options["round_blocks"]`` as for ManiSDP_onlyunitblockdiag (the polar factors are those
+    of the rotation rows; a rerun leaves the resident factor where it is; ``data["R"]`` and ``data["t"]``, from
+    problems.round_poses on a fallback).
     ``line_search = 1``, ``device_factor``, ``round`` and ``comm`` raise ValueError before the library is loaded."""
     with _host_threads():
         return _posegraph_impl(C, d, options, verbose, rng)
@@ -817,6 +921,7 @@ def _posegraph_impl(C, d, options, verbose, rng):
         raise ValueError(f"options['precon'] must be None or 'blockjacobi' for the pose-graph problem, not {o.get('precon')!r}")
     if o.get("device_factor"):
         raise ValueError("options['device_factor'] is not available for the pose-graph problem: the rank cut stays on the host")
+    device = _block_factor_option(o, "pose-graph") == "device"
     if C.shape[0] != C.shape[1] or C.shape[0] % B:
         raise ValueError(f"the cost matrix must be square of an order that is a multiple of d + 1 = {B}, not {C.shape}")
     dense_max = int(o.get("dense_eig_max", 3000))
@@ -856,24 +961,36 @@ def _posegraph_impl(C, d, options, verbose, rng):
         raise
     topts = _rtr_opts(o)
     data = {"status": 0, "hessvecs": 0, "cost_evals": 0, "rejected": 0, "rtr_seconds": 0.0, "eig_seconds": 0.0, "log": [],
-            "reruns": 0}
+            "reruns": 0, "factor_device_calls": 0, "factor_host_fallbacks": 0, "factor_seconds": 0.0}
     t0 = time.time()
     dinf0 = None
     obj = dual = gap = dinf = gradnorm = z = Lam = r = None
     certified = True
     Y_eval = Y
+    # options["block_factor"] = "device": as in _onlyunitblockdiag_impl -- one set_point per solve, the factor comes down when the
+    # loop ends; a rerun (below) does not touch it
+    resident = False
+    last_it = int(o["AL_maxiter"])
     try:
-        for it in range(1, int(o["AL_maxiter"]) + 1):
-            h.set_point(Y)
+        for it in range(1, last_it + 1):
+            if not resident:
+                tf = time.time()
+                h.set_point(Y)
+                if it > 1:                                 # part of a re-shape on the host (a rerun uploads the same point again)
+                    data["factor_seconds"] += time.time() - tf
             st = h.rtr(topts)
             data["rtr_seconds"] += st.seconds
             data["hessvecs"] += st.hessvecs
             data["cost_evals"] += st.cost_evals
             data["rejected"] += st.rejected
             gradnorm = st.gradnorm
-            Y = h.get_point()
-            Y_eval = Y
-            Lam = h.get_blockmult()                        # Lambda_i = sym(G_i Y_i'), d x d
+            if not device:
+                tf = time.time()
+                Y = h.get_point()
+                data["factor_seconds"] += time.time() - tf
+                Y_eval = Y
+            if not device or eig_mode == "host":
+                Lam = h.get_blockmult()                    # Lambda_i = sym(G_i Y_i'), d x d
             z = h.get_z()                                  # its diagonals, 0 in the free-row entries
             dual = float(np.sum(z))
             obj = 2.0 * h.cost()                           # <C, Y Y'> = dual + sum <g_i, tau_i>
@@ -899,7 +1016,12 @@ def _posegraph_impl(C, d, options, verbose, rng):
                     vS = np.hstack([v_v, vS[:, :max(delta - 1, 0)]])
                     nneg = max(nneg, 1)
                 dinf = dinf_v
-            Q, e, r = _thin_svd_rank(Y, float(o["theta"]))
+            tf = time.time()
+            if device:
+                Q, e, r = _thin_svd_rank(None, float(o["theta"]), gram=h.blockfactor_gram())
+            else:
+                Q, e, r = _thin_svd_rank(Y, float(o["theta"]))
+            data["factor_seconds"] += time.time() - tf
             _say(verbose, "Iter %d, obj:%0.8f, dinf:%0.1e, gap:%0.1e, r:%d, p:%d, time:%0.2fs" % (it, obj, dinf, gap, r, p, time.time() - t0))
             data["log"].append((it, obj, dinf, gap, r, p, time.time() - t0, st.hessvecs))
             data["iters"] = it
@@ -912,10 +1034,19 @@ def _posegraph_impl(C, d, options, verbose, rng):
                     _say(verbose, "Slow progress!")
                     break
                 dinf0 = max(dinf, gap)
+            if device and it == last_it:                   # last pass: the evaluated point stays resident, nothing to re-shape for
+                break
             if dinf < o["tol"] <= gap:                     # S is PSD but the point is not stationary: trustregions() again
                 data["reruns"] += 1
+                resident = device                          # (the device path: on the factor where it is)
                 continue
             nne = max(min(nneg, delta), 1)
+            tf = time.time()
+            if device:
+                Y, p = _block_reshape_device(h, d, _polar_rotation_rows, Q, e, r, p, vS, nne, float(o["alpha"]), data)
+                resident = Y is None
+                data["factor_seconds"] += time.time() - tf
+                continue
             if d <= r <= p - 1:                            # never below d: d orthonormal rows need d columns
                 Y = _polar_rotation_rows(_rank_cut(Y, Q, e, r), d)
                 p = r
@@ -923,6 +1054,11 @@ def _posegraph_impl(C, d, options, verbose, rng):
                 raise RuntimeError(f"the factor width would exceed the device's 256 columns (p = {p}, {nne} more)")
             Y = _polar_rotation_rows(np.hstack([Y, o["alpha"] * vS[:, :nne]]), d)
             p = p + nne
+            data["factor_seconds"] += time.time() - tf
+        if device and obj is not None:
+            Y_eval, Lam = h.get_point(), h.get_blockmult()
+        if o.get("round_blocks") and obj is not None:
+            _round_blocks_option(h, d, Y_eval, data)
     finally:
         h.close()
     Y = Y_eval

@@ -634,6 +634,10 @@ int msdp_block_reshape(msdp_handle h, int32_t nb, const int64_t* row0, const int
  *   "pipe_refresh" k   one-reduction trip: every k-th trip also publishes tangent(r) and mdelta, and the next one forms both
  *                       products from direct gathers (default 16: |Heta - Hess(eta)|/|Heta| <= 1.2e-11 after 100 trips on G81;
  *                       32: 6e-11, 8: 2.5e-12; the recurrences lose accuracy with the SQUARE of k)
+ *   "pipe_own"     1/0  fused one-reduction launch at 17 <= p <= 32, rows of <= 5 entries: a row's entry in its own column (the
+ *                       diagonal, or a padding slot of a row without one) is taken from the lane's registers, a trip gathers 12 rows
+ *                       instead of 15.  Only where every row holds such an entry (msdp_debug_fused_own); bit-identical results
+ *                       (default 1; 0 = every column through the exchange buffer, for A/B timing and tests)
  *   "affine_overlap" 1/0  affine kinds: the 2*eS*U contraction of a Hess-vec runs on a second stream beside the A(.) / A'(.)
  *                       chain (default 0: measured slower than one stream; kept for A/B timing; results agree to rounding)
  *   "trip2"        0/1/2  chunked path, sparse C / oblique manifold / one rank: two launches per tCG trip (12 vector passes,
@@ -720,6 +724,10 @@ int msdp_debug_block_persist_plan(msdp_handle h, int32_t* out);
  * two-launch trip (option "trip2"), 3 = three launches per trip (every other kind and storage, the option "precon" included);
  * 0 = the tCG is persistent (msdp_tcg_path reports 1 or 2).  Read-only: no launch, the handle is not modified. */
 int msdp_debug_trip_form(msdp_handle h, int32_t* form);
+/* (test / diagnostic) 1 = the next fused launch (option "fused_rtr") at the resident point takes the own-column instance of the
+ * one-reduction trip (option "pipe_own"; every row of C holds an entry in its own column or has fewer than 5 entries); 0 = any other
+ * instance, or no fused launch.  Read-only: no launch. */
+int msdp_debug_fused_own(msdp_handle h, int32_t* own);
 /* (test / diagnostic) What the set-up of a primal affine handle (MSDP_KIND_UNITDIAG, _UNITTRACE, _GENERIC) planned from the constraint
  * data, and which branch the last calls took.  Host only: no launch, the handle is not modified.  out[0..15]:
  *    0 usym      1 = c and every A_k are symmetric entry by entry (upper view, tiled adjoint, B route possible)

@@ -149,6 +149,7 @@ SIGNATURES = {
     "msdp_debug_block_persist_plan": (C.c_int, [C.c_void_p, _P(C.c_int32)]),
     "msdp_debug_affine_plan": (C.c_int, [C.c_void_p, _P(C.c_int32)]),
     "msdp_debug_trip_form": (C.c_int, [C.c_void_p, _P(C.c_int32)]),
+    "msdp_debug_fused_own": (C.c_int, [C.c_void_p, _P(C.c_int32)]),
     "msdp_point_snapshot": (C.c_int, [C.c_void_p]),
     "msdp_point_restore": (C.c_int, [C.c_void_p]),
     "msdp_al_primal": (C.c_int, [C.c_void_p, _dp, _dp]),
@@ -987,6 +988,12 @@ class Handle:
         _check(self._lib.msdp_debug_persist_form(self._h, C.byref(v)))
         if v.value < 0:                                    # the block kinds' kernel (option "block_persist") is a unit of its own
             _check(self._lib.msdp_debug_block_persist_form(self._h, C.byref(v)))
+        return v.value
+
+    def fused_own(self):
+        """1 where the next fused launch takes the own-column instance of the one-reduction trip (msdp_debug_fused_own), else 0."""
+        v = C.c_int32()
+        _check(self._lib.msdp_debug_fused_own(self._h, C.byref(v)))
         return v.value
 
     def trip_form(self):

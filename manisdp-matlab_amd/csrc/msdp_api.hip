@@ -218,6 +218,7 @@ int msdp_upload_sparse_rows(msdp_handle h) {
     int W = 0;
     for (int i = 0; i < d.n_loc; ++i) W = std::max(W, rp[i + 1] - rp[i]);
     d.ellW = 0; d.ellc = nullptr; d.ellv = nullptr;
+    h->ell_own_col = false;
     if (W >= 1 && W <= 8) {
         // stored width 5 or 8 (the persistent tCG kernel is instantiated for these and loads every slice
         // without a branch); the padding entries are (own row, 0.0)
@@ -240,6 +241,15 @@ int msdp_upload_sparse_rows(msdp_handle h) {
         HIPCHK(msdp_memcpy(h->d_ellc, ec.data(), ec.size() * sizeof(int), hipMemcpyHostToDevice));
         HIPCHK(msdp_memcpy(h->d_ellv, ev.data(), ev.size() * sizeof(double), hipMemcpyHostToDevice));
         d.ellW = W; d.ell_stride = (int64_t)cap; d.ellc = h->d_ellc; d.ellv = h->d_ellv;
+        // every stored row references itself -- through its diagonal entry or, with fewer than W entries, through a padding slot: what
+        // the own-column form of the fused tCG needs (msdp_pipe.h, OWNC)
+        bool own = true;
+        for (int i = 0; i < d.n_loc && own; ++i) {
+            bool has = rp[i + 1] - rp[i] < W;
+            for (int t = rp[i]; t < rp[i + 1] && !has; ++t) has = h->h_colind[base + t] == i + d.row0;
+            own = has;
+        }
+        h->ell_own_col = own;
     }
     return 0;
 }
@@ -1011,6 +1021,7 @@ extern "C" int msdp_set_option(msdp_handle h, const char* name, int32_t value) {
     else if (!strcmp(name, "persist_pipe")) t.persist_pipe = value > 0 ? 1 : 0;
     else if (!strcmp(name, "pipe_refresh")) t.pipe_refresh = value > 0 ? (value < 2 ? 2 : value) : 0;   // (1 would store the refresh rows of trip j + 1 into the regions a slower workgroup still gathers those of trip j from: msdp_pipe.h)
     else if (!strcmp(name, "pipe_local")) t.pipe_local = value > 0 ? 1 : 0;
+    else if (!strcmp(name, "pipe_own")) t.pipe_own = value > 0 ? 1 : 0;
     else if (!strcmp(name, "persist_goff")) t.persist_goff = value ? 1 : 0;
     else if (!strcmp(name, "persist_ep")) { t.persist_ep = value ? 1 : 0; h->d.persist_ep = t.persist_ep; h->persist_sig_fn = nullptr; }
     else if (!strcmp(name, "persist_slots")) { t.persist_slots = (value == 3 || value == 4) ? value : 0; h->d.persist_slots = t.persist_slots; }

@@ -250,6 +250,7 @@ struct Tuning {
     int persist_ep = 1;        // CSR rows of the persistent tCG: entry-parallel lanes where the rows leave lanes free (A/B: 0 never)
     int persist_goff = 1;      // persistent tCG: the byte offsets of the R x EW gathers of a trip live in registers (0: recomputed per trip from the LDS copy of the column indices)
     int pipe_local = 1;        // one-reduction trip: neighbours that belong to the same workgroup are read from LDS, the diagonal from registers
+    int pipe_own = 1;          // fused one-reduction trip at 16 lanes per row: a row's entry in its own column from registers, 12 gathers a trip (0: all 15; A/B, tests)
     int xr_twolevel = 0;       // process ranks: 1 = two-level grid reductions (msdp_psync.h psync2) also where the flat ones would do (one device, <= 4 members); A/B, tests
     int pipe_refresh = 16;     // one-reduction trip: trips between two direct exchanges (its recurrences drift with the square of this)
     int persist_pipe = 1;      // persistent tCG: ONE grid reduction per trip (msdp_pipe.h) where an instance exists (rows of <= 8 entries, p <= 32)
@@ -382,6 +383,7 @@ struct msdp_handle_s {
     int persist_sig_lpr = 0, persist_sig_ew = 0, persist_sig_r = 0, persist_sig_G = 0, persist_sig_ok = 0;
     const void* persist_sig_fn = nullptr; const void* fused_sig_fn = nullptr;     // the kernel instance the cached answers are for
     int fused_sig_lpr = 0, fused_sig_ew = 0, fused_sig_G = 0, fused_sig_ok = 0;
+    bool ell_own_col = false;         // ELL copy: every local row has an entry in its own column or a padding slot (msdp_upload_sparse_rows)
     // persistent tCG kernel of the block kinds (msdp_blockpersist.hip): cached eligibility, the slot region of the next launch
     const void* blkpersist_sig_fn = nullptr; int blkpersist_sig_G = 0, blkpersist_sig_ok = 0; size_t blkpersist_sig_lds = 0;
     int blkpersist_region = 0;

@@ -1060,6 +1060,17 @@ int msdp_persist_trace_dims(msdp_handle h, int* G, int* nj, int* j0) { *G = pers
 
 int msdp_tr_tail_grid(msdp_handle h) { return persist_grid(h->d); }
 
+// The own-column form of the fused one-reduction launch at 16 lanes per row (msdp_pipe.h, OWNC): only where every local row holds an
+// entry in its own column or a padding slot (msdp_upload_sparse_rows) and the option "pipe_own" is on; else the five-gather instance
+static bool fused_takes_own(msdp_handle h, const PersistPlan& pl) {
+    return h->tune.pipe_own && h->ell_own_col && pl.ep <= 1 && pl.lpr == 16 && pl.ew == 5 && pl.r == 3 && persist_is_pipe(h, pl, true);
+}
+static persist_fn fused_kernel(msdp_handle h, const PersistPlan& pl) {
+    persist_fn fn = persist_kernel(pl, true, persist_mode(h));
+    if (fn && fused_takes_own(h, pl)) fn = k_tcg_pipe_obl<16, 5, 3, false, true, 0, 1, true>;
+    return fn;
+}
+
 // LDS of the fused form: + the proposal point, its gradient (R x PB double2 each) and eG
 static size_t fused_lds(const PersistPlan& pl) {
     const size_t rows = (size_t)pl.r * plan_rstep(pl);
@@ -1082,7 +1093,7 @@ int msdp_persist_fused_ok(msdp_handle h) {
     // where the one-reduction trip exists for per-iteration launches only, those beat the fused two-reduction launch (G81 p = 32:
     // 164 000 against 143 000 Hess-vec/s)
     if (persist_is_pipe(h, pl, false) && !persist_is_pipe(h, pl, true)) return 0;
-    persist_fn fn = persist_kernel(pl, true, persist_mode(h));
+    persist_fn fn = fused_kernel(h, pl);
     if (!fn) return 0;
     {   // (the one-reduction form: + ls and HQs)
         const bool pipe = persist_is_pipe(h, pl, true), early = persist_is_early(h, pl, true);
@@ -1103,10 +1114,11 @@ int msdp_launch_rtr_fused(msdp_handle h) {
     const int G = persist_grid(h->d);
     PersistPlan pl;
     if (!persist_plan(h->d, G, pl)) { msdp_set_error("fused RTR: not eligible"); return MSDP_ESTATE; }
-    persist_fn fn = persist_kernel(pl, true, persist_mode(h));
+    persist_fn fn = fused_kernel(h, pl);
     if (!fn) { msdp_set_error("fused RTR: no kernel instance"); return MSDP_ESTATE; }
-    if (h->tune.timing) fprintf(stderr, "[msdp_rtr] fused launch: <%d, %d, %d>, %s, G = %d\n", pl.lpr, pl.ew, pl.r,
-                                persist_is_pipe(h, pl, true) ? "one reduction per trip" : "two reductions per trip", G);
+    if (h->tune.timing) fprintf(stderr, "[msdp_rtr] fused launch: <%d, %d, %d>, %s%s, G = %d\n", pl.lpr, pl.ew, pl.r,
+                                persist_is_pipe(h, pl, true) ? "one reduction per trip" : "two reductions per trip",
+                                fused_takes_own(h, pl) ? ", own column from registers" : "", G);
     {   // (the one-reduction form: + ls and HQs)
         const bool pipe = persist_is_pipe(h, pl, true), early = persist_is_early(h, pl, true);
         const size_t rows = (size_t)pl.r * plan_rstep(pl);
@@ -1117,7 +1129,7 @@ int msdp_launch_rtr_fused(msdp_handle h) {
     if (dp.trace) {
         // (msdp_debug_persist_trace with reps <= 0: the phases of the TR iterations around the tCGs, FSTAMP in msdp_pipe.h)
         if (!(pl.lpr == 16 && pl.ew == 5 && pl.r == 3 && persist_is_pipe(h, pl, true))) { msdp_set_error("fused trace: only the one-reduction <16, 5, 3> instance (17 <= p <= 32, rows of <= 5 entries) is traced"); return MSDP_EUNSUPPORTED; }
-        fn = k_tcg_pipe_obl<16, 5, 3, true, true>;
+        fn = fused_takes_own(h, pl) ? k_tcg_pipe_obl<16, 5, 3, true, true, 0, 1, true> : k_tcg_pipe_obl<16, 5, 3, true, true>;
         HIPCHK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
     }
     hipLaunchKernelGGL(k_psync_reset, dim3(8), dim3(256), 0, h->stream, h->psync_slots, h->psync_err);
@@ -1126,7 +1138,16 @@ int msdp_launch_rtr_fused(msdp_handle h) {
     HIPCHK(hipGetLastError());
     return 0;
 }
-
+// 1: the next fused launch of this handle takes the own-column instance; 0: any other instance, or no fused launch at all
+extern "C" int msdp_debug_fused_own(msdp_handle h, int32_t* own) {
+    if (!h || !own) return MSDP_EINVAL;
+    *own = 0;
+    if (!msdp_persist_fused_ok(h)) return 0;
+    PersistPlan pl;
+    if (!persist_plan(h->d, persist_grid(h->d), pl)) return 0;
+    *own = fused_takes_own(h, pl) ? 1 : 0;
+    return 0;
+}
 
 // ------------------------------------------------------------------ cross-rank persistent tCG (XR)
 // N in-process ranks (msdp_comm_init_local) run the persistent tCG TOGETHER: N x G workgroups, G = (256 / N) rounded down to a

@@ -394,6 +394,10 @@ __device__ __forceinline__ bool psync2_8(unsigned long long* blk, unsigned long 
 #ifndef MSDP_PIPE_LINES
 #define MSDP_PIPE_LINES 1
 #endif
+// where the twelve requests of the own-column instance sit (tcg_pipe_body, SPREAD)
+#ifndef MSDP_OWN_SPREAD
+#define MSDP_OWN_SPREAD 0x369c
+#endif
 #if MSDP_PIPE_LINES
 #define PSYNC8(slots, gen, G, v, sh8, shb8, err, bid, backoff, tr, f) psync8_lines(slots, gen, G, v, sh8, shp, shb8, err, bid, backoff, tr, f)
 #else
@@ -409,12 +413,21 @@ __device__ __forceinline__ bool psync2_8(unsigned long long* blk, unsigned long 
 // EW = 0, EP > 1 (round 6): CSR rows with entry-parallel lanes -- the 64 / LPR lane groups of a wave share ONE row (group epi = 0 owns it:
 // registers, sums, stores) and split its entries (msdp_persist.hip, option persist_ep); no ELL copy, no local columns, no gather requested
 // inside the reduction: a trip's products come from ONE batch of gathers per lane for rows of up to 8 x EP entries.
-template <int LPR, int EW, int R, bool TRACE, bool FUSE, int XRM = 0, int EP = 1>
+// OWNC (round 11, the fused launch at 16 lanes per row only): "column 0 is the own row".  The handle's rows all hold an entry in their own
+// column or a padding slot (own row, 0.0) -- msdp_upload_sparse_rows decides, the host picks the instance -- and set-up sorts that entry to
+// ELL column 0 whatever its value.  The lane holds the bits a gather of that column would return: H md of its row in hmd[r] (live until the
+// next trip's H md loop), the gradient row in md[r] at the first trip of a tCG, the proposal row in YPs in the TR tail.  A trip then
+// requests R x 4 = 12 rows, not 15 (X[3][4]); the fold order is the one of the five-column form (column 0 first), and for a row without a
+// diagonal the exact zero of the padding term moves from the last place of the fold to the first: the same bits.  The refresh trip's two
+// direct gathers keep all five columns (tangent(r) and md of the trip before are no longer in registers): two passes, 4 + 1.
+template <int LPR, int EW, int R, bool TRACE, bool FUSE, int XRM = 0, int EP = 1, bool OWNC = false>
 __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* slots, int* err, const int bx) {
     constexpr bool XR = XRM != 0, XTWO = XRM == 2;
     constexpr bool CSR = EW == 0;
     static_assert(!XR || (!FUSE && !TRACE), "cross-rank instances: per-iteration launches");
     static_assert(R <= 5, "pipelined trip: every vector in registers");
+    static_assert(!OWNC || (FUSE && LPR == 16 && EW == 5 && R == 3 && XRM == 0), "own-column form: the fused launch at 16 lanes per row");
+    constexpr int NO = OWNC ? 1 : 0;                               // leading ELL columns that are the lane's own row (never gathered in a trip)
     static_assert(CSR ? (EP == 64 / LPR && !XR && !TRACE) : EP == 1, "CSR rows: one row per wave, one rank");
     static_assert(PSYNC_NV == 8 && PSYNC_REP * PSYNC_NV == 64, "psync8 posts one slot per lane of wave 0");
     // What each instance takes of the launch-invariant address and mask work.  Decided by the register allocation: an instance takes a
@@ -576,10 +589,16 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
         // the entries of the row ordered own row, rows of this workgroup, other rows, empty slots: a column of the ELL block then
         // holds ONE kind for (nearly) all rows of a wave, and the wave picks the source per column, not per lane
         int kw[EW > 0 ? EW : 1];
+        bool own_seen = false;
 #pragma unroll
         for (int w = 0; w < EW; ++w) {
             if (!rok) vw[w] = 0.0;                                 // INVARIANT: a row slot past `hi` has no entries -- its products are exact zeros
-            kw[w] = vw[w] == 0.0 ? 3 : (cw[w] == rc ? 0 : ((cw[w] >= lo && cw[w] < hi) ? 1 : 2));
+            // OWNC: the FIRST entry in the row's own column is kind 0 whatever its value -- the diagonal, or the first padding slot
+            // (own row, 0.0) of a row without one -- so that column 0 of the sorted row is the own row (cs[] keeps its offset: the
+            // refresh trip's direct gathers still use it)
+            const bool own = OWNC && !own_seen && cw[w] == rc;
+            own_seen = own_seen || own;
+            kw[w] = own ? 0 : (vw[w] == 0.0 ? 3 : (cw[w] == rc ? 0 : ((cw[w] >= lo && cw[w] < hi) ? 1 : 2)));
         }
 #pragma unroll
         for (int a = 0; a < (LOC ? EW - 1 : 0); ++a)
@@ -772,7 +791,8 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
 #define PTSTAMP(ph) do { if (!FUSE) { TSTAMP(ph); } else if (FTRIP_ON && threadIdx.x == 0) FTRIP_PTR[ph] = __builtin_readcyclecounter(); } while (0)
   auto trips = [&](auto nlc) {
     constexpr int NL = decltype(nlc)::value;                       // columns [0, NL) from LDS, [NL, EW) through the buffer
-    constexpr int NG = EW - NL;
+    constexpr int NG = EW - NL - NO;                               // (OWNC: column NL is the own row, from registers)
+    constexpr int NC0 = NL + NO;                                   // the first column that goes through the buffer in a trip
     // the next trip's rows requested inside the reduction, in ONE batch: where they are few enough to stay in flight across the trip's
     // arithmetic (the fused launch: 9 rows)
     constexpr bool PREF = !CSR && R * NG <= (FUSE ? 9 : 15);
@@ -784,7 +804,14 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
     // time with 15 to 70 VALU instructions between the batches 214 900 (medians of six alternating runs; the runs themselves are in
     // profiles/r10_trip_instruction_counts.md).  One or two requests per place (a branch and an LDS read of the offset each) lose to
     // batches of three.  Every batch is skipped in front of a refresh trip.
+    // OWNC: twelve requests do not fill five places of three.  The places: 0 on_ready, 1 behind the boundary test, 2 behind the model
+    // test, 3 in front of the new direction, 4 behind it; place q takes the requests SPq .. SP(q+1) - 1, SP0 = 0, SP5 = 12, and
+    // MSDP_OWN_SPREAD holds SP1 .. SP4 as four hexadecimal digits: 0x369c = 3/3/3/3 without the last place, 0x0369 = 3/3/3/3 without
+    // on_ready, 0x368a = 3/3/2/2/2 (the runs are in profiles/r11_trip_instruction_counts.md)
     constexpr bool SPREAD = PARK;
+    constexpr int SP1 = !OWNC ? 3 : ((MSDP_OWN_SPREAD >> 12) & 15), SP2 = !OWNC ? 6 : ((MSDP_OWN_SPREAD >> 8) & 15);
+    constexpr int SP3 = !OWNC ? 9 : ((MSDP_OWN_SPREAD >> 4) & 15), SP4 = !OWNC ? 12 : (MSDP_OWN_SPREAD & 15), SP5 = R * NG;
+    static_assert(!OWNC || (SP1 <= SP2 && SP2 <= SP3 && SP3 <= SP4 && SP4 <= SP5), "the places take the requests in order");
     // SPLIT: the four sums without H md under the gather, the other four behind the row stores: the instances whose gather is not
     // requested in one batch inside the reduction
     constexpr bool SPLIT = !PREF;
@@ -792,7 +819,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
     // requests ka .. kb - 1 of the R x NG of a trip, row slot by row slot, from region `base` of the exchange buffer
 #define PIPE_ISSUE_PART(base, ka, kb) do { \
             _Pragma("unroll") for (int k = (ka); k < (kb); ++k) { \
-                const unsigned coff = (unsigned)cs[(NL + k % NGD) * ROWS + SLOT(k / NGD)]; \
+                const unsigned coff = (unsigned)cs[(NC0 + k % NGD) * ROWS + SLOT(k / NGD)]; \
                 X[k / NGD][k % NGD] = ld2_cp<XTWO ? 17 : MSDP_CPOL_SC1>(rs_md, (base) + (BOFF ? coff + gcol8 : (coff * gld + gcol) * 8u)); } } while (0)
 #define PIPE_SPREAD(ka, kb) do { if (SPREAD && !pub) PIPE_ISSUE_PART(xq * half_bytes, ka, kb); } while (0)
     double2 X[R][NG > 0 ? NG : 1];                                 // the gathered rows (in flight across the end of a trip)
@@ -825,6 +852,15 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
                 PIPE_ISSUE(rs, base, w0); \
                 _Pragma("unroll") for (int r = 0; r < R; ++r) PIPE_FOLDX(r, (dst)[r], w0); } \
             if (!colok) { _Pragma("unroll") for (int r = 0; r < R; ++r) (dst)[r] = zz; } } while (0)
+        // OWNC: column 0 from the lane's own copy of the row (`own`: the bits a gather of that column would return), columns 1 .. EW - 1
+        // through the buffer; the fold order of PIPE_GATHER_ALL
+#define PIPE_GATHER_OWN(rs, base, own, dst) do { \
+            PIPE_ISSUE(rs, base, NO); \
+            _Pragma("unroll") for (int r = 0; r < R; ++r) { \
+                const double v0 = vs[SLOT(r)]; \
+                (dst)[r] = make_double2(fma(v0, (own)[r].x, 0.0), fma(v0, (own)[r].y, 0.0)); \
+                PIPE_FOLDX(r, (dst)[r], NO); } \
+            if (!colok) { _Pragma("unroll") for (int r = 0; r < R; ++r) (dst)[r] = zz; } } while (0)
         // the eight partial sums of this trip's reduction.  Round 6, the instances that do NOT have the next gather requested in one
         // batch inside the reduction (!PREF: the fused launch at 16 lanes per row, whose requests are spread from the reduction to the
         // loop's back edge since round 10 -- the last rows are still on their way at the top of the trip): four sums -- <md, g>, <md, Heta>, <r, r>, the model value -- do not
@@ -849,7 +885,8 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
             // the first direction = the gradient (tangent): r = md = grad.  Its rows: in global memory since an earlier launch, in the
             // exchange buffer since the TR tail that proposed this point
             pre_sums();
-            PIPE_GATHER_ALL(rs_g, g_base, cmd);
+            if (OWNC) PIPE_GATHER_OWN(rs_g, g_base, md, cmd);      // (md = the gradient row: the bits in d.Gr / region 5 or 6)
+            else PIPE_GATHER_ALL(rs_g, g_base, cmd);
 #pragma unroll
             for (int r = 0; r < R; ++r) ctr[r] = cmd[r];
         } else {
@@ -859,7 +896,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
                 PIPE_GATHER_ALL(rs_md, 2u * half_bytes, cmd);
             }
             // the neighbours' rows of last trip's Hmd: requested inside that trip's reduction already (have_x), except behind a refresh
-            if (!CSR && !have_x) PIPE_ISSUE(rs_md, (xq ^ 1u) * half_bytes, NL);
+            if (!CSR && !have_x) PIPE_ISSUE(rs_md, (xq ^ 1u) * half_bytes, NC0);
             pre_sums();
             // PARK: the two recurrences come back from LDS while the gathers are in flight (a refresh trip has just formed both afresh)
             if (PARK && !direct) {
@@ -874,7 +911,14 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
                 for (int r = 0; r < R; ++r) {
                     double2 a = zz;
                     if (CSR) a = csr_gather(r, rs_md, (xq ^ 1u) * half_bytes);
-                    else { PIPE_FOLDL(r, a, HQs + (xq ^ 1u) * R * PB); PIPE_FOLDX(r, a, NL); }
+                    else {
+                        PIPE_FOLDL(r, a, HQs + (xq ^ 1u) * R * PB);
+                        if (OWNC) {                                // the own row of last trip's H md: still in hmd[r], the bits that were stored
+                            const double v0 = vs[NL * ROWS + SLOT(r)];
+                            a.x = fma(v0, hmd[r].x, a.x); a.y = fma(v0, hmd[r].y, a.y);
+                        }
+                        PIPE_FOLDX(r, a, NC0);
+                    }
                     if (decltype(masked)::value && !colok) a = zz;
                     ctr[r].x = fma(-alpha, a.x, ctr[r].x); ctr[r].y = fma(-alpha, a.y, ctr[r].y);      // C tangent(r') = C tangent(r) - alpha C Hmd
                     cmd[r].x = fma(beta, cmd[r].x, ctr[r].x); cmd[r].y = fma(beta, cmd[r].y, ctr[r].y);  // C md' = C tangent(r') + beta C md
@@ -955,8 +999,8 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
         // (the next trip's gather goes out as soon as this wave has seen every workgroup's post: its latency runs under the rest of the
         // reduction and the arithmetic behind it.  Not behind a refresh trip: that one's two direct gathers come first.)
         auto next_gather = [&]() {
-            if (SPREAD) { PIPE_SPREAD(0, 3); }
-            else if (PREF && !pub) { PIPE_ISSUE(rs_md, xq * half_bytes, NL); have_x = true; }
+            if (SPREAD) { PIPE_SPREAD(0, SP1); }
+            else if (PREF && !pub) { PIPE_ISSUE(rs_md, xq * half_bytes, NC0); have_x = true; }
         };
         if (XTWO) {
             if (!psync2_8(d.xr2_blk, shpeer, d.xr2_n, d.xr2_me, xri, gen++, GS + d.xr2_skip, v, sh8, shb8, err, bid, backoff, next_gather)) { failed = true; break; }
@@ -982,13 +1026,13 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
             ++j;
             break;
         }
-        PIPE_SPREAD(3, 6);
+        PIPE_SPREAD(SP1, SP2);
         // the trial step's three inner products (tCG.m:215-241), expanded in alpha
         const double new_model = model_value - alpha * v[3] - 0.5 * alpha * (v[4] + v[5]) + 0.5 * alpha * alpha * d_Hd;   // :227
         const double r_r = fmax(z_r - 2.0 * alpha * v[1] + alpha * alpha * v[2], 0.0);                                    // :241
         e_Pe = e_Pe_new;
         if (!bench && new_model >= model_value) { stop = 6; ++j; break; }                 // :228 (eta, Heta stay)
-        PIPE_SPREAD(6, 9);
+        PIPE_SPREAD(SP2, SP3);
 #pragma unroll
         for (int r = 0; r < R; ++r) {                                                     // :233-238
             eta[r].x -= alpha * md[r].x; eta[r].y -= alpha * md[r].y;
@@ -1007,7 +1051,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
         e_Pd = beta * (e_Pd + alpha * d_Pd);                                              // :286
         d_Pd = r_r + beta * beta * d_Pd;                                                  // :287
         z_r = r_r;
-        PIPE_SPREAD(9, 12);
+        PIPE_SPREAD(SP3, SP4);
         // ---- mdelta = tangent(r + beta*mdelta)  (:273,283)
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -1016,7 +1060,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
             const double dot = msdp_group_sum_all<LPR>(vv.x * y.x + vv.y * y.y);
             md[r] = make_double2(vv.x - y.x * dot, vv.y - y.y * dot);
         }
-        PIPE_SPREAD(12, 15);
+        PIPE_SPREAD(SP4, SP5);
         if (SPREAD) have_x = !pub;                                        // (all R x NG are on their way)
         direct = pub;
         first = false;
@@ -1029,6 +1073,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
 #undef PIPE_FOLDX
 #undef PIPE_FOLDL
 #undef PIPE_GATHER_ALL
+#undef PIPE_GATHER_OWN
 #undef PTSTAMP
 #undef FTRIP_ON
 #undef FTRIP_PTR
@@ -1162,14 +1207,16 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
 #pragma unroll
         for (int r = 0; r < R; ++r) prop_finish(r, csr_gather(r, rs_md, yx_base));
     } else if (R * EW <= 16) {                                     // all gathers in flight (wider rows: a row slot at a time, registers)
+        // (OWNC: the proposal's own row is the value this lane stored into region 4, still in YPs -- R x 4 loads)
         double2 XG[R][EW > 0 ? EW : 1];
 #pragma unroll
         for (int r = 0; r < R; ++r)
 #pragma unroll
-            for (int w = 0; w < EW; ++w) XG[r][w] = ld2_sc1(rs_md, yx_base + (BOFF ? (unsigned)cs[w * ROWS + SLOT(r)] + gcol8 : ((unsigned)cs[w * ROWS + SLOT(r)] * gld + gcol) * 8u));
+            for (int w = NO; w < EW; ++w) XG[r][w] = ld2_sc1(rs_md, yx_base + (BOFF ? (unsigned)cs[w * ROWS + SLOT(r)] + gcol8 : ((unsigned)cs[w * ROWS + SLOT(r)] * gld + gcol) * 8u));
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             double2 acc = zz;
+            if (OWNC) XG[r][0] = YPs[r * PB + threadIdx.x];
 #pragma unroll
             for (int w = 0; w < EW; ++w) { const double vv = vs[w * ROWS + SLOT(r)]; acc.x = fma(vv, XG[r][w].x, acc.x); acc.y = fma(vv, XG[r][w].y, acc.y); }
             prop_finish(r, acc);
@@ -1260,7 +1307,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
 #undef ROWB
 }
 
-template <int LPR, int EW, int R, bool TRACE = false, bool FUSE = false, int XRM = 0, int EP = 1>
+template <int LPR, int EW, int R, bool TRACE = false, bool FUSE = false, int XRM = 0, int EP = 1, bool OWNC = false>
 __global__ __launch_bounds__(PB) void k_tcg_pipe_obl(Dev d, unsigned long long* slots, int* err) {
-    tcg_pipe_body<LPR, EW, R, TRACE, FUSE, XRM, EP>(d, slots, err, (int)blockIdx.x);
+    tcg_pipe_body<LPR, EW, R, TRACE, FUSE, XRM, EP, OWNC>(d, slots, err, (int)blockIdx.x);
 }

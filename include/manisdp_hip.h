@@ -638,6 +638,11 @@ int msdp_block_reshape(msdp_handle h, int32_t nb, const int64_t* row0, const int
  *                       diagonal, or a padding slot of a row without one) is taken from the lane's registers, a trip gathers 12 rows
  *                       instead of 15.  Only where every row holds such an entry (msdp_debug_fused_own); bit-identical results
  *                       (default 1; 0 = every column through the exchange buffer, for A/B timing and tests)
+ *   "pipe_wide"    1/0  fused own-column launch (see "pipe_own"): the wide plan -- the fewest workgroups, in multiples of 8, whose
+ *                       chunks hold at most 80 rows, so that the third row slot belongs to the waves 0..3 of a workgroup alone and the
+ *                       waves 4..7 run code that computes two row slots (msdp_debug_fused_plan).  Where that is another number of
+ *                       workgroups than with 0 the grid reduction sums in another order: results agree to rounding, not bit for bit
+ *                       (default 1; 0 = the grid and the instance of the per-iteration launches, for A/B timing and tests)
  *   "affine_overlap" 1/0  affine kinds: the 2*eS*U contraction of a Hess-vec runs on a second stream beside the A(.) / A'(.)
  *                       chain (default 0: measured slower than one stream; kept for A/B timing; results agree to rounding)
  *   "trip2"        0/1/2  chunked path, sparse C / oblique manifold / one rank: two launches per tCG trip (12 vector passes,
@@ -728,6 +733,14 @@ int msdp_debug_trip_form(msdp_handle h, int32_t* form);
  * one-reduction trip (option "pipe_own"; every row of C holds an entry in its own column or has fewer than 5 entries); 0 = any other
  * instance, or no fused launch.  Read-only: no launch. */
 int msdp_debug_fused_own(msdp_handle h, int32_t* own);
+/* (test / diagnostic) The plan of the next fused launch at the resident point: *G = its workgroups (0: no fused launch applies),
+ * *rw_split = the waves of a workgroup that compute all three row slots (4 in the wide plan of option "pipe_wide", where the other four
+ * waves compute two; 0 = every wave computes every slot: any other instance).  Read-only: no launch. */
+int msdp_debug_fused_plan(msdp_handle h, int32_t* G, int32_t* rw_split);
+/* (test / diagnostic) The planning rule of the wide plan alone, host arithmetic without a handle or a launch: *G = the smallest multiple
+ * of 8, at least 8 and at most min(256, cus / 8 * 8), with ceil(n_loc / G) <= 80, or 0 where there is none.  cus <= 0 asks for the
+ * current device's CU count; *cus_used returns the count that was used. */
+int msdp_debug_fused_wide_rule(int32_t n_loc, int32_t cus, int32_t* G, int32_t* cus_used);
 /* (test / diagnostic) What the set-up of a primal affine handle (MSDP_KIND_UNITDIAG, _UNITTRACE, _GENERIC) planned from the constraint
  * data, and which branch the last calls took.  Host only: no launch, the handle is not modified.  out[0..15]:
  *    0 usym      1 = c and every A_k are symmetric entry by entry (upper view, tiled adjoint, B route possible)

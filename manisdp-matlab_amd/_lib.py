@@ -150,6 +150,8 @@ SIGNATURES = {
     "msdp_debug_affine_plan": (C.c_int, [C.c_void_p, _P(C.c_int32)]),
     "msdp_debug_trip_form": (C.c_int, [C.c_void_p, _P(C.c_int32)]),
     "msdp_debug_fused_own": (C.c_int, [C.c_void_p, _P(C.c_int32)]),
+    "msdp_debug_fused_plan": (C.c_int, [C.c_void_p, _P(C.c_int32), _P(C.c_int32)]),
+    "msdp_debug_fused_wide_rule": (C.c_int, [C.c_int32, C.c_int32, _P(C.c_int32), _P(C.c_int32)]),
     "msdp_point_snapshot": (C.c_int, [C.c_void_p]),
     "msdp_point_restore": (C.c_int, [C.c_void_p]),
     "msdp_al_primal": (C.c_int, [C.c_void_p, _dp, _dp]),
@@ -222,6 +224,14 @@ def _dptr(a):
 
 def set_device(dev):
     _check(load().msdp_set_device(int(dev)))
+
+
+def fused_wide_rule(n_loc, cus=0):
+    """(G, cus_used) of the wide plan's planning rule alone (msdp_debug_fused_wide_rule): host arithmetic, no handle, no launch.
+    G = 0 where the wide plan does not apply; cus <= 0 asks for the current device's CU count."""
+    g, c = C.c_int32(), C.c_int32()
+    _check(load().msdp_debug_fused_wide_rule(int(n_loc), int(cus), C.byref(g), C.byref(c)))
+    return g.value, c.value
 
 
 def device_count():
@@ -995,6 +1005,13 @@ class Handle:
         v = C.c_int32()
         _check(self._lib.msdp_debug_fused_own(self._h, C.byref(v)))
         return v.value
+
+    def fused_plan(self):
+        """(G, rw_split) of the next fused launch (msdp_debug_fused_plan): its workgroups (0: no fused launch) and the waves per workgroup
+        that compute all three row slots (0: every wave does)."""
+        g, s = C.c_int32(), C.c_int32()
+        _check(self._lib.msdp_debug_fused_plan(self._h, C.byref(g), C.byref(s)))
+        return g.value, s.value
 
     def trip_form(self):
         """Trip of the chunked tCG at the resident point (msdp_debug_trip_form): 1 the linear-product trip, 2 the two-launch trip,

@@ -149,6 +149,7 @@ extern "C" int msdp_debug_persist_trace(msdp_handle h, int32_t reps, uint64_t* o
     msdp_persist_trace_dims(h, &G, &nj, &j0);
     dims[0] = G; dims[1] = nj; dims[2] = j0;
     const bool fused = reps <= 0;                                  // the TR iterations of one trustregions() call in the fused launch
+    if (fused) { G = msdp_fused_grid(h); dims[0] = G; }            // (the fused launch plans its own grid)
     const size_t cnt = (size_t)G * nj * 8 * (fused ? 2 : 1);       // (fused: + the trips of one TR iteration, msdp_pipe.h MSDP_TRACE_KSEL)
     if (fused) { j0 = 0; dims[2] = 0; }
     if (cap < (int64_t)cnt || (!fused && reps < j0 + nj)) { msdp_set_error("persist_trace: cap >= %zu entries and reps >= %d needed", cnt, j0 + nj); return MSDP_EINVAL; }

@@ -192,6 +192,9 @@ struct Dev {
     // The pose-graph kind (msdp_pose.hip) is the same storage with efree = 1: blocks of blk = d + 1 rows, the last of them a free
     // (Euclidean) row; Lambda stays d x d with d = blk - efree (nb * d * d doubles per slot), eG holds 0 in the free-row entries
     int blk, nb, efree;
+    // fused own-column launch in its wide plan (k_tcg_pipe_ws, msdp_pipe.h): the waves [0, rw_split) of a workgroup compute all three row
+    // slots, the others two; 0 everywhere else.  (Sits in what was padding in front of the pointers: no other member moves.)
+    int rw_split;
     const int* brp; const int* bci; const double* bval;
     double* Lam[2];
     // pose-graph kind, option "precon" (msdp_pose_precon.hip): pcM = the inverses M_i^-1 of the diagonal blocks sym(C_[ii]) (nb * blk * blk
@@ -250,6 +253,8 @@ struct Tuning {
     int persist_ep = 1;        // CSR rows of the persistent tCG: entry-parallel lanes where the rows leave lanes free (A/B: 0 never)
     int persist_goff = 1;      // persistent tCG: the byte offsets of the R x EW gathers of a trip live in registers (0: recomputed per trip from the LDS copy of the column indices)
     int pipe_local = 1;        // one-reduction trip: neighbours that belong to the same workgroup are read from LDS, the diagonal from registers
+    int pipe_wide = 1;         // fused own-column launch: the wide plan -- the fewest workgroups whose chunks end inside the first half of the third row slot
+                               //   (<= 80 rows), waves 4..7 compute two slots (k_tcg_pipe_ws; 0: the plan of persist_grid and its instance; A/B, tests)
     int pipe_own = 1;          // fused one-reduction trip at 16 lanes per row: a row's entry in its own column from registers, 12 gathers a trip (0: all 15; A/B, tests)
     int xr_twolevel = 0;       // process ranks: 1 = two-level grid reductions (msdp_psync.h psync2) also where the flat ones would do (one device, <= 4 members); A/B, tests
     int pipe_refresh = 16;     // one-reduction trip: trips between two direct exchanges (its recurrences drift with the square of this)
@@ -383,6 +388,7 @@ struct msdp_handle_s {
     int persist_sig_lpr = 0, persist_sig_ew = 0, persist_sig_r = 0, persist_sig_G = 0, persist_sig_ok = 0;
     const void* persist_sig_fn = nullptr; const void* fused_sig_fn = nullptr;     // the kernel instance the cached answers are for
     int fused_sig_lpr = 0, fused_sig_ew = 0, fused_sig_G = 0, fused_sig_ok = 0;
+    int slots_grid = 0;               // workgroups of the last persistent launch on psync_slots (a launch on another grid resets the slot lines first)
     bool ell_own_col = false;         // ELL copy: every local row has an entry in its own column or a padding slot (msdp_upload_sparse_rows)
     // persistent tCG kernel of the block kinds (msdp_blockpersist.hip): cached eligibility, the slot region of the next launch
     const void* blkpersist_sig_fn = nullptr; int blkpersist_sig_G = 0, blkpersist_sig_ok = 0; size_t blkpersist_sig_lds = 0;
@@ -533,6 +539,7 @@ int msdp_persist_fused_ok(msdp_handle h);                     // whole trustregi
 int msdp_launch_rtr_fused(msdp_handle h);
 size_t msdp_psync_bytes();
 int msdp_tr_tail_grid(msdp_handle h);                         // (persist_grid)
+int msdp_fused_grid(msdp_handle h);                           // workgroups of the fused launch (fused_grid: the wide plan where it applies, else persist_grid)
 int msdp_persist_trace_dims(msdp_handle h, int* G, int* nj, int* j0);
 int msdp_xpersist_eligible(msdp_handle h, int nranks);
 size_t msdp_xpersist_slot_bytes();

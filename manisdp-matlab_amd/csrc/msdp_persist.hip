@@ -962,7 +962,8 @@ static size_t pipe_lds(const PersistPlan& pl) { const size_t rows = (size_t)pl.r
 
 // The persistent kernel has its own grid: at most one workgroup per CU (co-residency), independent of the grid
 // of the row-parallel kernels around it (those exchange data through global memory only).
-static int persist_grid(const Dev& d) {
+// (the CUs of the current device, asked once per process: persist_grid, fused_grid and the occupancy check of the fused launch)
+static int device_cus() {
     static int cus = -1;
     if (cus < 0) {
         int dev = 0, v = 0;
@@ -971,6 +972,10 @@ static int persist_grid(const Dev& d) {
         else cus = 0;
         (void)hipGetLastError();
     }
+    return cus;
+}
+static int persist_grid(const Dev& d) {
+    const int cus = device_cus();
     // (round 5: NOT d.G -- the grid of the row-parallel kernels follows THEIR lanes per row: 4 lanes at p <= 8, i.e. 256 rows per
     // pass and 80 workgroups for G81, on which this kernel (8 lanes per row at least) needed its four-slot instance and left two
     // thirds of the CUs idle: p = 8 6.8 us per trip against 5.5 at p = 16, p = 4 not eligible at all (12.6 us on the chunked path);
@@ -979,6 +984,8 @@ static int persist_grid(const Dev& d) {
     if (g > cus) g = (cus / 8) * 8;
     // the fewest workgroups that need the same number of row slots: a workgroup with 93 rows in three slots of 32 takes as
     // long as one with 79, and the grid synchronisation has fewer slots to poll
+    // (round 12: true of the instances whose waves all compute every row slot, i.e. all but k_tcg_pipe_ws -- the fused own-column
+    // launch plans its grid in fused_grid below, where 79 rows ARE cheaper than 93)
     PersistPlan pl;
     if (g >= 8 && persist_plan(d, g, pl)) {
         // (CSR rows, round 5: the row slots of a workgroup are walked one after the other, each a chain of gather batches as long as
@@ -1032,6 +1039,15 @@ int msdp_launch_tcg_persist(msdp_handle h, int reset_slots) {
     if (persist_is_pipe(h, pl, false)) pl.lds += pipe_lds(pl);
     Dev dp = h->d;
     dp.G = G;
+    // A launch on another grid than the handle's last persistent launch (round 12: the fused launch may run on more workgroups than
+    // this one) starts from clean slot lines whatever the caller asked for.  Defensive: every caller of today passes reset_slots = 1
+    // for the first launch of a call and the fused launch always resets, so no sequence of today's calls needs it.  What it guards: a
+    // launch leaves the lines of its last generations POSTED (a workgroup puts generation g - 1 back to the sentinel when it has passed
+    // g, nobody does that for the last ones).  A per-iteration launch on G workgroups that followed a fused one on more WITHOUT a reset
+    // would meet, in the lines below G, the values the fused launch posted for the same generation numbers: its first polls would
+    // pass before its own workgroups have posted and its sums would be the fused launch's.  (The lines >= G it never polls: in0 / in1.)
+    if (h->slots_grid != G) reset_slots = 1;
+    h->slots_grid = G;
     if (reset_slots) {
         hipLaunchKernelGGL(k_psync_reset, dim3(8), dim3(256), 0, h->stream, h->psync_slots, h->psync_err);
         HIPCHK(hipGetLastError());
@@ -1058,6 +1074,7 @@ extern "C" int msdp_debug_persist_form(msdp_handle h, int32_t* form) {
 }
 int msdp_persist_trace_dims(msdp_handle h, int* G, int* nj, int* j0) { *G = persist_grid(h->d); *nj = MSDP_TRACE_NJ; *j0 = MSDP_TRACE_J0; return 0; }
 
+// (the tail KERNEL follows the per-iteration tCG launch, never the fused one, whose tail is part of its own kernel on fused_grid)
 int msdp_tr_tail_grid(msdp_handle h) { return persist_grid(h->d); }
 
 // The own-column form of the fused one-reduction launch at 16 lanes per row (msdp_pipe.h, OWNC): only where every local row holds an
@@ -1065,9 +1082,45 @@ int msdp_tr_tail_grid(msdp_handle h) { return persist_grid(h->d); }
 static bool fused_takes_own(msdp_handle h, const PersistPlan& pl) {
     return h->tune.pipe_own && h->ell_own_col && pl.ep <= 1 && pl.lpr == 16 && pl.ew == 5 && pl.r == 3 && persist_is_pipe(h, pl, true);
 }
-static persist_fn fused_kernel(msdp_handle h, const PersistPlan& pl) {
+// The grid of the FUSED launch (round 12).  The own-column instance has a second form, k_tcg_pipe_ws (msdp_pipe.h), in which the waves
+// [rw_split, PWAVES) compute R - 1 of the R = 3 row slots: right where no chunk reaches into the second half of the last slot, i.e.
+// ceil(n_loc / G) <= (R - 1) RSTEP + RSTEP / 2 = 80 rows.  The wide plan takes the SMALLEST such G (a multiple of 8, at most
+// min(256, CUs / 8 x 8)) and rw_split = PWAVES / 2: G81 runs on 256 workgroups of 78 - 79 rows instead of 216 of 92 - 93, and every
+// SIMD runs 3 + 2 slot bodies per trip instead of 6.  Where no such G exists, for every other instance and with the option
+// "pipe_wide" off: persist_grid and rw_split = 0 (k_tcg_pipe_obl).
+// The rule alone, host arithmetic: the workgroups of the wide plan for n_loc rows on a device with `cus` CUs (cap = the rows a chunk
+// may hold), or 0 where no grid of at most min(256, cus / 8 x 8) workgroups keeps every chunk within cap
+static int fused_wide_rule(int n_loc, int cus, int cap) {
+    const int gmax = cus >= 256 ? 256 : (cus / 8) * 8;
+    int g = (((n_loc + cap - 1) / cap + 7) / 8) * 8;
+    if (g < 8) g = 8;
+    return (g <= gmax && (n_loc + g - 1) / g <= cap) ? g : 0;
+}
+static int fused_grid(msdp_handle h, int* rw_split) {
+    *rw_split = 0;
+    const int G0 = persist_grid(h->d);
+    PersistPlan pl;
+    if (!h->tune.pipe_wide || G0 < 8 || !persist_plan(h->d, G0, pl) || !fused_takes_own(h, pl)) return G0;
+    const int rstep = plan_rstep(pl), cap = (pl.r - 1) * rstep + rstep / 2;
+    const int g = fused_wide_rule(h->d.n_loc, device_cus(), cap);
+    PersistPlan pw;
+    if (g < 8 || !persist_plan(h->d, g, pw) || !fused_takes_own(h, pw)) return G0;
+    *rw_split = PWAVES / 2;
+    return g;
+}
+// (test / diagnostic, host only: no handle, no launch) the wide plan's workgroups for n_loc rows at 16 lanes per row (chunks of at most
+// 80 rows) on a device with `cus` CUs -- cus <= 0: the current device's, returned in *cus_used; *G = 0 where the wide plan does not apply
+extern "C" int msdp_debug_fused_wide_rule(int32_t n_loc, int32_t cus, int32_t* G, int32_t* cus_used) {
+    if (!G || !cus_used || n_loc < 1) return MSDP_EINVAL;
+    const int c = cus > 0 ? cus : device_cus();
+    *cus_used = c;
+    *G = fused_wide_rule(n_loc, c, 2 * PWAVES * 4 + PWAVES * 2);
+    return 0;
+}
+int msdp_fused_grid(msdp_handle h) { int s; return fused_grid(h, &s); }
+static persist_fn fused_kernel(msdp_handle h, const PersistPlan& pl, int rw_split = 0) {
     persist_fn fn = persist_kernel(pl, true, persist_mode(h));
-    if (fn && fused_takes_own(h, pl)) fn = k_tcg_pipe_obl<16, 5, 3, false, true, 0, 1, true>;
+    if (fn && fused_takes_own(h, pl)) fn = rw_split ? k_tcg_pipe_ws<false> : k_tcg_pipe_obl<16, 5, 3, false, true, 0, 1, true>;
     return fn;
 }
 
@@ -1088,12 +1141,13 @@ int msdp_persist_fused_ok(msdp_handle h) {
     if (!h->tune.fused_rtr) return 0;
     if (!msdp_persist_eligible(h)) return 0;
     PersistPlan pl;
-    const int G = persist_grid(h->d);
+    int rw_split = 0;
+    const int G = fused_grid(h, &rw_split);
     if (!persist_plan(h->d, G, pl)) return 0;
     // where the one-reduction trip exists for per-iteration launches only, those beat the fused two-reduction launch (G81 p = 32:
     // 164 000 against 143 000 Hess-vec/s)
     if (persist_is_pipe(h, pl, false) && !persist_is_pipe(h, pl, true)) return 0;
-    persist_fn fn = fused_kernel(h, pl);
+    persist_fn fn = fused_kernel(h, pl, rw_split);
     if (!fn) return 0;
     {   // (the one-reduction form: + ls and HQs)
         const bool pipe = persist_is_pipe(h, pl, true), early = persist_is_early(h, pl, true);
@@ -1102,23 +1156,26 @@ int msdp_persist_fused_ok(msdp_handle h) {
     }
     if (h->fused_sig_lpr == pl.lpr && h->fused_sig_ew == pl.ew && h->fused_sig_G == G && h->fused_sig_fn == (const void*)fn) return h->fused_sig_ok;
     int ok = 0, per_cu = 0;
+    const int cus = device_cus();
+    // (one workgroup per CU on the fused launch's OWN grid: msdp_persist_eligible has checked persist_grid, which may be smaller)
     if (hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds) == hipSuccess &&
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)fn, PB, pl.lds) == hipSuccess)
-        ok = per_cu >= 1 ? 1 : 0;
+        ok = (per_cu >= 1 && cus >= G) ? 1 : 0;
     (void)hipGetLastError();
     h->fused_sig_lpr = pl.lpr; h->fused_sig_ew = pl.ew; h->fused_sig_G = G; h->fused_sig_fn = (const void*)fn; h->fused_sig_ok = ok;
     return ok;
 }
 
 int msdp_launch_rtr_fused(msdp_handle h) {
-    const int G = persist_grid(h->d);
+    int rw_split = 0;
+    const int G = fused_grid(h, &rw_split);
     PersistPlan pl;
     if (!persist_plan(h->d, G, pl)) { msdp_set_error("fused RTR: not eligible"); return MSDP_ESTATE; }
-    persist_fn fn = fused_kernel(h, pl);
+    persist_fn fn = fused_kernel(h, pl, rw_split);
     if (!fn) { msdp_set_error("fused RTR: no kernel instance"); return MSDP_ESTATE; }
     if (h->tune.timing) fprintf(stderr, "[msdp_rtr] fused launch: <%d, %d, %d>, %s%s, G = %d\n", pl.lpr, pl.ew, pl.r,
                                 persist_is_pipe(h, pl, true) ? "one reduction per trip" : "two reductions per trip",
-                                fused_takes_own(h, pl) ? ", own column from registers" : "", G);
+                                fused_takes_own(h, pl) ? (rw_split ? ", own column from registers, waves 4..7 two row slots" : ", own column from registers") : "", G);
     {   // (the one-reduction form: + ls and HQs)
         const bool pipe = persist_is_pipe(h, pl, true), early = persist_is_early(h, pl, true);
         const size_t rows = (size_t)pl.r * plan_rstep(pl);
@@ -1126,10 +1183,12 @@ int msdp_launch_rtr_fused(msdp_handle h) {
     }
     Dev dp = h->d;
     dp.G = G;
+    dp.rw_split = rw_split;
+    h->slots_grid = G;                                 // (the reset below is unconditional: see msdp_launch_tcg_persist)
     if (dp.trace) {
         // (msdp_debug_persist_trace with reps <= 0: the phases of the TR iterations around the tCGs, FSTAMP in msdp_pipe.h)
         if (!(pl.lpr == 16 && pl.ew == 5 && pl.r == 3 && persist_is_pipe(h, pl, true))) { msdp_set_error("fused trace: only the one-reduction <16, 5, 3> instance (17 <= p <= 32, rows of <= 5 entries) is traced"); return MSDP_EUNSUPPORTED; }
-        fn = fused_takes_own(h, pl) ? k_tcg_pipe_obl<16, 5, 3, true, true, 0, 1, true> : k_tcg_pipe_obl<16, 5, 3, true, true>;
+        fn = fused_takes_own(h, pl) ? (rw_split ? k_tcg_pipe_ws<true> : k_tcg_pipe_obl<16, 5, 3, true, true, 0, 1, true>) : k_tcg_pipe_obl<16, 5, 3, true, true>;
         HIPCHK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
     }
     hipLaunchKernelGGL(k_psync_reset, dim3(8), dim3(256), 0, h->stream, h->psync_slots, h->psync_err);
@@ -1146,6 +1205,17 @@ extern "C" int msdp_debug_fused_own(msdp_handle h, int32_t* own) {
     PersistPlan pl;
     if (!persist_plan(h->d, persist_grid(h->d), pl)) return 0;
     *own = fused_takes_own(h, pl) ? 1 : 0;
+    return 0;
+}
+// The plan of the next fused launch of this handle: its workgroups and the number of waves per workgroup that compute all three row slots
+// (0: every wave does -- any instance but the wide form of the own-column one).  G = 0 where no fused launch applies.
+extern "C" int msdp_debug_fused_plan(msdp_handle h, int32_t* G, int32_t* rw_split) {
+    if (!h || !G || !rw_split) return MSDP_EINVAL;
+    *G = 0; *rw_split = 0;
+    if (!msdp_persist_fused_ok(h)) return 0;
+    int s = 0;
+    *G = fused_grid(h, &s);
+    *rw_split = s;
     return 0;
 }
 

@@ -398,8 +398,12 @@ __device__ __forceinline__ bool psync2_8(unsigned long long* blk, unsigned long 
 #ifndef MSDP_OWN_SPREAD
 #define MSDP_OWN_SPREAD 0x369c
 #endif
+// ... and the eight requests of a wave that computes two of the three row slots (RW = 2): 2/2/2/2 without the last place
+#ifndef MSDP_OWN_SPREAD2
+#define MSDP_OWN_SPREAD2 0x2468
+#endif
 #if MSDP_PIPE_LINES
-#define PSYNC8(slots, gen, G, v, sh8, shb8, err, bid, backoff, tr, f) psync8_lines(slots, gen, G, v, sh8, shp, shb8, err, bid, backoff, tr, f)
+#define PSYNC8(slots, gen, G, v, sh8, shb8, err, bid, backoff, tr, f) psync8_lines(slots, gen, G, v, sh8, PIPE_SHP, shb8, err, bid, backoff, tr, f)
 #else
 #define PSYNC8(slots, gen, G, v, sh8, shb8, err, bid, backoff, tr, f) psync8(slots, gen, G, v, sh8, shb8, err, bid, backoff, tr, f)
 #endif
@@ -420,8 +424,20 @@ __device__ __forceinline__ bool psync2_8(unsigned long long* blk, unsigned long 
 // requests R x 4 = 12 rows, not 15 (X[3][4]); the fold order is the one of the five-column form (column 0 first), and for a row without a
 // diagonal the exact zero of the padding term moves from the last place of the fold to the first: the same bits.  The refresh trip's two
 // direct gathers keep all five columns (tangent(r) and md of the trip before are no longer in registers): two passes, 4 + 1.
-template <int LPR, int EW, int R, bool TRACE, bool FUSE, int XRM = 0, int EP = 1, bool OWNC = false>
+// RW (round 12): the row slots THIS WAVE computes, beside R, the row slots of the workgroup's LAYOUT (ROWS, RSTEP, every LDS array, cs[] /
+// vs[], set-up and the final write-back).  Every loop over the row slots in a trip and in the TR tail runs to RW; a slot that is not
+// computed issues no store, no gather and no LDS write, its part of Ys / Gs / YPs / GPs / eGs / EGPs keeps set-up's zeros and nothing
+// reads it (NL = 0 in the instance that uses it).  RW < R is for the waves whose last slot holds no row in ANY workgroup of the launch
+// (the host's plan says so: fused_grid in msdp_persist.hip); such a slot only ever added +0 to a sum, so the bits are those of RW = R.
+// k_tcg_pipe_ws below runs two bodies, RW = R and R - 1, in one workgroup.  EXTSH: the static LDS arrays of the reductions are those of
+// pipe_ws_shared() (2 x 8 x PWAVES + 16 doubles) -- two bodies in one kernel must share them, and each instantiation would get its own.
+__device__ __forceinline__ double* pipe_ws_shared() {
+    __shared__ double shx[16 * PWAVES + 16];
+    return shx;
+}
+template <int LPR, int EW, int R, bool TRACE, bool FUSE, int XRM = 0, int EP = 1, bool OWNC = false, int RW = R, bool EXTSH = false>
 __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* slots, int* err, const int bx) {
+    static_assert(RW == R || (RW == R - 1 && OWNC && EXTSH), "a wave computes all row slots of the layout, or all but the last (own-column fused instance)");
     constexpr bool XR = XRM != 0, XTWO = XRM == 2;
     constexpr bool CSR = EW == 0;
     static_assert(!XR || (!FUSE && !TRACE), "cross-rank instances: per-iteration launches");
@@ -457,6 +473,10 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
     __shared__ double sh8[8 * PWAVES];
     __shared__ double shp[8 * PWAVES];
     __shared__ double shb8[16];
+    // (EXTSH: the three arrays are the shared ones; an instantiation's own are then unused and take no LDS)
+#define PIPE_SH8 (EXTSH ? pipe_ws_shared() : sh8)
+#define PIPE_SHP (EXTSH ? pipe_ws_shared() + 8 * PWAVES : shp)
+#define PIPE_SHB8 (EXTSH ? pipe_ws_shared() + 16 * PWAVES : shb8)
     constexpr int RPW = 64 / (LPR * EP);
     constexpr int RSTEP = PWAVES * RPW;
     constexpr int ROWS = R * RSTEP;
@@ -648,7 +668,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
         for (int w = 0; w < EW; ++w) {
             bool glob = false;
 #pragma unroll
-            for (int r = 0; r < R; ++r) glob = glob || ls[w * ROWS + SLOT(r)] < 0;
+            for (int r = 0; r < RW; ++r) glob = glob || ls[w * ROWS + SLOT(r)] < 0;
             lead_ok = lead_ok && __builtin_amdgcn_ballot_w64(glob) == 0ULL;
             if (lead_ok) nl = w + 1;
         }
@@ -681,7 +701,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
     if (XR) {
         bool any = false, any2 = false;
 #pragma unroll
-        for (int r = 0; r < R; ++r) { any = any || pds[SLOT(r)] != 0ULL; any2 = any2 || pds[ROWS + SLOT(r)] != 0ULL; }
+        for (int r = 0; r < RW; ++r) { any = any || pds[SLOT(r)] != 0ULL; any2 = any2 || pds[ROWS + SLOT(r)] != 0ULL; }
         xr_has_push2 = __builtin_amdgcn_ballot_w64(any2) != 0ULL;
         xr_has_push = xr_has_push2 || __builtin_amdgcn_ballot_w64(any) != 0ULL;
     }
@@ -720,7 +740,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
     double vkeep[CSR_KEEP ? R : 1][CSR_CB];
     if (CSR_KEEP) {
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
+        for (int r = 0; r < RW; ++r) {
             const bool rok = ROK(r);
             const int s0 = rok ? d.rowptr[ROW(r)] : 0, s1 = rok ? d.rowptr[ROW(r) + 1] : 0;
 #pragma unroll
@@ -809,8 +829,9 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
     // MSDP_OWN_SPREAD holds SP1 .. SP4 as four hexadecimal digits: 0x369c = 3/3/3/3 without the last place, 0x0369 = 3/3/3/3 without
     // on_ready, 0x368a = 3/3/2/2/2 (the runs are in profiles/r11_trip_instruction_counts.md)
     constexpr bool SPREAD = PARK;
-    constexpr int SP1 = !OWNC ? 3 : ((MSDP_OWN_SPREAD >> 12) & 15), SP2 = !OWNC ? 6 : ((MSDP_OWN_SPREAD >> 8) & 15);
-    constexpr int SP3 = !OWNC ? 9 : ((MSDP_OWN_SPREAD >> 4) & 15), SP4 = !OWNC ? 12 : (MSDP_OWN_SPREAD & 15), SP5 = R * NG;
+    constexpr int OSP = RW == R ? MSDP_OWN_SPREAD : MSDP_OWN_SPREAD2;
+    constexpr int SP1 = !OWNC ? 3 : ((OSP >> 12) & 15), SP2 = !OWNC ? 6 : ((OSP >> 8) & 15);
+    constexpr int SP3 = !OWNC ? 9 : ((OSP >> 4) & 15), SP4 = !OWNC ? 12 : (OSP & 15), SP5 = RW * NG;
     static_assert(!OWNC || (SP1 <= SP2 && SP2 <= SP3 && SP3 <= SP4 && SP4 <= SP5), "the places take the requests in order");
     // SPLIT: the four sums without H md under the gather, the other four behind the row stores: the instances whose gather is not
     // requested in one batch inside the reduction
@@ -822,13 +843,13 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
                 const unsigned coff = (unsigned)cs[(NC0 + k % NGD) * ROWS + SLOT(k / NGD)]; \
                 X[k / NGD][k % NGD] = ld2_cp<XTWO ? 17 : MSDP_CPOL_SC1>(rs_md, (base) + (BOFF ? coff + gcol8 : (coff * gld + gcol) * 8u)); } } while (0)
 #define PIPE_SPREAD(ka, kb) do { if (SPREAD && !pub) PIPE_ISSUE_PART(xq * half_bytes, ka, kb); } while (0)
-    double2 X[R][NG > 0 ? NG : 1];                                 // the gathered rows (in flight across the end of a trip)
+    double2 X[RW][NG > 0 ? NG : 1];                                 // the gathered rows (in flight across the end of a trip)
     for (;;) {
         PTSTAMP(0);
         // ---- the products: C md of this trip (cmd) and C tangent(r) (ctr)
         // columns [w0, w0 + NG) of the rows my rows reference, requested from (rs, base) / folded into acc
 #define PIPE_ISSUE(rs, base, w0) do { \
-            _Pragma("unroll") for (int r = 0; r < R; ++r) \
+            _Pragma("unroll") for (int r = 0; r < RW; ++r) \
             _Pragma("unroll") for (int w = 0; w < NG; ++w) { \
                 if ((w0) + w < EW) { \
                     const unsigned coff = (unsigned)cs[((w0) + w) * ROWS + SLOT(r)]; \
@@ -846,21 +867,21 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
                 (acc).x = fma(vv, xx.x, (acc).x); (acc).y = fma(vv, xx.y, (acc).y); } } while (0)
         // all EW columns through the buffer (the gradient / the refresh vectors are not in LDS): passes of NG columns
 #define PIPE_GATHER_ALL(rs, base, dst) do { \
-            if (CSR) { _Pragma("unroll") for (int r = 0; r < R; ++r) (dst)[r] = csr_gather(r, (rs), (base)); break; } \
-            _Pragma("unroll") for (int r = 0; r < R; ++r) (dst)[r] = zz; \
+            if (CSR) { _Pragma("unroll") for (int r = 0; r < RW; ++r) (dst)[r] = csr_gather(r, (rs), (base)); break; } \
+            _Pragma("unroll") for (int r = 0; r < RW; ++r) (dst)[r] = zz; \
             _Pragma("unroll") for (int w0 = 0; w0 < EW; w0 += (NG > 0 ? NG : 1)) { \
                 PIPE_ISSUE(rs, base, w0); \
-                _Pragma("unroll") for (int r = 0; r < R; ++r) PIPE_FOLDX(r, (dst)[r], w0); } \
-            if (!colok) { _Pragma("unroll") for (int r = 0; r < R; ++r) (dst)[r] = zz; } } while (0)
+                _Pragma("unroll") for (int r = 0; r < RW; ++r) PIPE_FOLDX(r, (dst)[r], w0); } \
+            if (!colok) { _Pragma("unroll") for (int r = 0; r < RW; ++r) (dst)[r] = zz; } } while (0)
         // OWNC: column 0 from the lane's own copy of the row (`own`: the bits a gather of that column would return), columns 1 .. EW - 1
         // through the buffer; the fold order of PIPE_GATHER_ALL
 #define PIPE_GATHER_OWN(rs, base, own, dst) do { \
             PIPE_ISSUE(rs, base, NO); \
-            _Pragma("unroll") for (int r = 0; r < R; ++r) { \
+            _Pragma("unroll") for (int r = 0; r < RW; ++r) { \
                 const double v0 = vs[SLOT(r)]; \
                 (dst)[r] = make_double2(fma(v0, (own)[r].x, 0.0), fma(v0, (own)[r].y, 0.0)); \
                 PIPE_FOLDX(r, (dst)[r], NO); } \
-            if (!colok) { _Pragma("unroll") for (int r = 0; r < R; ++r) (dst)[r] = zz; } } while (0)
+            if (!colok) { _Pragma("unroll") for (int r = 0; r < RW; ++r) (dst)[r] = zz; } } while (0)
         // the eight partial sums of this trip's reduction.  Round 6, the instances that do NOT have the next gather requested in one
         // batch inside the reduction (!PREF: the fused launch at 16 lanes per row, whose requests are spread from the reduction to the
         // loop's back edge since round 10 -- the last rows are still on their way at the top of the trip): four sums -- <md, g>, <md, Heta>, <r, r>, the model value -- do not
@@ -872,7 +893,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
         auto pre_sums = [&]() {
             if (!SPLIT) return;
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
+            for (int r = 0; r < RW; ++r) {
                 const double2 g = Gs[r * PB + threadIdx.x], mdr = md[r], e0 = eta[r], rv = rr[r];
                 const double2 rg = make_double2(rv.x - g.x, rv.y - g.y);                  // Heta (:220)
                 v[3] += mdr.x * g.x + mdr.y * g.y;                                        // <md, g>
@@ -888,7 +909,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
             if (OWNC) PIPE_GATHER_OWN(rs_g, g_base, md, cmd);      // (md = the gradient row: the bits in d.Gr / region 5 or 6)
             else PIPE_GATHER_ALL(rs_g, g_base, cmd);
 #pragma unroll
-            for (int r = 0; r < R; ++r) ctr[r] = cmd[r];
+            for (int r = 0; r < RW; ++r) ctr[r] = cmd[r];
         } else {
             if (direct) {
                 // the trip before published tangent(r) and md next to Hmd: both products start afresh from direct gathers
@@ -901,14 +922,14 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
             // PARK: the two recurrences come back from LDS while the gathers are in flight (a refresh trip has just formed both afresh)
             if (PARK && !direct) {
 #pragma unroll
-                for (int r = 0; r < R; ++r) { ctr[r] = CTs[r * PB + threadIdx.x]; cmd[r] = CMs[r * PB + threadIdx.x]; }
+                for (int r = 0; r < RW; ++r) { ctr[r] = CTs[r * PB + threadIdx.x]; cmd[r] = CMs[r * PB + threadIdx.x]; }
             }
             // (a lane without columns gathers column 0 of the rows: its product is masked -- under ONE workgroup-uniform branch per trip, so
             // that a launch whose lanes all have columns, ld = 2 LPR, pays nothing for it; CSR rows mask inside csr_gather.  A row slot
             // past `hi` needs no mask: its vs[] are zero, set-up)
             auto products = [&](auto masked) {
 #pragma unroll
-                for (int r = 0; r < R; ++r) {
+                for (int r = 0; r < RW; ++r) {
                     double2 a = zz;
                     if (CSR) a = csr_gather(r, rs_md, (xq ^ 1u) * half_bytes);
                     else {
@@ -936,7 +957,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
         pub = pub && !first;
         // ---- Hmd = proj(C*md) - md.*eG (tCG.m:163, ManiSDP_onlyunitdiag.m:127-130), its rows to the neighbours, the eight partial sums
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
+        for (int r = 0; r < RW; ++r) {
             const double2 acc = cmd[r];
             // PARK: this is the last use of cmd[r] in the trip (ctr[r]'s was in the products) -- both to their slots, on every path
             // (first trip, refresh, recurrence)
@@ -968,7 +989,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
         if (pub) {
             // the refresh rows: md and tangent(r) of this trip's start, in a block of their own behind the rows of Hmd
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
+            for (int r = 0; r < RW; ++r) {
                 const double2 y = Ys[r * PB + threadIdx.x], mdr = md[r], rv = rr[r];
                 const double dn = msdp_group_sum_all<LPR>(rv.x * y.x + rv.y * y.y);
                 if (BSTORE) {
@@ -985,7 +1006,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
         if (SPLIT) {
             // (every row store of the trip is on its way: the sums that need H md run under their drain)
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
+            for (int r = 0; r < RW; ++r) {
                 const double2 hq = hmd[r], mdr = md[r], e0 = eta[r], rv = rr[r];
                 v[0] += mdr.x * hq.x + mdr.y * hq.y;                                      // <md, Hmd>   (:166)
                 v[1] += rv.x * hq.x + rv.y * hq.y;                                        // <r, Hmd>
@@ -1003,9 +1024,9 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
             else if (PREF && !pub) { PIPE_ISSUE(rs_md, xq * half_bytes, NC0); have_x = true; }
         };
         if (XTWO) {
-            if (!psync2_8(d.xr2_blk, shpeer, d.xr2_n, d.xr2_me, xri, gen++, GS + d.xr2_skip, v, sh8, shb8, err, bid, backoff, next_gather)) { failed = true; break; }
+            if (!psync2_8(d.xr2_blk, shpeer, d.xr2_n, d.xr2_me, xri, gen++, GS + d.xr2_skip, v, PIPE_SH8, PIPE_SHB8, err, bid, backoff, next_gather)) { failed = true; break; }
         } else
-        if (!PSYNC8(slots, gen++, GS, v, sh8, shb8, err, bid, backoff,
+        if (!PSYNC8(slots, gen++, GS, v, PIPE_SH8, PIPE_SHB8, err, bid, backoff,
                     (TRACE && !FUSE && j >= MSDP_TRACE_J0 && j < MSDP_TRACE_J0 + MSDP_TRACE_NJ) ? d.trace + ((size_t)bx * MSDP_TRACE_NJ + (j - MSDP_TRACE_J0)) * 8 :
                     (FTRIP_ON ? FTRIP_PTR : nullptr),
                     next_gather)) { failed = true; break; }
@@ -1018,7 +1039,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
         if (!bench && (d_Hd <= 0.0 || e_Pe_new >= Delta * Delta)) {                       // :183
             const double tau = (-e_Pd + sqrt(e_Pd * e_Pd + d_Pd * (Delta * Delta - e_Pe))) / d_Pd;   // :188
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
+            for (int r = 0; r < RW; ++r) {
                 eta[r].x -= tau * md[r].x; eta[r].y -= tau * md[r].y;                     // :192
                 rr[r].x -= tau * hmd[r].x; rr[r].y -= tau * hmd[r].y;                     // :198 (Heta = r - grad)
             }
@@ -1034,7 +1055,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
         if (!bench && new_model >= model_value) { stop = 6; ++j; break; }                 // :228 (eta, Heta stay)
         PIPE_SPREAD(SP2, SP3);
 #pragma unroll
-        for (int r = 0; r < R; ++r) {                                                     // :233-238
+        for (int r = 0; r < RW; ++r) {                                                     // :233-238
             eta[r].x -= alpha * md[r].x; eta[r].y -= alpha * md[r].y;
             rr[r].x -= alpha * hmd[r].x; rr[r].y -= alpha * hmd[r].y;
         }
@@ -1054,7 +1075,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
         PIPE_SPREAD(SP3, SP4);
         // ---- mdelta = tangent(r + beta*mdelta)  (:273,283)
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
+        for (int r = 0; r < RW; ++r) {
             const double2 y = Ys[r * PB + threadIdx.x];
             const double2 vv = make_double2(rr[r].x + beta * md[r].x, rr[r].y + beta * md[r].y);
             const double dot = msdp_group_sum_all<LPR>(vv.x * y.x + vv.y * y.y);
@@ -1085,15 +1106,15 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
     // the first direction = the gradient, whose rows every member keeps to itself: hand them to the others first (region 2: the refresh
     // trips use it from trip `refresh` on, long behind the first trip's gather)
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
+    for (int r = 0; r < RW; ++r) {
         if (OK(r)) st2_sc1(rs_md, 2u * half_bytes + ROWB(r), md[r]);
         xr_push(r, 2u, md[r]);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (XTWO) {
         double z0 = 0.0, z1 = 0.0, z2 = 0.0;
-        if (!psync2(d.xr2_blk, shpeer, d.xr2_n, d.xr2_me, xri, gen++, GS + d.xr2_skip, 0, z0, z1, z2, sh8, shb8, err, bid, backoff, false)) return;
-    } else if (!pbar8_lines(slots, gen++, GS, shb8, err, bid, backoff)) return;
+        if (!psync2(d.xr2_blk, shpeer, d.xr2_n, d.xr2_me, xri, gen++, GS + d.xr2_skip, 0, z0, z1, z2, PIPE_SH8, PIPE_SHB8, err, bid, backoff, false)) return;
+    } else if (!pbar8_lines(slots, gen++, GS, PIPE_SHB8, err, bid, backoff)) return;
     rs_g = rs_md; g_base = 2u * half_bytes;
   }
   bool first_tr = true;
@@ -1102,7 +1123,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
     if (FUSE && !first_tr) {
         // tCG.m:102-157 at the (possibly new) current point: eta = 0, r = mdelta = grad
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
+        for (int r = 0; r < RW; ++r) {
             const double2 g = Gs[r * PB + threadIdx.x];
             eta[r] = zz; rr[r] = g; md[r] = g; hmd[r] = zz; cmd[r] = zz; ctr[r] = zz;   // (cmd / ctr: dead across the tail, said so)
         }
@@ -1132,6 +1153,10 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
     // hardware behaviour, not the HIP model's guarantee.  Making `nl` workgroup-uniform would send every workgroup of a grid in natural
     // order to NL = 2 (each holds the two ends of its chunk).  Covered on the device by the G81 tests: a workgroup there mixes NL = 3
     // waves (interior), NL = 2 (the two waves at the chunk's ends) and NL = 0 (the waves with the wrap-around columns of a grid row).
+    // Round 12, the same reliance one level up: k_tcg_pipe_ws sends the waves of a workgroup into two instantiations of this whole
+    // BODY (RW = R and RW = R - 1).  Both run the same barriers -- the __syncthreads() behind set-up, PSYNC8 per trip, pbar8_lines and
+    // PSYNC8 per TR iteration -- and leave their loops on the same workgroup-uniform values (the reduced sums, ctl), so the arrivals
+    // pair up as above.  Covered on the device by tests/test_gpu_fused_wave_slots.py.
     if (MULTI && nl >= 3) trips(std::integral_constant<int, MULTI ? 3 : 0>());
     else if (MULTI && nl == 2) trips(std::integral_constant<int, MULTI ? 2 : 0>());
     else trips(std::integral_constant<int, 0>());
@@ -1141,7 +1166,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
     if (!FUSE) {
         // ---- hand eta, Heta = r - grad and the final scalars to the RTR kernels (trustregions.m:540-550)
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
+        for (int r = 0; r < RW; ++r) {
             if (OK(r)) {
                 const int64_t o = (int64_t)ROW(r) * d.ld + 2 * sub;
                 const double2 g = Gs[r * PB + threadIdx.x];
@@ -1167,7 +1192,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
     double tv[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};          // [0] cost, [1] |grad|^2 at the proposal, [2] <eta, grad + .5 Heta>
     const unsigned yx_base = 4u * half_bytes, gx_base = (5u + (unsigned)(cur ^ 1)) * half_bytes;   // the proposal's rows / its gradient's rows
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
+    for (int r = 0; r < RW; ++r) {
         const double2 y = Ys[r * PB + threadIdx.x], g = Gs[r * PB + threadIdx.x];
         const double2 e0 = eta[r];
         const double2 he = make_double2(rr[r].x - g.x, rr[r].y - g.y);
@@ -1184,7 +1209,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
     }
     FSTAMP(3);
     // (my proposal rows are performed before the post: the wait is inside)
-    if (!pbar8_lines(slots, gen++, GS, shb8, err, bid, backoff)) return;
+    if (!pbar8_lines(slots, gen++, GS, PIPE_SHB8, err, bid, backoff)) return;
     FSTAMP(4);
     // cost and gradient at the proposal (ManiSDP_onlyunitdiag.m:117-125): YC = Y*C, eG = sum(YC.*Y), G = YC - Y.*eG
     auto prop_finish = [&](int r, double2 acc) {
@@ -1205,16 +1230,16 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
     };
     if (CSR) {
 #pragma unroll
-        for (int r = 0; r < R; ++r) prop_finish(r, csr_gather(r, rs_md, yx_base));
+        for (int r = 0; r < RW; ++r) prop_finish(r, csr_gather(r, rs_md, yx_base));
     } else if (R * EW <= 16) {                                     // all gathers in flight (wider rows: a row slot at a time, registers)
         // (OWNC: the proposal's own row is the value this lane stored into region 4, still in YPs -- R x 4 loads)
-        double2 XG[R][EW > 0 ? EW : 1];
+        double2 XG[RW][EW > 0 ? EW : 1];
 #pragma unroll
-        for (int r = 0; r < R; ++r)
+        for (int r = 0; r < RW; ++r)
 #pragma unroll
             for (int w = NO; w < EW; ++w) XG[r][w] = ld2_sc1(rs_md, yx_base + (BOFF ? (unsigned)cs[w * ROWS + SLOT(r)] + gcol8 : ((unsigned)cs[w * ROWS + SLOT(r)] * gld + gcol) * 8u));
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
+        for (int r = 0; r < RW; ++r) {
             double2 acc = zz;
             if (OWNC) XG[r][0] = YPs[r * PB + threadIdx.x];
 #pragma unroll
@@ -1223,7 +1248,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
         }
     } else {
 #pragma unroll 1
-        for (int r = 0; r < R; ++r) {
+        for (int r = 0; r < RW; ++r) {
             double2 xw[EW > 0 ? EW : 1];
 #pragma unroll
             for (int w = 0; w < EW; ++w) xw[w] = ld2_sc1(rs_md, yx_base + (BOFF ? (unsigned)cs[w * ROWS + SLOT(r)] + gcol8 : ((unsigned)cs[w * ROWS + SLOT(r)] * gld + gcol) * 8u));
@@ -1238,7 +1263,7 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
     // gradient inside this reduction -- the first gather of the next tCG when the step is accepted -- was built and measured: the R x EW
     // row registers do not survive the decision block, the compiler parks them in scratch and WAITS for the loads to do so: the
     // reduction went from 6 300 to 15 500 ticks.  The first trip gathers them itself.)
-    if (!PSYNC8(slots, gen++, GS, tv, sh8, shb8, err, bid, backoff, nullptr, []() {})) return;
+    if (!PSYNC8(slots, gen++, GS, tv, PIPE_SH8, PIPE_SHB8, err, bid, backoff, nullptr, []() {})) return;
     FSTAMP(6);
     {   // trustregions.m:548-729, identical in every workgroup (same bits in, same decision out)
         const double fp = tv[0], ggp = tv[1], prd = tv[2];
@@ -1299,6 +1324,9 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
         cw->tcg_running = 0;
         frame_store(&d.F[0], 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, 0, stop, 0, 0, 0);
     }
+#undef PIPE_SH8
+#undef PIPE_SHP
+#undef PIPE_SHB8
 #undef FSTAMP
 #undef SLOT
 #undef ROW
@@ -1310,4 +1338,18 @@ __device__ __forceinline__ void tcg_pipe_body(const Dev& d, unsigned long long* 
 template <int LPR, int EW, int R, bool TRACE = false, bool FUSE = false, int XRM = 0, int EP = 1, bool OWNC = false>
 __global__ __launch_bounds__(PB) void k_tcg_pipe_obl(Dev d, unsigned long long* slots, int* err) {
     tcg_pipe_body<LPR, EW, R, TRACE, FUSE, XRM, EP, OWNC>(d, slots, err, (int)blockIdx.x);
+}
+
+// Round 12, the wide plan of the fused own-column launch (fused_grid in msdp_persist.hip): every workgroup's chunk ends inside the
+// first half of the last row slot, so that slot holds rows of the waves [0, rw_split) only.  The kernel branches ONCE, on a
+// wave-uniform value, into a body that computes all R = 3 row slots and one that computes two; the layout (LDS, row -> slot -> lane) is
+// that of three slots in both, and the two share no live state: the number of slots a wave computes is a compile-time constant of the
+// code it runs, no run-time branch inside the trip.  ASSUMPTION (not observable from the kernel): the waves of a workgroup are placed on
+// the SIMDs round robin, w and w + 4 on SIMD w % 4; with rw_split = PWAVES / 2 a SIMD then runs 3 + 2 slot bodies per trip where
+// k_tcg_pipe_obl runs 3 + 3.  What was measured is in profiles/r12_trip_instruction_counts.md (the phases of the traced twins).
+template <bool TRACE>
+__global__ __launch_bounds__(PB) void k_tcg_pipe_ws(Dev d, unsigned long long* slots, int* err) {
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (wave < d.rw_split) tcg_pipe_body<16, 5, 3, TRACE, true, 0, 1, true, 3, true>(d, slots, err, (int)blockIdx.x);
+    else tcg_pipe_body<16, 5, 3, TRACE, true, 0, 1, true, 2, true>(d, slots, err, (int)blockIdx.x);
 }

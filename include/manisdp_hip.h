@@ -129,7 +129,8 @@ int msdp_create_onlyunitdiag_csc_lowrank(int64_t n, const int64_t* jc, const int
  * msdp_escape_eigs returns k complex eigenvectors of S = C - diag(z): V holds k columns of n (re, im) pairs (2 n k doubles),
  * orthonormal in the complex inner product, eigenvalues ascending, none reported more often than S has it (Lanczos path on
  * the real view; span(Y) is not deflated).  msdp_rtr runs the generic per-iteration path.
- * MSDP_EUNSUPPORTED: every communicator, msdp_round_hyperplane, msdp_factor_gram / _rotate / _append. */
+ * MSDP_EUNSUPPORTED: every communicator, msdp_round_hyperplane, msdp_factor_gram / _rotate / _append -- the kind has calls
+ * of its own for both: msdp_round_phases (rounding to phases) and msdp_hfactor_gram / _rotate / _append (below). */
 int msdp_create_onlyunitdiag_csc_hermitian(int64_t n, const int64_t* jc, const int64_t* ir, const double* val, int32_t pcap,
                                            msdp_handle* out);
 
@@ -358,6 +359,18 @@ int msdp_blockfactor_gram(msdp_handle h, double* G);
 int msdp_blockfactor_rotate(msdp_handle h, int32_t r, const double* Q, int32_t* ndeg);
 int msdp_blockfactor_append(msdp_handle h, int32_t k, const double* V, double alpha, int32_t* ndeg);
 int msdp_blockfactor_round(msdp_handle h, const double* W, double* R, double* t, int32_t* flipped, int32_t* ndeg);
+/* The same steps for the Hermitian kind (msdp_create_onlyunitdiag_csc_hermitian; msdp_factor_gram / _rotate / _append stay
+ * refused for it), p counting COMPLEX columns (msdp_get_p / 2).  Any other handle: MSDP_EUNSUPPORTED, the message names the
+ * call.  No resident point: MSDP_ESTATE.  All three run the kernels of the real calls on the real view of the factor.
+ * msdp_hfactor_gram: G = Y^H Y, p x p complex row-major, (re, im) pairs (2 p p doubles).
+ * msdp_hfactor_rotate: Y <- Y*Q with Q p x r complex ROW-major, (re, im) pairs; 1 <= r <= p, else MSDP_EINVAL.
+ * msdp_hfactor_append: Y <- [Y, alpha*V] with every row scaled to unit norm; V as msdp_escape_eigs returns it on such a
+ *   handle: k columns of n (re, im) pairs.  MSDP_EUNSUPPORTED, with nothing modified, when p + k exceeds the complex width
+ *   the handle has allocated: re-enter through msdp_set_point then.
+ * After _rotate / _append the cost state is invalid, as after msdp_set_point. */
+int msdp_hfactor_gram(msdp_handle h, double* G);
+int msdp_hfactor_rotate(msdp_handle h, int32_t r, const double* Q);
+int msdp_hfactor_append(msdp_handle h, int32_t k, const double* V, double alpha);
 int msdp_get_p(msdp_handle h, int32_t* p);
 /* MSDP_KIND_* of the handle: tells a binding which factor layout the handle expects at the boundary
  * (p x n for ONLYUNITDIAG / UNITDIAG, n x p for UNITTRACE / GENERIC) without guessing from array shapes. */
@@ -431,6 +444,38 @@ int msdp_linesearch_accept(msdp_handle h);
 #define MSDP_ROUND_MAX_TRIALS 4096
 int msdp_round_hyperplane(msdp_handle h, int32_t trials, const double* R, int32_t sweeps, double* values0, double* values,
                           int32_t* info, uint64_t* masks, int32_t* best, int8_t* x);
+
+/* Rounding of the resident point of a Hermitian handle (msdp_create_onlyunitdiag_csc_hermitian) to phases, with a
+ * coordinate-minimisation local search, on the device (not in the reference).  The target is the unit circle (M = 0) or the
+ * M-th roots of unity (2 <= M <= MSDP_ROUND_PHASES_MAX_M): phase synchronisation, unimodular programmes, M-PSK detection.
+ *   Table: c_k = (cos, sin)(2 pi k / M), k = 0 .. M-1, built on the host in double: the angle is ((2 * pi) * k) / M with
+ *     pi = 3.141592653589793, evaluated left to right, and goes to the C library's cos and sin; where 4 k is a multiple of M
+ *     the entry is written as exactly (1, 0), (0, 1), (-1, 0) or (0, -1) (4 k / M = 0, 1, 2, 3), so M = 2 and M = 4 are exact.
+ *   Rounding: w = sum_a Y_ia R_ta for the `trials` rows of R (trials x p complex row-major, (re, im) pairs, p = msdp_get_p / 2;
+ *     complex products, no conjugate, ascending a).  M = 0: z_i = w / sqrt(w.re^2 + w.im^2), z_i = 1 where that is 0.
+ *     M >= 2: z_i = c_k with the k of the largest Re(conj(c_k) w) = c.re w.re + c.im w.im, the lowest k at a tie.
+ *   val_t = sum_i Re(conj(z_i) sum_j C_ij z_j), diagonal included; deterministic sums (fixed row chunks added in index
+ *     order, no floating-point atomics).
+ *   sweeps > 0: up to `sweeps` Gauss-Seidel sweeps per trial -- rows i = 0 .. n-1 in order, s_i = sum_{j != i} C_ij z_j in
+ *     stored order.  M = 0: z_i <- -s_i / |s_i|, left as it is where |s_i|^2 == 0; exactly `sweeps` sweeps run.  M >= 2: with
+ *     cur = z_i.re s.re + z_i.im s.im and cand_k the same expression for c_k, k* the minimising k (the lowest at a tie),
+ *     z_i <- c_k* only where cand_k* < cur strictly.  A phase is a bit copy of its table entry, so a converged phase never
+ *     counts as changed.  The 64 trials of a word sweep together; a word stops after a sweep of its own without a change, the
+ *     call when every word has stopped.  All values are then recomputed from the final phases.
+ * trials: a multiple of 64, at most MSDP_ROUND_PHASES_MAX_TRIALS.  The call holds trials * n complex numbers on the device
+ * (MSDP_ENOMEM when they cannot be had) and releases every allocation before it returns.
+ *   values0 (trials, may be NULL): the values right after the rounding;   values (trials): the final ones;   info
+ *   (2 x trials/64, may be NULL): per word the sweeps run, then per word the changes of its last sweep (0 for M = 0);   phases
+ *   (may be NULL): all final phases in the device layout [trials/64][n][64] of (re, im) pairs;   *best: the trial of the
+ *   smallest value (the lowest index wins a tie);   z (n (re, im) pairs, may be NULL): the phases of trial *best;   k (n, may
+ *   be NULL, must be NULL with M = 0): their table indices.
+ * The point, the cost state and the options of the handle stay as they are.  MSDP_EUNSUPPORTED: any other kind of handle.
+ * MSDP_EINVAL: M outside {0, 2 .. MSDP_ROUND_PHASES_MAX_M}, trials <= 0, not a multiple of 64 or above the cap, sweeps < 0,
+ * R / values / best NULL, k not NULL with M = 0.  MSDP_ESTATE: no resident point. */
+#define MSDP_ROUND_PHASES_MAX_TRIALS 1024
+#define MSDP_ROUND_PHASES_MAX_M 64
+int msdp_round_phases(msdp_handle h, int32_t M, int32_t trials, const double* R, int32_t sweeps, double* values0,
+                      double* values, int32_t* info, double* phases, int32_t* best, double* z, int32_t* k);
 
 /* ----------------------------------------------------------------- escape */
 

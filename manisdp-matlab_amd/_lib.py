@@ -44,6 +44,8 @@ ESTATE, EUNSUPPORTED = -4, -6
 EINVAL = -1
 ROUND_MAX_TRIALS = 4096             # MSDP_ROUND_MAX_TRIALS
 LOWRANK_MAX = 8                     # MSDP_LOWRANK_MAX
+ROUND_PHASES_MAX_TRIALS = 1024      # MSDP_ROUND_PHASES_MAX_TRIALS
+ROUND_PHASES_MAX_M = 64             # MSDP_ROUND_PHASES_MAX_M
 
 
 _P = C.POINTER
@@ -93,6 +95,7 @@ SIGNATURES = {
     "msdp_linesearch_accept": (C.c_int, [C.c_void_p]),
     "msdp_round_hyperplane": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.c_int32, _dp, _dp, _i32p, _P(C.c_uint64), _i32p,
                                         _P(C.c_int8)]),
+    "msdp_round_phases": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _dp, C.c_int32, _dp, _dp, _i32p, _dp, _i32p, _dp, _i32p]),
     "msdp_escape_eigs": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int32, _dp, _dp, _dp, _P(C.c_int32)]),
     "msdp_escape_eigs_matrix": (C.c_int, [C.c_void_p, _dp, C.c_int32, C.c_double, C.c_int32, _dp, _dp, _dp,
                                          _P(C.c_int32)]),
@@ -125,6 +128,9 @@ SIGNATURES = {
     "msdp_factor_gram": (C.c_int, [C.c_void_p, _dp]),
     "msdp_factor_rotate": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
     "msdp_factor_append": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.c_double, C.c_int32]),
+    "msdp_hfactor_gram": (C.c_int, [C.c_void_p, _dp]),
+    "msdp_hfactor_rotate": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
+    "msdp_hfactor_append": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.c_double]),
     "msdp_blockfactor_gram": (C.c_int, [C.c_void_p, _dp]),
     "msdp_blockfactor_rotate": (C.c_int, [C.c_void_p, C.c_int32, _dp, _i32p]),
     "msdp_blockfactor_append": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.c_double, _i32p]),
@@ -634,6 +640,60 @@ class Handle:
         assert Vf.shape[0] == self.n
         _check(self._lib.msdp_factor_append(self._h, Vf.shape[1], _dptr(Vf), float(alpha), 1 if normalize else 0))
         self.p += Vf.shape[1]
+
+    # ---- the Hermitian kind's factor between two trustregions() calls (msdp_hfactor_*); p counts complex columns
+    def hfactor_gram(self):
+        """Y^H Y of the resident factor of an onlyunitdiag_hermitian handle: a complex p x p array (computed on the device)."""
+        pc = self.p if self.hermitian else max(self.p // 2, 1)      # (any other handle: the library refuses the call)
+        G = np.zeros((pc, pc), dtype=np.complex128)
+        _check(self._lib.msdp_hfactor_gram(self._h, _dptr(G.view(np.float64))))
+        return G
+
+    def hfactor_rotate(self, Q):
+        """Resident factor <- factor @ Q (Q: p x r complex): the rank cut, on the device (msdp_hfactor_rotate)."""
+        Q = np.ascontiguousarray(Q, dtype=np.complex128)
+        if Q.ndim != 2 or (self.hermitian and self.p and Q.shape[0] != self.p):   # (no point yet, or another kind: the library refuses the call)
+            raise ValueError(f"hfactor_rotate: Q must be p x r with p = {self.p}, not {Q.shape}")
+        _check(self._lib.msdp_hfactor_rotate(self._h, Q.shape[1], _dptr(Q.view(np.float64))))
+        self.p = Q.shape[1]
+
+    def hfactor_append(self, V, alpha):
+        """Resident factor <- [factor, alpha * V] (V: n x k complex) with the rows renormalised, on the device
+        (msdp_hfactor_append)."""
+        Vf = np.asfortranarray(V, dtype=np.complex128)
+        if Vf.ndim != 2 or Vf.shape[0] != self.n:
+            raise ValueError(f"hfactor_append: V must be n x k with n = {self.n}, not {Vf.shape}")
+        Vb = np.ascontiguousarray(Vf.T)                           # k columns of n (re, im) pairs
+        _check(self._lib.msdp_hfactor_append(self._h, Vf.shape[1], _dptr(Vb.view(np.float64)), float(alpha)))
+        self.p += Vf.shape[1]
+
+    def round_phases(self, R, M=0, sweeps=0, phases=False):
+        """Rounding of the resident point of an onlyunitdiag_hermitian handle to phases on the device (msdp_round_phases):
+        z_t = round(Y r_t) for the rows r_t of R (trials x p complex, trials a multiple of 64) to the unit circle (M = 0) or the
+        M-th roots of unity, the values z_t^H C z_t, then up to `sweeps` Gauss-Seidel sweeps of coordinate minimisation.
+        Returns a dict: values0 (after the rounding), values (final), info (2 x trials/64: sweeps run and changes of the last
+        sweep, per word of 64 trials), best (trial of the smallest value), z (its phases, complex n), k (their table indices,
+        int32; M >= 2 only) and, when asked for, phases (all final phases, a (trials/64, n, 64) complex array)."""
+        R = np.ascontiguousarray(R, dtype=np.complex128)
+        if R.ndim != 2 or (self.hermitian and self.p and R.shape[1] != self.p):   # (no point yet, or another kind: the library refuses the call)
+            raise ValueError(f"round_phases: R must be trials x p = {self.p}, not {R.shape}")
+        T = R.shape[0]
+        W = max(T // 64, 1)
+        values0, values = np.zeros(T), np.zeros(T)
+        info = np.zeros((2, W), dtype=np.int32)
+        P = np.zeros((W, self.n, 64), dtype=np.complex128) if phases else None
+        z = np.zeros(self.n, dtype=np.complex128)
+        k = np.zeros(self.n, dtype=np.int32) if M else None
+        best = C.c_int32()
+        _check(self._lib.msdp_round_phases(self._h, int(M), T, _dptr(R.view(np.float64)), int(sweeps), _dptr(values0), _dptr(values),
+                                           info.ctypes.data_as(_i32p), _dptr(P.view(np.float64)) if phases else None,
+                                           C.byref(best), _dptr(z.view(np.float64)), k.ctypes.data_as(_i32p) if M else None))
+        out = {"values0": values0, "values": values, "info": info, "best": best.value, "z": z}
+        if M:
+            out["k"] = k
+        if phases:
+            out["phases"] = P
+        return out
 
     # ---- the block kinds' factor between two trustregions() calls, and their rounding (msdp_blockfactor_*)
     def blockfactor_gram(self):

@@ -56,6 +56,106 @@ int msdp_hermitian_jcopy(msdp_handle h, const double* v, double* w) {
     return 0;
 }
 
+// ---- the factor between two trustregions() calls (msdp_hfactor_gram / _rotate / _append): the complex algebra is real algebra
+// on the real view, so all three run the kernels of msdp_factor_gram / _rotate / _append (msdp_kernels.hip) at real width 2p;
+// only the host-side packing of G, Q and V is complex.
+static int hfactor_check(msdp_handle h, const char* call) {
+    if (h->d.costkind != COST_HERM) {
+        msdp_set_error("%s: for Hermitian handles only (the real kinds take msdp_factor_gram / _rotate / _append, the block kinds msdp_blockfactor_*)", call);
+        return MSDP_EUNSUPPORTED;
+    }
+    if (!h->have_point) { msdp_set_error("%s: no resident point", call); return MSDP_ESTATE; }
+    return 0;
+}
+
+// G = Y^H Y from the real Gram matrix Gr of the real view: Re G_ab = Gr[2a,2b] + Gr[2a+1,2b+1], Im G_ab = Gr[2a,2b+1] - Gr[2a+1,2b]
+extern "C" int msdp_hfactor_gram(msdp_handle h, double* G) {
+    MSDP_CHECK_H(h);
+    int rc = hfactor_check(h, "hfactor_gram");
+    if (rc) return rc;
+    if (!G) { msdp_set_error("hfactor_gram: null out"); return MSDP_EINVAL; }
+    Dev& d = h->d;
+    const int ld = d.ld, p = d.p / 2;
+    const int nblk = (int)std::min<int64_t>(64, std::max<int64_t>(1, (int64_t)(1 << 22) / ((int64_t)ld * ld)));
+    double* buf = nullptr;
+    if ((rc = msdp_dev_alloc<double>(h, &buf, ((size_t)nblk + 1) * ld * ld))) return rc;
+    double* out = buf + (size_t)nblk * ld * ld;
+    std::vector<double> Gr((size_t)ld * ld);
+    rc = msdp_k_fgram(h, d.Y[msdp_host_cur(h)], buf, nblk, out);
+    if (!rc && msdp_memcpy_async(Gr.data(), out, Gr.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess) {
+        msdp_set_error("hfactor_gram: D2H failed"); rc = MSDP_EHIP;
+    }
+    (void)hipStreamSynchronize(h->stream);
+    msdp_dev_free(h, buf);
+    if (rc) return rc;
+    for (int a = 0; a < p; ++a)
+        for (int b = 0; b < p; ++b) {
+            G[2 * ((size_t)a * p + b)] = Gr[(size_t)(2 * a) * ld + 2 * b] + Gr[(size_t)(2 * a + 1) * ld + 2 * b + 1];
+            G[2 * ((size_t)a * p + b) + 1] = Gr[(size_t)(2 * a) * ld + 2 * b + 1] - Gr[(size_t)(2 * a + 1) * ld + 2 * b];
+        }
+    return 0;
+}
+
+// Y <- Y Q: the real view times the 2p x 2r matrix with the block [qr, qi; -qi, qr] per complex q_ab
+extern "C" int msdp_hfactor_rotate(msdp_handle h, int32_t r, const double* Q) {
+    MSDP_CHECK_H(h);
+    int rc = hfactor_check(h, "hfactor_rotate");
+    if (rc) return rc;
+    Dev& d = h->d;
+    const int p = d.p / 2;
+    if (!Q || r < 1 || r > p) { msdp_set_error("hfactor_rotate: r = %d outside 1..p = %d, or null Q", r, p); return MSDP_EINVAL; }
+    std::vector<double> Qr((size_t)4 * p * r);
+    const size_t ldq = (size_t)2 * r;
+    for (int a = 0; a < p; ++a)
+        for (int b = 0; b < r; ++b) {
+            const double qr = Q[2 * ((size_t)a * r + b)], qi = Q[2 * ((size_t)a * r + b) + 1];
+            Qr[(size_t)(2 * a) * ldq + 2 * b] = qr;      Qr[(size_t)(2 * a) * ldq + 2 * b + 1] = qi;
+            Qr[(size_t)(2 * a + 1) * ldq + 2 * b] = -qi; Qr[(size_t)(2 * a + 1) * ldq + 2 * b + 1] = qr;
+        }
+    const int cur = msdp_host_cur(h), rn = 2 * r;
+    double* qd = nullptr;
+    if ((rc = msdp_dev_alloc<double>(h, &qd, Qr.size()))) return rc;
+    if (msdp_memcpy_async(qd, Qr.data(), Qr.size() * sizeof(double), hipMemcpyHostToDevice, h->stream) != hipSuccess) {
+        msdp_set_error("hfactor_rotate: H2D failed"); rc = MSDP_EHIP;
+    }
+    if (!rc) rc = msdp_k_frotate(h, msdp_rows_capacity(h), rn, rn, d.Y[cur], qd, d.Y[cur ^ 1]);
+    (void)hipStreamSynchronize(h->stream);
+    msdp_dev_free(h, qd);
+    if (rc) return rc;
+    return msdp_adopt_point(h, cur ^ 1, rn);
+}
+
+// Y <- rows_normalised([Y, alpha V]): k complex columns are 2k real ones (re, im of column c at real columns 2c, 2c + 1), and
+// the real row norm is the complex one
+extern "C" int msdp_hfactor_append(msdp_handle h, int32_t k, const double* V, double alpha) {
+    MSDP_CHECK_H(h);
+    int rc = hfactor_check(h, "hfactor_append");
+    if (rc) return rc;
+    Dev& d = h->d;
+    if (!V || k < 1) { msdp_set_error("hfactor_append: k = %d, or null V", k); return MSDP_EINVAL; }
+    if (d.p + 2 * k > h->pcap) {
+        msdp_set_error("hfactor_append: width %d exceeds the allocated capacity %d (complex columns; use msdp_set_point)", d.p / 2 + k, h->pcap / 2);
+        return MSDP_EUNSUPPORTED;
+    }
+    const int n = d.n, cur = msdp_host_cur(h), pn = d.p + 2 * k;
+    std::vector<double> Vr((size_t)2 * k * n);
+    for (int c = 0; c < k; ++c)
+        for (int i = 0; i < n; ++i) {
+            Vr[(size_t)(2 * c) * n + i] = V[2 * ((size_t)c * n + i)];
+            Vr[(size_t)(2 * c + 1) * n + i] = V[2 * ((size_t)c * n + i) + 1];
+        }
+    double* vd = nullptr;
+    if ((rc = msdp_dev_alloc<double>(h, &vd, Vr.size()))) return rc;
+    if (msdp_memcpy_async(vd, Vr.data(), Vr.size() * sizeof(double), hipMemcpyHostToDevice, h->stream) != hipSuccess) {
+        msdp_set_error("hfactor_append: H2D failed"); rc = MSDP_EHIP;
+    }
+    if (!rc) rc = msdp_k_fappend(h, msdp_rows_capacity(h), 2 * k, pn, d.Y[cur], vd, alpha, 1, d.Y[cur ^ 1]);
+    (void)hipStreamSynchronize(h->stream);
+    msdp_dev_free(h, vd);
+    if (rc) return rc;
+    return msdp_adopt_point(h, cur ^ 1, pn);
+}
+
 // h_rowptr / h_colind hold the pattern (column j of the CSC input = row j); val: nnz (re, im) pairs in the same order.
 int msdp_hermitian_setup(msdp_handle h, const double* val) {
     Dev& d = h->d;

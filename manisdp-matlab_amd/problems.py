@@ -1229,6 +1229,41 @@ def phase_synchronization(n, degree, sigma, rng):
     return C, z
 
 
+def mpsk_synchronization(n, degree, sigma, M, rng):
+    """Synchronisation of M-PSK symbols: phase_synchronization's graph and noise with planted M-th roots of unity.  Returns
+    ``(C, z)`` as phase_synchronization does.  Definition, in draw order: ``z = exp(2 pi i rng.integers(M, size=n) / M)``; then
+    the edges, ``w = (rng.standard_normal(m) + 1j rng.standard_normal(m)) / sqrt(2)`` (the real draw first) and ``C`` exactly as
+    in phase_synchronization."""
+    n, M = int(n), int(M)
+    if M < 2:
+        raise ValueError(f"mpsk_synchronization: M = {M} (at least 2)")
+    z = np.exp(2j * np.pi * rng.integers(M, size=n) / M)
+    i = np.concatenate([np.arange(n) for _ in range(1, int(degree) // 2 + 1)] or [np.zeros(0, dtype=np.int64)])
+    j = np.concatenate([(np.arange(n) + d * d + 1) % n for d in range(1, int(degree) // 2 + 1)] or [np.zeros(0, dtype=np.int64)])
+    keep = i != j
+    i, j = i[keep], j[keep]
+    m = i.size
+    wr = rng.standard_normal(m)
+    wi = rng.standard_normal(m)
+    w = (wr + 1j * wi) / np.sqrt(2.0)
+    H = sp.coo_matrix((z[i] * np.conj(z[j]) + float(sigma) * w, (i, j)), shape=(n, n)).tocsr()
+    H = H + H.conj().T
+    C = sp.csr_matrix(-H)
+    C.sort_indices()
+    return C, z
+
+
+def phase_error(z, z_true, M=0):
+    """``max_i |g z_i - z_true_i|`` over the global phase g that a synchronisation leaves free.  M = 0: g is the unit-modulus
+    alignment ``sum_i conj(z_i) z_true_i / |.|`` (1 where the sum is 0); M >= 2: the best of the M-th roots of unity."""
+    z, z_true = np.asarray(z, dtype=np.complex128), np.asarray(z_true, dtype=np.complex128)
+    if M == 0:
+        s = np.vdot(z, z_true)
+        g = s / abs(s) if abs(s) > 0 else 1.0
+        return float(np.max(np.abs(g * z - z_true)))
+    return float(min(np.max(np.abs(np.exp(2j * np.pi * k / int(M)) * z - z_true)) for k in range(int(M))))
+
+
 # --------------------------------------------------------------------------- rotation synchronisation
 def _to_so(M):
     """The nearest rotation(s) to the d x d matrix / stack of matrices M (Frobenius norm): U diag(1, .., det(U V')) V'."""

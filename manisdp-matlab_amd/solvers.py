@@ -250,6 +250,65 @@ def round_unitdiag(C, Y, trials=256, sweeps=50, rng=None, R=None):
     return res["x"], float(res["values"][res["best"]]), res
 
 
+def _round_phases_option(o):
+    """options["round_phases"] = {"M", "trials", "sweeps", "seed"} of a complex Hermitian C: round the solution to phases on the
+    device after the solve (msdp_round_phases; not in the reference, so no DEFAULTS entry).  Returns None when the option is
+    absent, else (M, trials, sweeps, seed) -- M = 0 (the unit circle) or 2 .. _lib.ROUND_PHASES_MAX_M (the M-th roots of unity),
+    trials a multiple of 64 up to _lib.ROUND_PHASES_MAX_TRIALS, sweeps >= 0 (0: no local search)."""
+    r = o.get("round_phases")
+    if r is None:
+        return None
+    if not isinstance(r, dict):
+        raise ValueError(f"options['round_phases'] must be a dict with 'M', 'trials', 'sweeps' and 'seed', not {r!r}")
+    unknown = sorted(set(r) - {"M", "trials", "sweeps", "seed"})
+    if unknown:
+        raise ValueError(f"options['round_phases'] has unknown fields {unknown} (known: 'M', 'trials', 'sweeps', 'seed')")
+    M, trials, sweeps, seed = r.get("M", 0), r.get("trials", 256), r.get("sweeps", 20), r.get("seed", 0)
+    for name, v in (("M", M), ("trials", trials), ("sweeps", sweeps), ("seed", seed)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"options['round_phases'][{name!r}] must be an integer, not {v!r}")
+    if M != 0 and not 2 <= M <= _lib.ROUND_PHASES_MAX_M:
+        raise ValueError(f"options['round_phases']['M'] must be 0 or in 2..{_lib.ROUND_PHASES_MAX_M}, not {M}")
+    if trials <= 0 or trials % 64 or trials > _lib.ROUND_PHASES_MAX_TRIALS:
+        raise ValueError(f"options['round_phases']['trials'] must be a multiple of 64 in 64..{_lib.ROUND_PHASES_MAX_TRIALS}, not {trials}")
+    if sweeps < 0 or seed < 0:
+        raise ValueError(f"options['round_phases']['sweeps'] and ['seed'] must be >= 0, not {sweeps} and {seed}")
+    return int(M), int(trials), int(sweeps), int(seed)
+
+
+def _hermitian_factor_option(o):
+    """options["hermitian_factor"] of a complex Hermitian C: "host" (default) or "device" (the rank decision, the cut and the
+    widening through msdp_hfactor_gram / _rotate / _append); anything else is a ValueError."""
+    mode = o.get("hermitian_factor", "host")
+    if mode not in ("host", "device"):
+        raise ValueError(f"options['hermitian_factor'] must be 'host' or 'device', not {mode!r}")
+    return mode
+
+
+def _draw_phase_R(rng, trials, p):
+    """The Gaussian rows of a phase rounding: the real draw first."""
+    Rr = rng.standard_normal((int(trials), int(p)))
+    return Rr + 1j * rng.standard_normal((int(trials), int(p)))
+
+
+def round_phases(C, Y, M=0, trials=256, sweeps=20, rng=None, R=None):
+    """Round the factor Y (n x p complex, rows of unit norm) of a complex unit-diagonal SDP with Hermitian cost C to phases on
+    the device: `trials` roundings of Y r with complex Gaussian r (drawn from `rng`, the real parts first, unless R, trials x p
+    complex, is given) to the unit circle (M = 0) or the M-th roots of unity, each improved by up to `sweeps` Gauss-Seidel
+    sweeps of coordinate minimisation; the best of them is returned.  Returns (z, value, info): z complex of length n,
+    value = z^H C z, info the dict of Handle.round_phases."""
+    Y = np.ascontiguousarray(Y, dtype=np.complex128)
+    if R is None:
+        R = _draw_phase_R(rng or np.random.default_rng(0), trials, Y.shape[1])
+    h = _lib.Handle.onlyunitdiag_hermitian(C, pcap=max(32, Y.shape[1]))
+    try:
+        h.set_point(Y)
+        res = h.round_phases(R, M=M, sweeps=sweeps)
+    finally:
+        h.close()
+    return res["z"], float(res["values"][res["best"]]), res
+
+
 # =============================================================== onlyunitdiag
 def ManiSDP_onlyunitdiag(C, options=None, verbose=True, rng=None):
     with _host_threads():
@@ -267,6 +326,9 @@ def _onlyunitdiag_impl(C, options=None, verbose=True, rng=None):
         o.setdefault(k, v)
     if getattr(C, "dtype", None) is not None and np.dtype(C.dtype).kind == "c":
         return _onlyunitdiag_hermitian_impl(C, o, verbose, rng)     # complex C: the Hermitian problem (real C: untouched below)
+    if _round_phases_option(o) is not None or _hermitian_factor_option(o) != "host":   # (malformed values: refused by the calls)
+        raise ValueError("options['round_phases'] and options['hermitian_factor'] belong to a complex Hermitian C "
+                         "(a real C takes options['round'] and options['device_factor'])")
     escape_rr = _escape_rr_option(o)                       # (a bad value is refused before anything is built)
     rounding = _round_option(o)
     dense_max = int(o.get("dense_eig_max", 3000))          # the host eig(S) is allowed up to this order (options['eig'] = 'host') ...
@@ -486,7 +548,10 @@ def _onlyunitdiag_hermitian_impl(C, o, verbose, rng):
     those of ManiSDP_onlyunitdiag.m; the algebra is complex: the factor Y is n x p complex with rows of unit modulus sum,
     z = Re sum((C Y) .* conj(Y), 2), the rank decision comes from Y^H Y, the cut is Y Q(:, 1:r), widening is [Y, alpha v] with
     the rows renormalised, X = Y Y^H.  ``o``: the options with the defaults filled in.  Every refusal comes before the first
-    library call."""
+    library call.  Extra option fields: ``hermitian_factor`` ("host" | "device": the rank decision, the cut and the widening through
+    msdp_hfactor_gram / _rotate / _append, the factor resident between the trustregions() calls) and ``round_phases`` = {"M",
+    "trials", "sweeps", "seed"} (msdp_round_phases on the evaluated point: ``data["round"]`` = z, value, values, best, info, and k
+    for M >= 2)."""
     Csp = _lib.hermitian_csc(sp.csc_matrix(C) if not sp.issparse(C) else C).tocsr()   # ValueError unless C == C^H exactly
     for name, what in (("round", "+1/-1 rounding belongs to the real problem"), ("comm", "a single-rank solve is needed")):
         if o.get(name) is not None:
@@ -494,7 +559,9 @@ def _onlyunitdiag_hermitian_impl(C, o, verbose, rng):
     if o["line_search"] == 1:
         raise ValueError("options['line_search'] = 1 is not available for a complex Hermitian C")
     if o.get("device_factor"):
-        raise ValueError("options['device_factor'] is not available for a complex Hermitian C: the rank cut stays on the host")
+        raise ValueError("options['device_factor'] is not available for a complex Hermitian C: its device re-shaping is options['hermitian_factor'] = 'device'")
+    rounding = _round_phases_option(o)
+    device_factor = _hermitian_factor_option(o) == "device"
     dense_max = int(o.get("dense_eig_max", 3000))
     dense_default = int(o.get("dense_eig_default", 600))
     dense_X_max = int(o.get("dense_X_max", 4000))
@@ -517,23 +584,37 @@ def _onlyunitdiag_hermitian_impl(C, o, verbose, rng):
     for name, value in (o.get("device_options") or {}).items():
         h.set_option(name, int(value))
     topts = _rtr_opts(o)
-    data = {"status": 0, "hessvecs": 0, "cost_evals": 0, "rejected": 0, "rtr_seconds": 0.0, "eig_seconds": 0.0, "log": []}
+    # factor_seconds: what the factor costs between the trustregions() calls -- its transfers (after the first upload), the rank
+    # decision, the cut and the widening
+    data = {"status": 0, "hessvecs": 0, "cost_evals": 0, "rejected": 0, "rtr_seconds": 0.0, "eig_seconds": 0.0, "factor_seconds": 0.0,
+            "log": []}
     t0 = time.time()
     dinf0 = None
     obj = dinf = gradnorm = z = None
     certified = True
     Y_eval = Y
+    # options["hermitian_factor"] = "device": the rank decision, the cut and the widening on the device (msdp_hfactor_gram /
+    # _rotate / _append); the factor stays resident between the trustregions() calls and comes to the host once, when the loop
+    # ends -- the device_factor branch of _onlyunitdiag_impl
+    resident = False
     try:
         for it in range(1, int(o["AL_maxiter"]) + 1):      # :38
-            h.set_point(Y)
+            if not resident:
+                t2 = time.time()
+                h.set_point(Y)
+                if it > 1:
+                    data["factor_seconds"] += time.time() - t2
             st = h.rtr(topts)                              # :43
             data["rtr_seconds"] += st.seconds
             data["hessvecs"] += st.hessvecs
             data["cost_evals"] += st.cost_evals
             data["rejected"] += st.rejected
             gradnorm = st.gradnorm
-            Y = h.get_point()
-            Y_eval = Y
+            if not device_factor:
+                t2 = time.time()
+                Y = h.get_point()
+                Y_eval = Y
+                data["factor_seconds"] += time.time() - t2
             z = h.get_z()                                  # :46-47  z = Re sum((C Y) .* conj(Y), 2)
             obj = float(np.sum(z))
             t1 = time.time()
@@ -557,26 +638,65 @@ def _onlyunitdiag_hermitian_impl(C, o, verbose, rng):
                     vS = np.hstack([v_v, vS[:, :max(delta - 1, 0)]])
                     nneg = max(nneg, 1)
                 dinf = dinf_v
-            Q, e, r = _thin_svd_rank(None, float(o["theta"]), gram=Y.conj().T @ Y)   # :52-54 from Y^H Y
+            t2 = time.time()
+            Q, e, r = _thin_svd_rank(None, float(o["theta"]), gram=h.hfactor_gram() if device_factor else Y.conj().T @ Y)   # :52-54 from Y^H Y
+            data["factor_seconds"] += time.time() - t2
             _say(verbose, "Iter %d, obj:%0.8f, dinf:%0.1e, r:%d, p:%d, time:%0.2fs" % (it, obj, dinf, r, p, time.time() - t0))
             data["log"].append((it, obj, dinf, r, p, time.time() - t0, st.hessvecs))
             data["iters"] = it
             if dinf < o["tol"] and certified:              # :57-60
                 _say(verbose, "Optimality is reached!")
+                if device_factor:
+                    Y_eval = h.get_point()
                 break
             if it % 20 == 0:                               # :61-69
                 if it > 50 and dinf > dinf0:
                     data["status"] = 2
                     _say(verbose, "Slow progress!")
+                    if device_factor:
+                        Y_eval = h.get_point()
                     break
                 dinf0 = dinf
             nne = max(min(nneg, delta), 1)                 # :74
+            if device_factor:
+                if it == int(o["AL_maxiter"]):
+                    Y_eval = h.get_point()                 # last pass: the evaluated point, before it is re-shaped
+                t2 = time.time()
+                try:
+                    if r <= p - 1:                         # :70-73
+                        h.hfactor_rotate(Q[:, :r])
+                        p = r
+                    h.hfactor_append(vS[:, :nne], float(o["alpha"]))   # :78-83
+                    p = p + nne
+                    resident = True
+                    data["factor_seconds"] += time.time() - t2
+                    continue
+                except _lib.MsdpError as err:              # wider than the handle's buffers: re-enter through set_point
+                    if "allocated capacity" not in str(err):
+                        raise
+                    Y = h.get_point()                      # the factor as the device holds it (already cut)
+                    Y = np.hstack([Y, o["alpha"] * vS[:, :nne]])
+                    Y = np.ascontiguousarray(Y / np.sqrt(np.sum(np.abs(Y) ** 2, axis=1, keepdims=True)))
+                    p = Y.shape[1]
+                    resident = False
+                    data["factor_seconds"] += time.time() - t2
+                    continue
+            t2 = time.time()
             if r <= p - 1:                                 # :70-73
                 Y = _rank_cut(Y, Q, e, r)
                 p = r
             Y = np.hstack([Y, o["alpha"] * vS[:, :nne]])   # :78-83
             Y = np.ascontiguousarray(Y / np.sqrt(np.sum(np.abs(Y) ** 2, axis=1, keepdims=True)))
             p = p + nne
+            data["factor_seconds"] += time.time() - t2
+        if rounding is not None and obj is not None:           # options["round_phases"]: phases from the evaluated point
+            M, trials, sweeps, seed = rounding
+            h.set_point(Y_eval)
+            res = h.round_phases(_draw_phase_R(np.random.default_rng(seed), trials, Y_eval.shape[1]), M=M, sweeps=sweeps)
+            data["round"] = {"z": res["z"], "value": float(res["values"][res["best"]]), "values": res["values"],
+                             "best": res["best"], "info": res["info"]}
+            if M:
+                data["round"]["k"] = res["k"]
     finally:
         h.close()
     Y = Y_eval

@@ -315,6 +315,16 @@ def ManiSDP_onlyunitdiag(C, options=None, verbose=True, rng=None):
         return _onlyunitdiag_impl(C, options, verbose, rng)
 
 
+def _set_device_options(h, o):
+    """options['device_options']: run-time switches of the handle (msdp_set_option), for A/B runs and tests."""
+    for name, value in (o.get("device_options") or {}).items():
+        h.set_option(name, int(value))
+
+
+def _rows_complex(Y):               # complex oblique factor: rows of unit norm
+    return Y / np.sqrt(np.sum(np.abs(Y) ** 2, axis=1, keepdims=True))
+
+
 def _onlyunitdiag_impl(C, options=None, verbose=True, rng=None):
     """``[X, obj, data] = ManiSDP_onlyunitdiag(C, options)`` (reference
     src/primal/ManiSDP_onlyunitdiag.m:6).  Extra, optional option fields that the
@@ -331,9 +341,8 @@ def _onlyunitdiag_impl(C, options=None, verbose=True, rng=None):
                          "(a real C takes options['round'] and options['device_factor'])")
     escape_rr = _escape_rr_option(o)                       # (a bad value is refused before anything is built)
     rounding = _round_option(o)
-    dense_max = int(o.get("dense_eig_max", 3000))          # the host eig(S) is allowed up to this order (options['eig'] = 'host') ...
-    dense_default = int(o.get("dense_eig_default", 600))   # ... and the default up to this one (round 6: G1, n = 800, 0.124 s with it, 0.047 s
-                                                           # with the device escape + its independent check; the affine kinds switch at 400 / 600)
+    dense_default = int(o.get("dense_eig_default", 600))   # the host eig(S) is the default up to this order (round 6: G1, n = 800, 0.124 s with it,
+                                                           # 0.047 s with the device escape + its independent check; the affine kinds switch at 400 / 600)
     dense_X_max = int(o.get("dense_X_max", 4000))
     rng = rng or np.random.default_rng(0)
 
@@ -364,182 +373,61 @@ def _onlyunitdiag_impl(C, options=None, verbose=True, rng=None):
         Csp = C.tocsr() if sp.issparse(C) else np.asarray(C, dtype=np.float64)
         eig_mode = o.get("eig", "host" if n <= dense_default else "device")
         h = _lib.Handle.onlyunitdiag(Csp, pcap=pcap)
-    # options['comm'] = (nranks, rank, unique_id): rows of the factor and of C sharded over the ranks (msdp_comm_init); this
-    # host loop then runs replicated -- same start point (pass Y0 or seed rng identically), same data, same decisions on
-    # every rank; the escape runs replicated on a full copy of the sparse C (device eigen-solver only)
     if comm is not None:
-        if not (sp.issparse(Csp) or isinstance(C, SyntheticDenseC)):
-            h.close()
-            raise ValueError("row-sharded solves need a sparse C or a problems.SyntheticDenseC")
         eig_mode = "device"
-        _join_comm(h, comm)
-        if o.get("halo_exchange"):                         # only the rows this rank's rows of C reference travel before S*U
-            h.set_option("halo_exchange", 1)
-    if "escape_method" in o:                               # 0 auto, 1 Lanczos, 2 block eigen-solver also below its size threshold
-        h.set_option("escape_method", int(o["escape_method"]))
-    if escape_rr:
-        h.set_option("escape_rr", escape_rr)
-    for name, value in (o.get("device_options") or {}).items():     # run-time switches of the handle (msdp_set_option): A/B runs, tests
-        h.set_option(name, int(value))
-    topts = _rtr_opts(o)
-    p = int(o["p0"])
+
+    def setup():
+        # options['comm'] = (nranks, rank, unique_id): rows of the factor and of C sharded over the ranks (msdp_comm_init); the
+        # host loop then runs replicated -- same start point (pass Y0 or seed rng identically), same data, same decisions on
+        # every rank; the escape runs replicated on a full copy of the sparse C (device eigen-solver only)
+        if comm is not None:
+            if not (sp.issparse(Csp) or isinstance(C, SyntheticDenseC)):
+                raise ValueError("row-sharded solves need a sparse C or a problems.SyntheticDenseC")
+            _join_comm(h, comm)
+            if o.get("halo_exchange"):                     # only the rows this rank's rows of C reference travel before S*U
+                h.set_option("halo_exchange", 1)
+        if "escape_method" in o:                           # 0 auto, 1 Lanczos, 2 block eigen-solver also below its size threshold
+            h.set_option("escape_method", int(o["escape_method"]))
+        if escape_rr:
+            h.set_option("escape_rr", escape_rr)
+        _set_device_options(h, o)
+
+    def finish(run):
+        if eig_mode == "device":
+            run.data["escape_rr_stages"] = h.ritz_stages()     # Rayleigh-Ritz stages: (device, host, host after fallback)
+        if rounding is not None and run.obj is not None:       # options["round"]: +1/-1 vectors from the evaluated point
+            trials, sweeps, seed = rounding
+            h.set_point(run.Y)
+            res = h.round_hyperplane(np.random.default_rng(seed).standard_normal((trials, run.Y.shape[1])), sweeps=sweeps)
+            run.data["round"] = {"x": res["x"], "value": float(res["values"][res["best"]]), "values": res["values"],
+                                 "best": res["best"], "info": res["info"]}
+
     Y = o.get("Y0", None)
     if Y is None:                                          # trustregions.m:390-392 -> M.rand()
-        Y = rng.standard_normal((n, p))
+        Y = rng.standard_normal((n, int(o["p0"])))
         Y /= np.sqrt(np.sum(Y * Y, axis=1, keepdims=True))
     Y = np.ascontiguousarray(Y, dtype=np.float64)
-    U = None
-    data = {"status": 0, "hessvecs": 0, "cost_evals": 0, "rejected": 0, "rtr_seconds": 0.0,
-            "eig_seconds": 0.0, "log": []}
-    t0 = time.time()
-    dinf0 = None
-    obj = dinf = gradnorm = None
-    z = S = None
-    certified = True
-    last_verified = True
     # Rank decision, rank cut and widening of the factor on the device (msdp_factor_gram / _rotate / _append): the factor
     # stays resident between the trustregions() calls and comes to the host once, when the solve ends.  Default with the
     # device escape (large n); the line-search variant keeps the host form (its direction U is a host array anyway).
     device_factor = bool(o.get("device_factor", eig_mode == "device" and o["line_search"] != 1))
-    resident = False
-    try:
-        for it in range(1, int(o["AL_maxiter"]) + 1):      # :38
-            if not resident:
-                h.set_point(Y)
-            if U is not None:                              # :40-42 line_search
-                _line_search(h, U)
-            st = h.rtr(topts)                              # :43
-            data["rtr_seconds"] += st.seconds
-            data["hessvecs"] += st.hessvecs
-            data["cost_evals"] += st.cost_evals
-            data["rejected"] += st.rejected
-            gradnorm = st.gradnorm                         # :44
-            if not device_factor:
-                Y = (h.get_point_all() if comm is not None else h.get_point())
-                Y_eval = Y                                 # X = Y'*Y of :45 -- what the reference returns (:86)
-            z = h.get_z_all() if comm is not None else h.get_z()    # :46-47  z = sum((Y*C).*Y)
-            obj = float(np.sum(z))                         # :48
-            t1 = time.time()
-            certified = True
-            if eig_mode == "host":
-                S = (Csp - sp.diags(z)) if sp.issparse(Csp) else (Csp - np.diag(z))   # :49
-                dS, vS, nneg = _extreme_eigs_host(S, int(o["delta"]), dense_max)     # :50
-                lam_min, lam_max = dS[0], dS[-1]
-            elif eig_mode == "host_sparse":
-                # diagnostic: ARPACK shift-invert on the host (sparse LU of S - sigma I), k bottom eigenpairs
-                import scipy.sparse.linalg as spla
-                S = (Csp - sp.diags(z)).tocsc()
-                k = int(o["delta"])
-                lam_max = float(spla.eigsh(S, k=1, which="LA", return_eigenvectors=False, tol=1e-6)[0])
-                lam, vS = spla.eigsh(S, k=k, sigma=-1e-3 - 0.0 * lam_max, which="LM", tol=1e-12)
-                order = np.argsort(lam); lam = lam[order]; vS = vS[:, order]
-                lam_min = lam[0]
-                nneg = int(np.sum(lam < 0))
-            else:
-                k = int(o["delta"])
-                lam, vS, lam_max, _, certified = _device_escape(
-                    h, lambda tol, maxit: h.escape_eigs(k, tol=tol, maxit=maxit), o, data, 1e-9, 60000)
-                lam_min = lam[0]
-                nneg = int(np.sum(lam < 0))            # missing pairs come back as +inf
-                S = None
-                data["escape_method"] = h.escape_method()      # 1: block eigen-solver, 0: Lanczos
-            data["eig_seconds"] += time.time() - t1
-            dinf = max(0.0, -lam_min) / (1.0 + lam_max)    # :51
-            last_verified = eig_mode != "device"
-            # the regular escape call is warm-started (columns of Y and the previous call's vectors in its start block, or
-            # span(Y) deflated): before dinf may end the solve -- always, the estimate of the same call is never taken as a
-            # certificate -- lambda_min is recomputed by a cold-started, undeflated run
-            if eig_mode == "device" and certified and (dinf < o["tol"] or it == int(o["AL_maxiter"])):
-                last_verified = True
-                lam_v, v_v, lmax_v, certified = _verify_lambda_min(
-                    h, lambda tol, maxit: h.escape_eigs(1, tol=tol, maxit=maxit), o, data, 1e-9, 60000)
-                dinf_v = max(0.0, -lam_v) / (1.0 + lmax_v)
-                if dinf_v >= o["tol"] > dinf:              # the deflated run had missed the bottom of the spectrum
-                    vS = np.hstack([v_v, vS[:, :max(int(o["delta"]) - 1, 0)]])
-                    nneg = max(nneg, 1)
-                dinf = dinf_v
-            if device_factor:
-                Q, e, r = _thin_svd_rank(None, float(o["theta"]), gram=h.factor_gram())   # :52-54 from the device's Gram matrix
-            else:
-                Q, e, r = _thin_svd_rank(Y, float(o["theta"]))  # :52-54
-            _say(verbose, "Iter %d, obj:%0.8f, dinf:%0.1e, r:%d, p:%d, time:%0.2fs"
-                 % (it, obj, dinf, r, p, time.time() - t0))
-            data["log"].append((it, obj, dinf, r, p, time.time() - t0, st.hessvecs))
-            data["iters"] = it
-            if dinf < o["tol"] and certified:              # :57-60 (an unconverged Lanczos run certifies nothing)
-                _say(verbose, "Optimality is reached!")
-                if device_factor:
-                    Y_eval = (h.get_point_all() if comm is not None else h.get_point())
-                break
-            if it % 20 == 0:                               # :61-69
-                if it > 50 and dinf > dinf0:
-                    data["status"] = 2
-                    _say(verbose, "Slow progress!")
-                    if device_factor:
-                        Y_eval = (h.get_point_all() if comm is not None else h.get_point())
-                    break
-                dinf0 = dinf
-            nne = max(min(nneg, int(o["delta"])), 1)       # :74
-            if device_factor:
-                if it == int(o["AL_maxiter"]):
-                    Y_eval = (h.get_point_all() if comm is not None else h.get_point())                 # last pass: the evaluated point, before it is re-shaped
-                try:
-                    if r <= p - 1:                         # :70-73
-                        h.factor_rotate(Q[:, :r])
-                        p = r
-                    h.factor_append(vS[:, :nne], float(o["alpha"]), normalize=True)   # :78-83
-                    p = p + nne
-                    resident = True
-                    continue
-                except _lib.MsdpError as err:              # wider than the handle's buffers: re-enter through set_point
-                    if "allocated capacity" not in str(err):
-                        raise
-                    Y = (h.get_point_all() if comm is not None else h.get_point())                      # the factor as the device holds it (already cut)
-                    Y = np.hstack([Y, o["alpha"] * vS[:, :nne]])
-                    Y = np.ascontiguousarray(Y / np.sqrt(np.sum(Y * Y, axis=1, keepdims=True)))
-                    p = Y.shape[1]
-                    resident = False
-                    continue
-            if r <= p - 1:                                 # :70-73
-                Y = _rank_cut(Y, Q, e, r)
-                p = r
-            if o["line_search"] == 1:                      # :75-77
-                U = np.hstack([np.zeros((n, p)), vS[:, :nne]])
-            p = p + nne                                    # :78
-            if o["line_search"] == 1:
-                Y = np.hstack([Y, np.zeros((n, nne))])     # :80
-            else:
-                Y = np.hstack([Y, o["alpha"] * vS[:, :nne]])   # :82
-                Y = Y / np.sqrt(np.sum(Y * Y, axis=1, keepdims=True))   # :83
-            Y = np.ascontiguousarray(Y)
-        if obj is not None and not last_verified and certified:   # a solve that stopped on "Slow progress": report the true dinf
-            lam_v, _, lmax_v, certified = _verify_lambda_min(
-                h, lambda tol, maxit: h.escape_eigs(1, tol=tol, maxit=maxit), o, data, 1e-9, 60000)
-            dinf = max(0.0, -lam_v) / (1.0 + lmax_v)
-        if eig_mode == "device":
-            data["escape_rr_stages"] = h.ritz_stages()         # Rayleigh-Ritz stages: (device, host, host after fallback)
-        if rounding is not None and obj is not None:           # options["round"]: +1/-1 vectors from the evaluated point
-            trials, sweeps, seed = rounding
-            h.set_point(Y_eval)
-            res = h.round_hyperplane(np.random.default_rng(seed).standard_normal((trials, Y_eval.shape[1])), sweeps=sweeps)
-            data["round"] = {"x": res["x"], "value": float(res["values"][res["best"]]), "values": res["values"],
-                             "best": res["best"], "info": res["info"]}
-    finally:
-        h.close()
-    if obj is not None:
-        Y = Y_eval          # the point the residues belong to (the loop's last pass has already widened its own copy)
+    get_z = h.get_z_all if comm is not None else h.get_z    # :46-47  z = sum((Y*C).*Y)
+    kind = _Manifold(
+        evaluate=lambda blocks: _obj_sum_z(get_z()),       # :48
+        host_S=lambda z, Lam: (Csp - sp.diags(z)) if sp.issparse(Csp) else (Csp - np.diag(z)),   # :49
+        fetch=h.get_point_all if comm is not None else h.get_point, normalise=_rows,
+        device=(h.factor_gram, h.factor_rotate, lambda V, alpha: h.factor_append(V, alpha, normalize=True)) if device_factor else None,
+        setup=setup, finish=finish, verify_at_end=True, reshape_last=True, line_search=o["line_search"] == 1 and not device_factor)
+    run = _manifold_loop(h, o, kind, Y, int(o["p0"]), eig_mode, verbose)
+    Y, z, S, data = run.Y, run.z, run.S, run.data
     if S is None and Csp is not None and sp.issparse(Csp) and z is not None:
         S = Csp - sp.diags(z)                              # :49 (kept sparse; the reference returns full(S))
     if S is None and isinstance(C, SparsePlusLowRank) and z is not None and n <= dense_X_max:
         S = C.toarray() - np.diag(z)                       # the implicit C is formed only below dense_X_max (None above)
-    data.update({"Y": Y, "S": S, "z": z, "dinf": dinf, "gradnorm": gradnorm,
-                 "time": time.time() - t0, "p": Y.shape[1],
+    data.update({"Y": Y, "S": S, "z": z, "dinf": run.dinf, "gradnorm": run.gradnorm,
+                 "time": time.time() - run.t0, "p": Y.shape[1],
                  "X": (Y @ Y.T if n <= dense_X_max else None)})   # :45,86
-    if data["status"] == 0 and (dinf > o["tol"] or not certified):   # :92-95
-        data["status"] = 1
-        _say(verbose, "Iteration maximum is reached!")
-    _say(verbose, "ManiSDP: optimum = %0.8f, time = %0.2fs" % (obj, time.time() - t0))
-    return Y, obj, data
+    return Y, run.obj, data
 
 
 def _onlyunitdiag_hermitian_impl(C, o, verbose, rng):
@@ -551,7 +439,8 @@ def _onlyunitdiag_hermitian_impl(C, o, verbose, rng):
     library call.  Extra option fields: ``hermitian_factor`` ("host" | "device": the rank decision, the cut and the widening through
     msdp_hfactor_gram / _rotate / _append, the factor resident between the trustregions() calls) and ``round_phases`` = {"M",
     "trials", "sweeps", "seed"} (msdp_round_phases on the evaluated point: ``data["round"]`` = z, value, values, best, info, and k
-    for M >= 2)."""
+    for M >= 2).  ``data["factor_seconds"]``: what the factor costs between the trustregions() calls -- its transfers (after the
+    first upload), the rank decision, the cut and the widening."""
     Csp = _lib.hermitian_csc(sp.csc_matrix(C) if not sp.issparse(C) else C).tocsr()   # ValueError unless C == C^H exactly
     for name, what in (("round", "+1/-1 rounding belongs to the real problem"), ("comm", "a single-rank solve is needed")):
         if o.get(name) is not None:
@@ -562,152 +451,45 @@ def _onlyunitdiag_hermitian_impl(C, o, verbose, rng):
         raise ValueError("options['device_factor'] is not available for a complex Hermitian C: its device re-shaping is options['hermitian_factor'] = 'device'")
     rounding = _round_phases_option(o)
     device_factor = _hermitian_factor_option(o) == "device"
-    dense_max = int(o.get("dense_eig_max", 3000))
-    dense_default = int(o.get("dense_eig_default", 600))
     dense_X_max = int(o.get("dense_X_max", 4000))
     rng = rng or np.random.default_rng(0)
     n = Csp.shape[0]
-    eig_mode = o.get("eig", "host" if n <= dense_default else "device")
+    eig_mode = o.get("eig", "host" if n <= int(o.get("dense_eig_default", 600)) else "device")
     if eig_mode not in ("host", "device"):
         raise ValueError(f"options['eig'] must be 'host' or 'device' for a complex Hermitian C, not {eig_mode!r}")
     _say(verbose, "ManiSDP is starting...")
     _say(verbose, f"SDP size: n = {n}, m = {n} (complex Hermitian)")
     p = int(o["p0"])
-    delta = int(o["delta"])
     Y = o.get("Y0", None)
     if Y is None:
         Y = rng.standard_normal((n, p)) + 1j * rng.standard_normal((n, p))
         Y /= np.sqrt(np.sum(np.abs(Y) ** 2, axis=1, keepdims=True))
     Y = np.ascontiguousarray(Y, dtype=np.complex128)
     p = Y.shape[1]
-    h = _lib.Handle.onlyunitdiag_hermitian(Csp, pcap=max(32, p + 2 * delta))
-    for name, value in (o.get("device_options") or {}).items():
-        h.set_option(name, int(value))
-    topts = _rtr_opts(o)
-    # factor_seconds: what the factor costs between the trustregions() calls -- its transfers (after the first upload), the rank
-    # decision, the cut and the widening
-    data = {"status": 0, "hessvecs": 0, "cost_evals": 0, "rejected": 0, "rtr_seconds": 0.0, "eig_seconds": 0.0, "factor_seconds": 0.0,
-            "log": []}
-    t0 = time.time()
-    dinf0 = None
-    obj = dinf = gradnorm = z = None
-    certified = True
-    Y_eval = Y
-    # options["hermitian_factor"] = "device": the rank decision, the cut and the widening on the device (msdp_hfactor_gram /
-    # _rotate / _append); the factor stays resident between the trustregions() calls and comes to the host once, when the loop
-    # ends -- the device_factor branch of _onlyunitdiag_impl
-    resident = False
-    try:
-        for it in range(1, int(o["AL_maxiter"]) + 1):      # :38
-            if not resident:
-                t2 = time.time()
-                h.set_point(Y)
-                if it > 1:
-                    data["factor_seconds"] += time.time() - t2
-            st = h.rtr(topts)                              # :43
-            data["rtr_seconds"] += st.seconds
-            data["hessvecs"] += st.hessvecs
-            data["cost_evals"] += st.cost_evals
-            data["rejected"] += st.rejected
-            gradnorm = st.gradnorm
-            if not device_factor:
-                t2 = time.time()
-                Y = h.get_point()
-                Y_eval = Y
-                data["factor_seconds"] += time.time() - t2
-            z = h.get_z()                                  # :46-47  z = Re sum((C Y) .* conj(Y), 2)
-            obj = float(np.sum(z))
-            t1 = time.time()
-            certified = True
-            if eig_mode == "host":
-                dS, vS, nneg = _extreme_eigs_host(Csp - sp.diags(z), delta, dense_max)    # eigh of the complex S
-                lam_min, lam_max = dS[0], dS[-1]
-            else:
-                lam, vS, lam_max, _, certified = _device_escape(
-                    h, lambda tol, maxit: h.escape_eigs(delta, tol=tol, maxit=maxit), o, data, 1e-9, 60000)
-                lam_min = lam[0]
-                nneg = int(np.sum(lam < 0))
-                data["escape_method"] = h.escape_method()
-            data["eig_seconds"] += time.time() - t1
-            dinf = max(0.0, -lam_min) / (1.0 + lam_max)    # :51
-            if eig_mode == "device" and certified and (dinf < o["tol"] or it == int(o["AL_maxiter"])):
-                lam_v, v_v, lmax_v, certified = _verify_lambda_min(
-                    h, lambda tol, maxit: h.escape_eigs(1, tol=tol, maxit=maxit), o, data, 1e-9, 60000)
-                dinf_v = max(0.0, -lam_v) / (1.0 + lmax_v)
-                if dinf_v >= o["tol"] > dinf:
-                    vS = np.hstack([v_v, vS[:, :max(delta - 1, 0)]])
-                    nneg = max(nneg, 1)
-                dinf = dinf_v
-            t2 = time.time()
-            Q, e, r = _thin_svd_rank(None, float(o["theta"]), gram=h.hfactor_gram() if device_factor else Y.conj().T @ Y)   # :52-54 from Y^H Y
-            data["factor_seconds"] += time.time() - t2
-            _say(verbose, "Iter %d, obj:%0.8f, dinf:%0.1e, r:%d, p:%d, time:%0.2fs" % (it, obj, dinf, r, p, time.time() - t0))
-            data["log"].append((it, obj, dinf, r, p, time.time() - t0, st.hessvecs))
-            data["iters"] = it
-            if dinf < o["tol"] and certified:              # :57-60
-                _say(verbose, "Optimality is reached!")
-                if device_factor:
-                    Y_eval = h.get_point()
-                break
-            if it % 20 == 0:                               # :61-69
-                if it > 50 and dinf > dinf0:
-                    data["status"] = 2
-                    _say(verbose, "Slow progress!")
-                    if device_factor:
-                        Y_eval = h.get_point()
-                    break
-                dinf0 = dinf
-            nne = max(min(nneg, delta), 1)                 # :74
-            if device_factor:
-                if it == int(o["AL_maxiter"]):
-                    Y_eval = h.get_point()                 # last pass: the evaluated point, before it is re-shaped
-                t2 = time.time()
-                try:
-                    if r <= p - 1:                         # :70-73
-                        h.hfactor_rotate(Q[:, :r])
-                        p = r
-                    h.hfactor_append(vS[:, :nne], float(o["alpha"]))   # :78-83
-                    p = p + nne
-                    resident = True
-                    data["factor_seconds"] += time.time() - t2
-                    continue
-                except _lib.MsdpError as err:              # wider than the handle's buffers: re-enter through set_point
-                    if "allocated capacity" not in str(err):
-                        raise
-                    Y = h.get_point()                      # the factor as the device holds it (already cut)
-                    Y = np.hstack([Y, o["alpha"] * vS[:, :nne]])
-                    Y = np.ascontiguousarray(Y / np.sqrt(np.sum(np.abs(Y) ** 2, axis=1, keepdims=True)))
-                    p = Y.shape[1]
-                    resident = False
-                    data["factor_seconds"] += time.time() - t2
-                    continue
-            t2 = time.time()
-            if r <= p - 1:                                 # :70-73
-                Y = _rank_cut(Y, Q, e, r)
-                p = r
-            Y = np.hstack([Y, o["alpha"] * vS[:, :nne]])   # :78-83
-            Y = np.ascontiguousarray(Y / np.sqrt(np.sum(np.abs(Y) ** 2, axis=1, keepdims=True)))
-            p = p + nne
-            data["factor_seconds"] += time.time() - t2
-        if rounding is not None and obj is not None:           # options["round_phases"]: phases from the evaluated point
+    h = _lib.Handle.onlyunitdiag_hermitian(Csp, pcap=max(32, p + 2 * int(o["delta"])))
+
+    def finish(run):
+        if rounding is not None and run.obj is not None:       # options["round_phases"]: phases from the evaluated point
             M, trials, sweeps, seed = rounding
-            h.set_point(Y_eval)
-            res = h.round_phases(_draw_phase_R(np.random.default_rng(seed), trials, Y_eval.shape[1]), M=M, sweeps=sweeps)
-            data["round"] = {"z": res["z"], "value": float(res["values"][res["best"]]), "values": res["values"],
-                             "best": res["best"], "info": res["info"]}
+            h.set_point(run.Y)
+            res = h.round_phases(_draw_phase_R(np.random.default_rng(seed), trials, run.Y.shape[1]), M=M, sweeps=sweeps)
+            run.data["round"] = {"z": res["z"], "value": float(res["values"][res["best"]]), "values": res["values"],
+                                 "best": res["best"], "info": res["info"]}
             if M:
-                data["round"]["k"] = res["k"]
-    finally:
-        h.close()
-    Y = Y_eval
-    data.update({"Y": Y, "S": (Csp - sp.diags(z)) if z is not None else None, "z": z, "dinf": dinf, "gradnorm": gradnorm,
-                 "time": time.time() - t0, "p": Y.shape[1], "X": (Y @ Y.conj().T if n <= dense_X_max else None)})
-    if data["status"] == 0 and (dinf is None or dinf > o["tol"] or not certified):
-        data["status"] = 1
-        _say(verbose, "Iteration maximum is reached!")
-    if obj is not None:
-        _say(verbose, "ManiSDP: optimum = %0.8f, time = %0.2fs" % (obj, time.time() - t0))
-    return Y, obj, data
+                run.data["round"]["k"] = res["k"]
+
+    kind = _Manifold(
+        evaluate=lambda blocks: _obj_sum_z(h.get_z()),     # :46-48  z = Re sum((C Y) .* conj(Y), 2)
+        host_S=lambda z, Lam: Csp - sp.diags(z),           # (eigh of the complex S)
+        fetch=h.get_point, normalise=_rows_complex, host_gram=lambda Y: Y.conj().T @ Y,   # :52-54 from Y^H Y
+        device=(h.hfactor_gram, h.hfactor_rotate, h.hfactor_append) if device_factor else None,
+        setup=lambda: _set_device_options(h, o), finish=finish, reshape_last=True)
+    run = _manifold_loop(h, o, kind, Y, p, eig_mode, verbose)
+    Y, z, data = run.Y, run.z, run.data
+    data.update({"Y": Y, "S": (Csp - sp.diags(z)) if z is not None else None, "z": z, "dinf": run.dinf, "gradnorm": run.gradnorm,
+                 "factor_seconds": run.factor_seconds,
+                 "time": time.time() - run.t0, "p": Y.shape[1], "X": (Y @ Y.conj().T if n <= dense_X_max else None)})
+    return Y, run.obj, data
 
 
 # =============================================================== onlyunitblockdiag
@@ -729,40 +511,6 @@ def _block_factor_option(o, what):
     if mode not in ("host", "device"):
         raise ValueError(f"options['block_factor'] must be 'host' or 'device' for the {what} problem, not {mode!r}")
     return mode
-
-
-def _block_reshape_device(h, d, polar, Q, e, r, p, vS, nne, alpha, data):
-    """The re-shape of a block kind's factor between two trustregions() calls on the device (msdp_blockfactor_rotate /
-    _append): the cut to r columns where d <= r <= p - 1, then the widening by alpha vS(:, 1:nne), the blocks re-orthonormalised
-    by the same launches.  Returns (None, p) with the new point resident.  A call that reports degenerate blocks (it has not
-    changed the point) or exceeds the handle's capacity hands this iteration to the host: the factor comes down as the device
-    holds it (cut or not), takes today's host steps with `polar`, and (Y, p) is returned for set_point."""
-    cut = d <= r <= p - 1
-    cut_done = False
-    ok = True
-    try:
-        if cut:
-            ok = h.blockfactor_rotate(Q[:, :r]) == 0
-            if ok:
-                cut_done = True
-                p = r
-                data["factor_device_calls"] += 1
-        if ok:
-            if p + nne > 256:
-                raise RuntimeError(f"the factor width would exceed the device's 256 columns (p = {p}, {nne} more)")
-            ok = h.blockfactor_append(vS[:, :nne], alpha) == 0
-            if ok:
-                data["factor_device_calls"] += 1
-                return None, p + nne
-    except _lib.MsdpError as err:                          # wider than the handle's buffers: re-enter through set_point
-        if "allocated capacity" not in str(err):
-            raise
-    data["factor_host_fallbacks"] += 1
-    Y = h.get_point()
-    if cut and not cut_done:
-        Y = polar(_rank_cut(Y, Q, e, r), d)
-    Y = polar(np.hstack([Y, alpha * vS[:, :nne]]), d)
-    return Y, Y.shape[1]
 
 
 def _round_blocks_option(h, d, Y_eval, data):
@@ -810,6 +558,30 @@ def ManiSDP_onlyunitblockdiag(C, d, options=None, verbose=True, rng=None):
         return _onlyunitblockdiag_impl(C, d, options, verbose, rng)
 
 
+def _block_kind(h, o, d, device, evaluate, host_S, polar, setup, rerun=False):
+    """The _Manifold of the two block kinds: what differs between them is how a point is evaluated, the host S, which rows the
+    polar factors re-orthonormalise, the options of the set-up, and the pose-graph kind's rerun."""
+    def finish(run):
+        if run.obj is None:
+            return
+        if device:                                         # the multiplier blocks once, at the evaluated point
+            run.Lam = h.get_blockmult()
+        if o.get("round_blocks"):
+            _round_blocks_option(h, d, run.Y, run.data)
+
+    return _Manifold(evaluate=evaluate, host_S=host_S, fetch=h.get_point, normalise=lambda Y: polar(Y, d),
+                     device=(h.blockfactor_gram, h.blockfactor_rotate, h.blockfactor_append) if device else None,
+                     setup=setup, finish=finish, min_rank=d, polar_cut=True, max_width=256, rerun=rerun)
+
+
+def _block_kind_data(run, S, N, dense_X_max):
+    """The data fields the two block kinds share."""
+    Y = run.Y
+    return {"Y": Y, "S": S, "z": run.z, "Lambda": run.Lam, "dinf": run.dinf, "gradnorm": run.gradnorm, "rank": run.r,
+            "factor_device_calls": run.device_calls, "factor_host_fallbacks": run.host_fallbacks, "factor_seconds": run.factor_seconds,
+            "time": time.time() - run.t0, "p": Y.shape[1], "X": (Y @ Y.T if N <= dense_X_max else None)}
+
+
 def _onlyunitblockdiag_impl(C, d, options, verbose, rng):
     d = int(d)
     if d not in (2, 3):
@@ -831,16 +603,13 @@ def _onlyunitblockdiag_impl(C, d, options, verbose, rng):
     device = _block_factor_option(o, "unit-block-diagonal") == "device"
     if C.shape[0] != C.shape[1] or C.shape[0] % d:
         raise ValueError(f"the cost matrix must be square of an order that is a multiple of d = {d}, not {C.shape}")
-    dense_max = int(o.get("dense_eig_max", 3000))
-    dense_default = int(o.get("dense_eig_default", 600))
     dense_X_max = int(o.get("dense_X_max", 4000))
     N = C.shape[0]
     nb = N // d
-    eig_mode = o.get("eig", "host" if N <= dense_default else "device")
+    eig_mode = o.get("eig", "host" if N <= int(o.get("dense_eig_default", 600)) else "device")
     if eig_mode not in ("host", "device"):
         raise ValueError(f"options['eig'] must be 'host' or 'device' for the unit-block-diagonal problem, not {eig_mode!r}")
     p = int(o["p0"])
-    delta = int(o["delta"])
     Y = o.get("Y0", None)
     if Y is None and p < d:
         raise ValueError(f"options['p0'] = {p} is below the block order d = {d}")
@@ -855,119 +624,24 @@ def _onlyunitblockdiag_impl(C, d, options, verbose, rng):
         Y = Y.reshape(N, p)
     Y = np.ascontiguousarray(Y, dtype=np.float64)
     p = Y.shape[1]
-    h = _lib.Handle.onlyunitblockdiag(Csp, d, pcap=min(256, max(32, p + 2 * delta)))
-    if o.get("block_persist"):                             # the tCG of a TR iteration in one persistent launch where it applies
-        h.set_option("block_persist", 1)
-    for name, value in (o.get("device_options") or {}).items():
-        h.set_option(name, int(value))
-    topts = _rtr_opts(o)
-    data = {"status": 0, "hessvecs": 0, "cost_evals": 0, "rejected": 0, "rtr_seconds": 0.0, "eig_seconds": 0.0, "log": [],
-            "factor_device_calls": 0, "factor_host_fallbacks": 0, "factor_seconds": 0.0}
-    t0 = time.time()
-    dinf0 = None
-    obj = dinf = gradnorm = z = Lam = r = None
-    certified = True
-    Y_eval = Y
-    # options["block_factor"] = "device": the factor stays resident between the trustregions() calls (msdp_blockfactor_gram /
-    # _rotate / _append) and comes to the host once, when the loop ends -- the device_factor branch of _onlyunitdiag_impl
-    resident = False
-    last_it = int(o["AL_maxiter"])
-    try:
-        for it in range(1, last_it + 1):
-            if not resident:
-                tf = time.time()
-                h.set_point(Y)
-                if it > 1:                                 # part of a re-shape on the host
-                    data["factor_seconds"] += time.time() - tf
-            st = h.rtr(topts)
-            data["rtr_seconds"] += st.seconds
-            data["hessvecs"] += st.hessvecs
-            data["cost_evals"] += st.cost_evals
-            data["rejected"] += st.rejected
-            gradnorm = st.gradnorm
-            if not device:
-                tf = time.time()
-                Y = h.get_point()
-                data["factor_seconds"] += time.time() - tf
-                Y_eval = Y
-            if not device or eig_mode == "host":
-                Lam = h.get_blockmult()                    # Lambda_i = sym((C Y)_i Y_i')
-                z = np.ascontiguousarray(np.diagonal(Lam, axis1=1, axis2=2)).ravel()
-            else:
-                z = h.get_z()                              # the diagonals alone; the blocks once, at the end
-            obj = float(np.sum(z))
-            t1 = time.time()
-            certified = True
-            if eig_mode == "host":
-                dS, vS, nneg = _extreme_eigs_host(Csp - sp.block_diag(list(Lam), format="csr"), delta, dense_max)
-                lam_min, lam_max = dS[0], dS[-1]
-            else:
-                lam, vS, lam_max, _, certified = _device_escape(
-                    h, lambda tol, maxit: h.escape_eigs(delta, tol=tol, maxit=maxit), o, data, 1e-9, 60000)
-                lam_min = lam[0]
-                nneg = int(np.sum(lam < 0))
-                data["escape_method"] = h.escape_method()
-            data["eig_seconds"] += time.time() - t1
-            dinf = max(0.0, -lam_min) / (1.0 + lam_max)
-            if eig_mode == "device" and certified and (dinf < o["tol"] or it == int(o["AL_maxiter"])):
-                lam_v, v_v, lmax_v, certified = _verify_lambda_min(
-                    h, lambda tol, maxit: h.escape_eigs(1, tol=tol, maxit=maxit), o, data, 1e-9, 60000)
-                dinf_v = max(0.0, -lam_v) / (1.0 + lmax_v)
-                if dinf_v >= o["tol"] > dinf:
-                    vS = np.hstack([v_v, vS[:, :max(delta - 1, 0)]])
-                    nneg = max(nneg, 1)
-                dinf = dinf_v
-            tf = time.time()
-            if device:
-                Q, e, r = _thin_svd_rank(None, float(o["theta"]), gram=h.blockfactor_gram())
-            else:
-                Q, e, r = _thin_svd_rank(Y, float(o["theta"]))
-            data["factor_seconds"] += time.time() - tf
-            _say(verbose, "Iter %d, obj:%0.8f, dinf:%0.1e, r:%d, p:%d, time:%0.2fs" % (it, obj, dinf, r, p, time.time() - t0))
-            data["log"].append((it, obj, dinf, r, p, time.time() - t0, st.hessvecs))
-            data["iters"] = it
-            if dinf < o["tol"] and certified:
-                _say(verbose, "Optimality is reached!")
-                break
-            if it % 20 == 0:
-                if it > 50 and dinf > dinf0:
-                    data["status"] = 2
-                    _say(verbose, "Slow progress!")
-                    break
-                dinf0 = dinf
-            if device and it == last_it:                   # last pass: the evaluated point stays resident, nothing to re-shape for
-                break
-            nne = max(min(nneg, delta), 1)
-            tf = time.time()
-            if device:
-                Y, p = _block_reshape_device(h, d, _polar_blocks, Q, e, r, p, vS, nne, float(o["alpha"]), data)
-                resident = Y is None
-                data["factor_seconds"] += time.time() - tf
-                continue
-            if d <= r <= p - 1:                            # never below the block order: d orthonormal rows need d columns
-                Y = _polar_blocks(_rank_cut(Y, Q, e, r), d)
-                p = r
-            if p + nne > 256:
-                raise RuntimeError(f"the factor width would exceed the device's 256 columns (p = {p}, {nne} more)")
-            Y = _polar_blocks(np.hstack([Y, o["alpha"] * vS[:, :nne]]), d)
-            p = p + nne
-            data["factor_seconds"] += time.time() - tf
-        if device and obj is not None:
-            Y_eval, Lam = h.get_point(), h.get_blockmult()
-        if o.get("round_blocks") and obj is not None:
-            _round_blocks_option(h, d, Y_eval, data)
-    finally:
-        h.close()
-    Y = Y_eval
-    S = (Csp - sp.block_diag(list(Lam), format="csr")) if Lam is not None else None
-    data.update({"Y": Y, "S": S, "z": z, "Lambda": Lam, "dinf": dinf, "gradnorm": gradnorm, "rank": r,
-                 "time": time.time() - t0, "p": Y.shape[1], "X": (Y @ Y.T if N <= dense_X_max else None)})
-    if data["status"] == 0 and (dinf is None or dinf > o["tol"] or not certified):
-        data["status"] = 1
-        _say(verbose, "Iteration maximum is reached!")
-    if obj is not None:
-        _say(verbose, "ManiSDP: optimum = %0.8f, time = %0.2fs" % (obj, time.time() - t0))
-    return Y, obj, data
+    h = _lib.Handle.onlyunitblockdiag(Csp, d, pcap=min(256, max(32, p + 2 * int(o["delta"]))))
+
+    def setup():
+        if o.get("block_persist"):                         # the tCG of a TR iteration in one persistent launch where it applies
+            h.set_option("block_persist", 1)
+        _set_device_options(h, o)
+
+    def evaluate(blocks):
+        if not blocks:
+            return _obj_sum_z(h.get_z())                   # the diagonals alone; the blocks once, at the end
+        Lam = h.get_blockmult()                            # Lambda_i = sym((C Y)_i Y_i')
+        z = np.ascontiguousarray(np.diagonal(Lam, axis1=1, axis2=2)).ravel()
+        return z, Lam, float(np.sum(z)), None
+
+    host_S = lambda z, Lam: Csp - sp.block_diag(list(Lam), format="csr")
+    run = _manifold_loop(h, o, _block_kind(h, o, d, device, evaluate, host_S, _polar_blocks, setup), Y, p, eig_mode, verbose)
+    run.data.update(_block_kind_data(run, host_S(None, run.Lam) if run.Lam is not None else None, N, dense_X_max))
+    return run.Y, run.obj, run.data
 
 
 # =============================================================== posegraph
@@ -1044,16 +718,13 @@ def _posegraph_impl(C, d, options, verbose, rng):
     device = _block_factor_option(o, "pose-graph") == "device"
     if C.shape[0] != C.shape[1] or C.shape[0] % B:
         raise ValueError(f"the cost matrix must be square of an order that is a multiple of d + 1 = {B}, not {C.shape}")
-    dense_max = int(o.get("dense_eig_max", 3000))
-    dense_default = int(o.get("dense_eig_default", 600))
     dense_X_max = int(o.get("dense_X_max", 4000))
     N = C.shape[0]
     nb = N // B
-    eig_mode = o.get("eig", "host" if N <= dense_default else "device")
+    eig_mode = o.get("eig", "host" if N <= int(o.get("dense_eig_default", 600)) else "device")
     if eig_mode not in ("host", "device"):
         raise ValueError(f"options['eig'] must be 'host' or 'device' for the pose-graph problem, not {eig_mode!r}")
     p = int(o["p0"])
-    delta = int(o["delta"])
     Y = o.get("Y0", None)
     if Y is None and p < d:
         raise ValueError(f"options['p0'] = {p} is below the dimension d = {d}")
@@ -1068,129 +739,28 @@ def _posegraph_impl(C, d, options, verbose, rng):
         Y = Y.reshape(N, p)
     Y = np.ascontiguousarray(Y, dtype=np.float64)
     p = Y.shape[1]
-    h = _lib.Handle.posegraph(Csp, d, pcap=min(256, max(32, p + 2 * delta)))
-    try:
+    h = _lib.Handle.posegraph(Csp, d, pcap=min(256, max(32, p + 2 * int(o["delta"]))))
+
+    def setup():
         if o.get("block_persist"):                         # the tCG of a TR iteration in one persistent launch where it applies
             h.set_option("block_persist", 1)
         if o.get("precon") == "blockjacobi":               # block-Jacobi preconditioned tCG (msdp_set_option "precon"); a refusal
             h.set_option("precon", 1)                      # (a diagonal block without a Cholesky factor) is the library's own error
-        for name, value in (o.get("device_options") or {}).items():
-            h.set_option(name, int(value))
-    except Exception:
-        h.close()
-        raise
-    topts = _rtr_opts(o)
-    data = {"status": 0, "hessvecs": 0, "cost_evals": 0, "rejected": 0, "rtr_seconds": 0.0, "eig_seconds": 0.0, "log": [],
-            "reruns": 0, "factor_device_calls": 0, "factor_host_fallbacks": 0, "factor_seconds": 0.0}
-    t0 = time.time()
-    dinf0 = None
-    obj = dual = gap = dinf = gradnorm = z = Lam = r = None
-    certified = True
-    Y_eval = Y
-    # options["block_factor"] = "device": as in _onlyunitblockdiag_impl -- one set_point per solve, the factor comes down when the
-    # loop ends; a rerun (below) does not touch it
-    resident = False
-    last_it = int(o["AL_maxiter"])
-    try:
-        for it in range(1, last_it + 1):
-            if not resident:
-                tf = time.time()
-                h.set_point(Y)
-                if it > 1:                                 # part of a re-shape on the host (a rerun uploads the same point again)
-                    data["factor_seconds"] += time.time() - tf
-            st = h.rtr(topts)
-            data["rtr_seconds"] += st.seconds
-            data["hessvecs"] += st.hessvecs
-            data["cost_evals"] += st.cost_evals
-            data["rejected"] += st.rejected
-            gradnorm = st.gradnorm
-            if not device:
-                tf = time.time()
-                Y = h.get_point()
-                data["factor_seconds"] += time.time() - tf
-                Y_eval = Y
-            if not device or eig_mode == "host":
-                Lam = h.get_blockmult()                    # Lambda_i = sym(G_i Y_i'), d x d
-            z = h.get_z()                                  # its diagonals, 0 in the free-row entries
-            dual = float(np.sum(z))
-            obj = 2.0 * h.cost()                           # <C, Y Y'> = dual + sum <g_i, tau_i>
-            gap = abs(obj - dual) / (1.0 + abs(obj) + abs(dual))
-            t1 = time.time()
-            certified = True
-            if eig_mode == "host":
-                dS, vS, nneg = _extreme_eigs_host(Csp - _pad_blocks(Lam), delta, dense_max)
-                lam_min, lam_max = dS[0], dS[-1]
-            else:
-                lam, vS, lam_max, _, certified = _device_escape(
-                    h, lambda tol, maxit: h.escape_eigs(delta, tol=tol, maxit=maxit), o, data, 1e-9, 60000)
-                lam_min = lam[0]
-                nneg = int(np.sum(lam < 0))
-                data["escape_method"] = h.escape_method()
-            data["eig_seconds"] += time.time() - t1
-            dinf = max(0.0, -lam_min) / (1.0 + lam_max)
-            if eig_mode == "device" and certified and (max(dinf, gap) < o["tol"] or it == int(o["AL_maxiter"])):
-                lam_v, v_v, lmax_v, certified = _verify_lambda_min(
-                    h, lambda tol, maxit: h.escape_eigs(1, tol=tol, maxit=maxit), o, data, 1e-9, 60000)
-                dinf_v = max(0.0, -lam_v) / (1.0 + lmax_v)
-                if dinf_v >= o["tol"] > dinf:
-                    vS = np.hstack([v_v, vS[:, :max(delta - 1, 0)]])
-                    nneg = max(nneg, 1)
-                dinf = dinf_v
-            tf = time.time()
-            if device:
-                Q, e, r = _thin_svd_rank(None, float(o["theta"]), gram=h.blockfactor_gram())
-            else:
-                Q, e, r = _thin_svd_rank(Y, float(o["theta"]))
-            data["factor_seconds"] += time.time() - tf
-            _say(verbose, "Iter %d, obj:%0.8f, dinf:%0.1e, gap:%0.1e, r:%d, p:%d, time:%0.2fs" % (it, obj, dinf, gap, r, p, time.time() - t0))
-            data["log"].append((it, obj, dinf, gap, r, p, time.time() - t0, st.hessvecs))
-            data["iters"] = it
-            if max(dinf, gap) < o["tol"] and certified:
-                _say(verbose, "Optimality is reached!")
-                break
-            if it % 20 == 0:
-                if it > 50 and max(dinf, gap) > dinf0:
-                    data["status"] = 2
-                    _say(verbose, "Slow progress!")
-                    break
-                dinf0 = max(dinf, gap)
-            if device and it == last_it:                   # last pass: the evaluated point stays resident, nothing to re-shape for
-                break
-            if dinf < o["tol"] <= gap:                     # S is PSD but the point is not stationary: trustregions() again
-                data["reruns"] += 1
-                resident = device                          # (the device path: on the factor where it is)
-                continue
-            nne = max(min(nneg, delta), 1)
-            tf = time.time()
-            if device:
-                Y, p = _block_reshape_device(h, d, _polar_rotation_rows, Q, e, r, p, vS, nne, float(o["alpha"]), data)
-                resident = Y is None
-                data["factor_seconds"] += time.time() - tf
-                continue
-            if d <= r <= p - 1:                            # never below d: d orthonormal rows need d columns
-                Y = _polar_rotation_rows(_rank_cut(Y, Q, e, r), d)
-                p = r
-            if p + nne > 256:
-                raise RuntimeError(f"the factor width would exceed the device's 256 columns (p = {p}, {nne} more)")
-            Y = _polar_rotation_rows(np.hstack([Y, o["alpha"] * vS[:, :nne]]), d)
-            p = p + nne
-            data["factor_seconds"] += time.time() - tf
-        if device and obj is not None:
-            Y_eval, Lam = h.get_point(), h.get_blockmult()
-        if o.get("round_blocks") and obj is not None:
-            _round_blocks_option(h, d, Y_eval, data)
-    finally:
-        h.close()
-    Y = Y_eval
-    S = (Csp - _pad_blocks(Lam)) if Lam is not None else None
-    data.update({"Y": Y, "S": S, "z": z, "Lambda": Lam, "dinf": dinf, "gap": gap, "dual": dual, "gradnorm": gradnorm, "rank": r,
-                 "time": time.time() - t0, "p": Y.shape[1], "X": (Y @ Y.T if N <= dense_X_max else None)})
-    if data["status"] == 0 and (dinf is None or max(dinf, gap) > o["tol"] or not certified):
-        data["status"] = 1
-        _say(verbose, "Iteration maximum is reached!")
-    if obj is not None:
-        _say(verbose, "ManiSDP: optimum = %0.8f, time = %0.2fs" % (obj, time.time() - t0))
-    return Y, obj, data
+        _set_device_options(h, o)
+
+    def evaluate(blocks):
+        Lam = h.get_blockmult() if blocks else None        # Lambda_i = sym(G_i Y_i'), d x d
+        z = h.get_z()                                      # its diagonals, 0 in the free-row entries
+        dual = float(np.sum(z))
+        obj = 2.0 * h.cost()                               # <C, Y Y'> = dual + sum <g_i, tau_i>
+        return z, Lam, obj, abs(obj - dual) / (1.0 + abs(obj) + abs(dual))
+
+    host_S = lambda z, Lam: Csp - _pad_blocks(Lam)
+    kind = _block_kind(h, o, d, device, evaluate, host_S, _polar_rotation_rows, setup, rerun=True)
+    run = _manifold_loop(h, o, kind, Y, p, eig_mode, verbose)
+    run.data.update(_block_kind_data(run, host_S(None, run.Lam) if run.Lam is not None else None, N, dense_X_max))
+    run.data.update({"gap": run.gap, "dual": float(np.sum(run.z)) if run.z is not None else None, "reruns": run.reruns})
+    return run.Y, run.obj, run.data
 
 
 def _line_search(h, U):
@@ -1206,6 +776,232 @@ def _line_search(h, U):
         val = h.linesearch_cost(U, alpha)
         i += 1
     h.linesearch_accept()
+
+
+def _count_rtr(data, st):
+    """The counters of one trustregions() call, added to those of the solve."""
+    data["rtr_seconds"] += st.seconds
+    data["hessvecs"] += st.hessvecs
+    data["cost_evals"] += st.cost_evals
+    data["rejected"] += st.rejected
+
+
+# ============================================================ one outer loop for the four manifold-only kinds
+# ManiSDP_onlyunitdiag with a real and with a complex Hermitian C, ManiSDP_onlyunitblockdiag and ManiSDP_posegraph have no multipliers
+# and no penalty -- the constraint is the manifold -- and share the loop of ManiSDP_onlyunitdiag.m:38-84: trustregions(), z or Lambda
+# and the objective, lambda_min / lambda_max of S with the independent check, the rank decision, the stop and slow-progress tests,
+# the cut and the widening.  _manifold_loop holds it once; a kind states what is its own in a _Manifold record.
+def _obj_sum_z(z):
+    """The evaluation of the kinds whose objective is the dual value: (z, no multiplier blocks, obj = sum z, no gap)."""
+    return z, None, float(np.sum(z)), None
+
+
+class _Manifold:
+    """What _manifold_loop needs to know of a kind.
+    ``evaluate(blocks)`` -> (z, Lambda or None, obj, gap or None) at the resident point after trustregions(); ``blocks``: the host
+    needs the multiplier blocks of this evaluation (it builds S, or holds the factor).  A kind with a gap ends on max(dinf, gap)
+    and prints it.  ``host_S(z, Lambda)``: S for the host eigen-solver.
+    The factor: ``fetch()`` brings it to the host; ``host_gram(Y)``: its Gram matrix for the rank decision (None: Y'Y);
+    ``normalise(Y)``: back onto the manifold after the widening; ``device``: None = the factor is re-shaped on the host and
+    uploaded before every trustregions() call, else (gram, rotate, append) of the handle = it stays resident and is re-shaped
+    there; rotate / append may answer with a count of degenerate blocks, which means the point is unchanged.
+    ``setup()`` / ``finish(run)``: the handle's options before the loop, the kind's own work at its end (rounding, a last fetch)
+    -- both run under the loop's ``finally: close``.
+    ``min_rank``: the cut happens only for min_rank <= r <= p - 1 (block kinds: d orthonormal rows need d columns).
+    ``polar_cut``: the factor is normalised after the cut as well (block kinds; a cut leaves unit-diagonal rows as they are).
+    ``max_width``: widest factor the handle takes (block kinds: 256), beyond it RuntimeError.
+    ``verify_at_end``: a solve that stopped on "Slow progress" gets the independent lambda_min check once more (real C only).
+    ``reshape_last``: the last pass re-shapes the resident factor like any other (unit-diagonal kinds); False: it stops before.
+    ``rerun``: with dinf < tol <= gap trustregions() runs again on the same factor, no cut, no widening (pose-graph only).
+    ``line_search``: the widening hands its directions to line_search() instead of appending them (real C, host factor only)."""
+
+    def __init__(self, evaluate, host_S, fetch, normalise, host_gram=None, device=None, setup=None, finish=None, min_rank=0,
+                 polar_cut=False, max_width=None, verify_at_end=False, reshape_last=False, rerun=False, line_search=False):
+        self.evaluate, self.host_S, self.fetch, self.normalise, self.host_gram = evaluate, host_S, fetch, normalise, host_gram
+        self.device, self.setup, self.finish, self.min_rank, self.polar_cut, self.max_width = device, setup, finish, min_rank, polar_cut, max_width
+        self.verify_at_end, self.reshape_last, self.rerun, self.line_search = verify_at_end, reshape_last, rerun, line_search
+
+
+_MANIFOLD_LINE = "Iter %d, obj:%0.8f, dinf:%0.1e, r:%d, p:%d, time:%0.2fs"
+_MANIFOLD_LINE_GAP = "Iter %d, obj:%0.8f, dinf:%0.1e, gap:%0.1e, r:%d, p:%d, time:%0.2fs"
+
+
+def _manifold_reshape(k, o, run, Y, p, Q, e, r, vS, nne):
+    """The factor between two trustregions() calls (ManiSDP_onlyunitdiag.m:70-83): cut to r columns where the kind allows it,
+    widened by alpha vS(:, 1:nne) and normalised.  On the device (msdp_factor_* / msdp_hfactor_* / msdp_blockfactor_*) the new
+    point stays resident and (None, None, p) is returned.  A device call that reports degenerate blocks or exceeds the handle's
+    capacity hands this iteration to the host: the factor comes down as the device holds it (cut or not) and takes the host
+    steps.  The host returns (Y, U, p) for set_point, U the direction of line_search() or None."""
+    cut = k.min_rank <= r <= p - 1
+    if k.device is not None:
+        _, rotate, append = k.device
+        try:
+            ok = True
+            if cut:                                        # :70-73
+                ok = not rotate(Q[:, :r])
+                if ok:
+                    cut, p = False, r
+                    run.device_calls += 1
+            if ok:
+                if k.max_width is not None and p + nne > k.max_width:
+                    raise RuntimeError(f"the factor width would exceed the device's {k.max_width} columns (p = {p}, {nne} more)")
+                if not append(vS[:, :nne], float(o["alpha"])):   # :78-83
+                    run.device_calls += 1
+                    return None, None, p + nne
+        except _lib.MsdpError as err:                      # wider than the handle's buffers: re-enter through set_point
+            if "allocated capacity" not in str(err):
+                raise
+        run.host_fallbacks += 1
+        Y = k.fetch()
+        if cut:
+            Y = _cut_on_host(k, Y, Q, e, r)
+        Y = np.ascontiguousarray(k.normalise(np.hstack([Y, o["alpha"] * vS[:, :nne]])))
+        return Y, None, Y.shape[1]
+    if cut:                                              # :70-73
+        Y, p = _cut_on_host(k, Y, Q, e, r), r
+    if k.max_width is not None and p + nne > k.max_width:
+        raise RuntimeError(f"the factor width would exceed the device's {k.max_width} columns (p = {p}, {nne} more)")
+    U = None
+    if k.line_search:                                      # :75-80
+        U = np.hstack([np.zeros((Y.shape[0], p)), vS[:, :nne]])
+        Y = np.hstack([Y, np.zeros((Y.shape[0], nne))])
+    else:
+        Y = k.normalise(np.hstack([Y, o["alpha"] * vS[:, :nne]]))   # :82-83
+    return np.ascontiguousarray(Y), U, p + nne
+
+
+def _cut_on_host(k, Y, Q, e, r):
+    Y = _rank_cut(Y, Q, e, r)
+    return k.normalise(Y) if k.polar_cut else Y
+
+
+def _manifold_loop(h, o, k, Y, p, eig_mode, verbose):
+    """The outer loop of the manifold-only kinds on the handle `h` from the start point Y of width p; closes `h`.  Returns the
+    state of the solve: obj, dinf, gap, gradnorm, z, Lam, S (the host's, where it built one), r of the last evaluation, Y = the
+    point they belong to, data, t0 and the counters device_calls, host_fallbacks, reruns and factor_seconds (the wall time of the
+    factor between the trustregions() calls: its transfers after the first upload, the rank decision, the cut and the widening)."""
+    from types import SimpleNamespace
+    tol, delta, maxiter, theta = o["tol"], int(o["delta"]), int(o["AL_maxiter"]), float(o["theta"])
+    dense_max = int(o.get("dense_eig_max", 3000))          # the host eig(S) is allowed up to this order (options['eig'] = 'host')
+    device = k.device is not None
+    data = {"status": 0, "hessvecs": 0, "cost_evals": 0, "rejected": 0, "rtr_seconds": 0.0, "eig_seconds": 0.0, "log": []}
+    run = SimpleNamespace(obj=None, dinf=None, gap=None, gradnorm=None, z=None, Lam=None, S=None, r=None, Y=Y, data=data,
+                          t0=time.time(), device_calls=0, host_fallbacks=0, reruns=0, factor_seconds=0.0)
+    t0 = run.t0
+    obj = dinf = gap = res = res0 = U = None
+    certified = last_verified = True
+    resident = False
+    escape = lambda kk: (lambda tol, maxit: h.escape_eigs(kk, tol=tol, maxit=maxit))
+
+    def verify():
+        # the regular escape call is warm-started (columns of Y and the previous call's vectors in its start block, or
+        # span(Y) deflated): before dinf may end the solve -- always, the estimate of the same call is never taken as a
+        # certificate (ADVICE round 2) -- lambda_min is recomputed by a cold-started, undeflated run
+        lam_v, v_v, lmax_v, conv = _verify_lambda_min(h, escape(1), o, data, 1e-9, 60000)
+        return max(0.0, -lam_v) / (1.0 + lmax_v), v_v, conv
+
+    try:
+        if k.setup is not None:
+            k.setup()
+        topts = _rtr_opts(o)
+        for it in range(1, maxiter + 1):                   # :38
+            if not resident:
+                tf = time.time()
+                h.set_point(Y)
+                if it > 1:                                 # part of a re-shape on the host
+                    run.factor_seconds += time.time() - tf
+            if U is not None:                              # :40-42 line_search
+                _line_search(h, U)
+            st = h.rtr(topts)                              # :43
+            _count_rtr(data, st)
+            run.gradnorm = st.gradnorm                     # :44
+            if not device:
+                tf = time.time()
+                Y = run.Y = k.fetch()                      # X = Y'*Y of :45 -- what the reference returns (:86)
+                run.factor_seconds += time.time() - tf
+            run.z, run.Lam, obj, gap = k.evaluate(not device or eig_mode == "host")   # :46-48
+            run.obj, run.gap = obj, gap
+            t1 = time.time()
+            certified = True
+            run.S = None
+            if eig_mode == "host":
+                run.S = k.host_S(run.z, run.Lam)           # :49
+                dS, vS, nneg = _extreme_eigs_host(run.S, delta, dense_max)   # :50
+                lam_min, lam_max = dS[0], dS[-1]
+            elif eig_mode == "host_sparse":
+                # diagnostic: ARPACK shift-invert on the host (sparse LU of S - sigma I), k bottom eigenpairs
+                import scipy.sparse.linalg as spla
+                run.S = k.host_S(run.z, run.Lam).tocsc()
+                lam_max = float(spla.eigsh(run.S, k=1, which="LA", return_eigenvectors=False, tol=1e-6)[0])
+                lam, vS = spla.eigsh(run.S, k=delta, sigma=-1e-3 - 0.0 * lam_max, which="LM", tol=1e-12)
+                order = np.argsort(lam); lam = lam[order]; vS = vS[:, order]
+                lam_min = lam[0]
+                nneg = int(np.sum(lam < 0))
+            else:
+                lam, vS, lam_max, _, certified = _device_escape(h, escape(delta), o, data, 1e-9, 60000)
+                lam_min = lam[0]
+                nneg = int(np.sum(lam < 0))                # missing pairs come back as +inf
+                data["escape_method"] = h.escape_method()  # 1: block eigen-solver, 0: Lanczos
+            data["eig_seconds"] += time.time() - t1
+            dinf = max(0.0, -lam_min) / (1.0 + lam_max)    # :51
+            res = dinf if gap is None else max(dinf, gap)  # what ends the solve and feeds the slow-progress watch
+            last_verified = eig_mode != "device"
+            if eig_mode == "device" and certified and (res < tol or it == maxiter):
+                last_verified = True
+                dinf_v, v_v, certified = verify()
+                if dinf_v >= tol > dinf:                   # the deflated run had missed the bottom of the spectrum
+                    vS = np.hstack([v_v, vS[:, :max(delta - 1, 0)]])
+                    nneg = max(nneg, 1)
+                dinf = dinf_v
+                res = dinf if gap is None else max(dinf, gap)
+            run.dinf = dinf
+            tf = time.time()
+            if device:                                     # :52-54 from the device's Gram matrix
+                Q, e, r = _thin_svd_rank(None, theta, gram=k.device[0]())
+            else:
+                Q, e, r = _thin_svd_rank(Y, theta, gram=k.host_gram(Y) if k.host_gram is not None else None)
+            run.r = r
+            run.factor_seconds += time.time() - tf
+            row = (it, obj, dinf) + (() if gap is None else (gap,)) + (r, p, time.time() - t0)
+            _say(verbose, (_MANIFOLD_LINE if gap is None else _MANIFOLD_LINE_GAP) % row)
+            data["log"].append(row + (st.hessvecs,))
+            data["iters"] = it
+            stop = res < tol and certified                 # :57-60 (an unconverged Lanczos run certifies nothing)
+            if stop:
+                _say(verbose, "Optimality is reached!")
+            elif it % 20 == 0:                             # :61-69
+                if it > 50 and res > res0:
+                    data["status"] = 2
+                    _say(verbose, "Slow progress!")
+                    stop = True
+                else:
+                    res0 = res
+            if device and (stop or it == maxiter):         # the evaluated point, before the last pass re-shapes it
+                run.Y = k.fetch()
+            if stop or (device and it == maxiter and not k.reshape_last):
+                break
+            if k.rerun and dinf < tol <= gap:              # S is PSD but the point is not stationary: trustregions() again
+                run.reruns += 1
+                resident = device                          # (the device path: on the factor where it is)
+                continue
+            nne = max(min(nneg, delta), 1)                 # :74
+            tf = time.time()
+            Y, U, p = _manifold_reshape(k, o, run, Y, p, Q, e, r, vS, nne)
+            resident = Y is None
+            run.factor_seconds += time.time() - tf
+        if k.verify_at_end and obj is not None and not last_verified and certified:   # stopped on "Slow progress": the true dinf
+            run.dinf, _, certified = verify()
+            res = run.dinf if gap is None else max(run.dinf, gap)
+        if k.finish is not None:
+            k.finish(run)
+    finally:
+        h.close()
+    if data["status"] == 0 and (res is None or res > tol or not certified):   # :92-95
+        data["status"] = 1
+        _say(verbose, "Iteration maximum is reached!")
+    if obj is not None:
+        _say(verbose, "ManiSDP: optimum = %0.8f, time = %0.2fs" % (obj, time.time() - t0))
+    return run
 
 
 # ============================================================ one AL loop for the affine, multiblock and dual kinds
@@ -1623,10 +1419,7 @@ def _al_loop(h, o, t, Y, p, mult, verbose):
         if U is not None:
             _line_search(h, geo.pack(U, p))
         st = h.rtr(geo.topts(p))                           # ManiSDP_unitdiag.m:57
-        data["rtr_seconds"] += st.seconds
-        data["hessvecs"] += st.hessvecs
-        data["cost_evals"] += st.cost_evals
-        data["rejected"] += st.rejected
+        _count_rtr(data, st)
         gradnorm = st.gradnorm
         Y = Y_eval = geo.fetch(p)                          # what the reference returns (:114)
         obj, by, pinf, mult, z, S = t.outer_step(Y, mult, sigma)

@@ -432,6 +432,8 @@ int msdp_linesearch_accept(msdp_handle h);
  *     C_ij x_j, x_i flipped where x_i s_i > 0 (strict: a tie stays).  The 64 trials of a word sweep together; a word stops
  *     after a sweep of its own without a flip, the call when every word has stopped.  All values are then recomputed from
  *     the final vectors (never updated incrementally); the sums are deterministic (no floating-point atomics).
+ *     With the option "round_order" = 1 (msdp_set_option; sparse C only) "rows i = 0 .. n-1 in order" reads "rows in (colour,
+ *     index) order" of msdp_round_coloring, everything else as written here.
  * trials: a multiple of 64, at most MSDP_ROUND_MAX_TRIALS.  Sign bits are packed 64 trials per word: bit t of
  * masks[w * n + i] is set when x_i = -1 in trial 64 w + t.
  *   values0 (trials, may be NULL): the values right after the rounding;   values (trials): the final ones (== values0 when
@@ -462,6 +464,8 @@ int msdp_round_hyperplane(msdp_handle h, int32_t trials, const double* R, int32_
  *     z_i <- c_k* only where cand_k* < cur strictly.  A phase is a bit copy of its table entry, so a converged phase never
  *     counts as changed.  The 64 trials of a word sweep together; a word stops after a sweep of its own without a change, the
  *     call when every word has stopped.  All values are then recomputed from the final phases.
+ *     With the option "round_order" = 1 (msdp_set_option) "rows i = 0 .. n-1 in order" reads "rows in (colour, index) order"
+ *     of msdp_round_coloring, everything else as written here.
  * trials: a multiple of 64, at most MSDP_ROUND_PHASES_MAX_TRIALS.  The call holds trials * n complex numbers on the device
  * (MSDP_ENOMEM when they cannot be had) and releases every allocation before it returns.
  *   values0 (trials, may be NULL): the values right after the rounding;   values (trials): the final ones;   info
@@ -476,6 +480,21 @@ int msdp_round_hyperplane(msdp_handle h, int32_t trials, const double* R, int32_
 #define MSDP_ROUND_PHASES_MAX_M 64
 int msdp_round_phases(msdp_handle h, int32_t M, int32_t trials, const double* R, int32_t sweeps, double* values0,
                       double* values, int32_t* info, double* phases, int32_t* best, double* z, int32_t* k);
+
+/* The colouring behind the colour-ordered local search of the two roundings above (option "round_order" = 1 of
+ * msdp_set_option), computed on the host on the first call and kept with the handle: greedy first-fit in index order,
+ * color(i) = the smallest colour that no already coloured neighbour j != i of row i holds; the neighbours are the stored entries
+ * of row i of C, diagonal entries left out; a row without neighbours gets colour 0.  No stored off-diagonal entry joins two
+ * rows of one colour, so all rows of a colour can be updated at once, and the colours taken one after another are the serial
+ * sweep over the rows sorted by (colour, index).  With "round_order" = 1 the sweeps of msdp_round_hyperplane and
+ * msdp_round_phases therefore read "rows in (colour, index) order" where their descriptions say "rows i = 0 .. n-1 in order":
+ * one launch per colour over the whole device; the row sums (stored order, diagonal skipped), the decision rules, the stopping
+ * rule, info and every output keep their meaning, the local optimum a trial reaches is that of the other order.
+ *   *ncolors: the number of colours (max color + 1);   color (n, may be NULL): the colour of every row.
+ * Needs no resident point.  MSDP_EUNSUPPORTED, the kind named: every handle that refuses "round_order" = 1.  MSDP_EINVAL:
+ * ncolors NULL; a pattern that is not structurally symmetric -- a stored (i, j) without a stored (j, i); the message names the
+ * first such entry in row order. */
+int msdp_round_coloring(msdp_handle h, int32_t* ncolors, int32_t* color);
 
 /* ----------------------------------------------------------------- escape */
 
@@ -748,6 +767,14 @@ int msdp_block_reshape(msdp_handle h, int32_t nb, const int64_t* row0, const int
  *                       three-launch trips also when "block_persist" is on (msdp_tcg_path reports 0).  MSDP_EUNSUPPORTED, the
  *                       handle left as it was: a block with a non-positive or non-finite pivot (the message names the first),
  *                       a unit-block-diagonal handle (its diagonal blocks are zero) and every other kind (the message names it)
+ *   "round_order"  0/1  local search of msdp_round_hyperplane and msdp_round_phases: 0 = the rows in index order, one wave per word
+ *                       of 64 trials walking all rows (default); 1 = the rows in (colour, index) order of msdp_round_coloring, one
+ *                       launch per colour with all rows of the colour and all words side by side.  Each order is a Gauss-Seidel
+ *                       sweep, bit-reproducible run to run; they end in different local optima.  1 is accepted on a single-rank
+ *                       MSDP_KIND_ONLYUNITDIAG handle with a sparse real or a Hermitian cost matrix.  MSDP_EUNSUPPORTED, the kind
+ *                       named: dense and sparse-plus-low-rank handles (every row is coupled to every other), the block kinds, the
+ *                       affine, dual and multiblock kinds, a handle that has joined a communicator.  Any other value: MSDP_EINVAL.
+ *                       A pattern that is not structurally symmetric is refused by the rounding call (see msdp_round_coloring)
  * The environment variables are read once, when the handle is created.  Unknown names -> MSDP_EINVAL. */
 int msdp_set_option(msdp_handle h, const char* name, int32_t value);
 /* (parity tests) Z = tangent_Y(blockdiag(M_i^-1) R) at the resident point Y of a pose-graph handle with the option "precon" set:

@@ -96,6 +96,7 @@ SIGNATURES = {
     "msdp_round_hyperplane": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.c_int32, _dp, _dp, _i32p, _P(C.c_uint64), _i32p,
                                         _P(C.c_int8)]),
     "msdp_round_phases": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _dp, C.c_int32, _dp, _dp, _i32p, _dp, _i32p, _dp, _i32p]),
+    "msdp_round_coloring": (C.c_int, [C.c_void_p, _i32p, _i32p]),
     "msdp_escape_eigs": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int32, _dp, _dp, _dp, _P(C.c_int32)]),
     "msdp_escape_eigs_matrix": (C.c_int, [C.c_void_p, _dp, C.c_int32, C.c_double, C.c_int32, _dp, _dp, _dp,
                                          _P(C.c_int32)]),
@@ -807,6 +808,14 @@ class Handle:
                                                info.ctypes.data_as(_i32p), M.ctypes.data_as(_P(C.c_uint64)) if masks else None,
                                                C.byref(best), x.ctypes.data_as(_P(C.c_int8))))
         return {"values0": values0, "values": values, "info": info, "best": best.value, "x": x, "masks": M}
+
+    def round_coloring(self):
+        """(ncolors, color): the greedy first-fit colouring of the rows of C behind set_option("round_order", 1)
+        (msdp_round_coloring) -- color an int32 array of n entries; computed once per handle, no resident point needed."""
+        nc = C.c_int32()
+        color = np.zeros(self.n, dtype=np.int32)
+        _check(self._lib.msdp_round_coloring(self._h, C.byref(nc), color.ctypes.data_as(_i32p)))
+        return nc.value, color
 
     def debug_get_tcg_step(self):
         """(eta, Heta) of the last tCG solve (test hook, see msdp_debug_get_tcg_step)."""

@@ -1063,6 +1063,12 @@ extern "C" int msdp_set_option(msdp_handle h, const char* name, int32_t value) {
         if (value < 0 || value > 1) { msdp_set_error("precon: 0 or 1"); return MSDP_EINVAL; }
         return msdp_pose_precon_set(h, value);             // (d.pcM is part of the chunk graph's signature: the graph is captured again)
     }
+    else if (!strcmp(name, "round_order")) {
+        if (value != 0 && value != 1) { msdp_set_error("round_order: 0 index order, 1 colour order"); return MSDP_EINVAL; }
+        int rc = value ? msdp_round_color_check(h, "round_order") : 0;
+        if (rc) return rc;
+        t.round_order = value;
+    }
     else if (!strcmp(name, "debug_xr_skip")) t.fail_xr = value != 0;
     else if (!strcmp(name, "debug_fail_block")) t.fail_block = value != 0;
     else if (!strcmp(name, "grid")) { t.grid = value > 0 ? value : 0; choose_grid(h); h->chunk_len = 0; }

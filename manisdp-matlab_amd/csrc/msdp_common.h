@@ -290,6 +290,8 @@ struct Tuning {
                                  //   (msdp_blockpersist.hip) where a plan exists; 0 (default): the generic three-launch trips
     int block_persist_grid = 0;  // ... cap on its workgroups (0: planned; tests and tuning: a small grid takes the two-slot instances)
     int block_persist_wide = 0;  // ... A/B: 1 = the largest grid the plan allows at its row slots, not the fewest workgroups
+    int round_order = 0;         // local search of msdp_round_hyperplane / msdp_round_phases: 0 = rows in index order, one wave per word (default);
+                                 //   1 = rows in (colour, index) order, one launch per colour class over the whole grid (msdp_roundcolor.hip)
 };
 
 struct msdp_handle_s {
@@ -396,6 +398,10 @@ struct msdp_handle_s {
     // option "precon" of the pose-graph kind (msdp_pose_precon.hip): the buffers behind Dev::pcM / Dev::pcz, allocated when the option is
     // first set and kept while it is off
     double* pc_minv = nullptr; double* pc_z = nullptr; size_t pc_z_cap = 0;
+    // colouring of the rows of C for the colour-ordered rounding sweeps (msdp_roundcolor.hip): built on first use, kept with the handle.
+    // rc_color[i] the colour of row i, rc_offs[c] .. rc_offs[c + 1] the positions of class c in the visiting order (device copies:
+    // rc_order_d, n rows sorted by (colour, index), and rc_offs_d, rc_ncolors + 1 offsets)
+    int rc_ncolors = -1; std::vector<int> rc_color, rc_offs; int* rc_order_d = nullptr; int* rc_offs_d = nullptr;
 };
 
 #define MSDP_CHECK_H(h)                                     \
@@ -496,6 +502,8 @@ int msdp_lowrank_setup(msdp_handle h, int q, const double* V, const double* s); 
 int msdp_lowrank_project(msdp_handle h, const double* X);     // d.lrT = diag(s) V' X (X: n x ld gather source)
 int msdp_lowrank_sv_add(msdp_handle h, const double* v, double* w);   // w += V (s .* (V' v)) for vectors of n entries (the escape's S*v; uses d.lrT / d.lrTp)
 // msdp_hermitian.hip
+int msdp_round_color_check(msdp_handle h, const char* who);    // 0 where the colour-ordered sweeps apply to the handle, else MSDP_EUNSUPPORTED with the kind named
+int msdp_round_color_plan(msdp_handle h, const char* who);     // the colouring of the handle, built and uploaded on the first call (h->rc_*)
 int msdp_hermitian_setup(msdp_handle h, const double* val);   // the complex CSR / ELL values of a COST_HERM handle (val: nnz (re, im) pairs in CSC order)
 int msdp_hermitian_sv(msdp_handle h, const double* z, const double* v, double* w);   // w = C v - z .* v, v and w n complex entries (re, im interleaved)
 int msdp_hermitian_jcopy(msdp_handle h, const double* v, double* w);                 // w = i * v: (re, im) -> (-im, re)

@@ -241,6 +241,52 @@ __global__ __launch_bounds__(64) void k_phase_sweep(PhaseCost c, double2* Z, int
     if (lane == 0) { st[w] += 1; st[W + w] = changes; }
 }
 
+// One colour class of a sweep in colour order (option "round_order" = 1): the rows order[offs[cls]] .. order[offs[cls + 1] - 1] for
+// every word at once.  Grid: (row groups, words); a wave takes one row of the class at a time for the word of its workgroup,
+// lane = trial.  s_i and both decision rules are those of k_phase_sweep.  No stored off-diagonal entry joins two rows of a class
+// (msdp_roundcolor.hip), so no wave of the launch writes a phase line that another one reads, and lane t reads and writes only
+// column t of its own row's line: plain loads, the kernel boundary orders the classes.  Z is read and written here as well: no
+// const __restrict__.  cur[w] gains the changes of word w (one integer atomic per wave: the sum does not depend on the order); a
+// word whose previous sweep changed nothing (prev[w] == 0) skips the sweep; CIRCLE counts nothing and never skips.
+template <bool CIRCLE>
+__global__ __launch_bounds__(PHASE_WAVES * 64) void k_phase_sweep_color(PhaseCost c, double2* Z, int M, const double2* __restrict__ tab,
+                                                                        const int* __restrict__ order, const int* __restrict__ offs, int cls,
+                                                                        const int* __restrict__ prev, int* cur, int first) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int w = blockIdx.y;
+    if (!CIRCLE && !first && prev[w] == 0) return;
+    double2* Zw = Z + (size_t)w * c.n * 64;
+    const int q1 = offs[cls + 1];
+    int changes = 0;
+    for (int q = offs[cls] + blockIdx.x * PHASE_WAVES + wave; q < q1; q += gridDim.x * PHASE_WAVES) {
+        const int i = __builtin_amdgcn_readfirstlane(order[q]);
+        const PhaseRow r = phase_row(c, i);
+        const double2 s = phase_row_sum(make_double2(0.0, 0.0), c, r, r.e0, Zw, i, true, lane);
+        if (CIRCLE) {
+            const double m2 = s.x * s.x + s.y * s.y;
+            if (m2 != 0.0) {
+                const double m = sqrt(m2);
+                Zw[(size_t)i * 64 + lane] = make_double2(-s.x / m, -s.y / m);
+            }
+        } else {
+            const double2 zi = Zw[(size_t)i * 64 + lane];
+            const double now = phase_dot(zi, s);
+            double2 zb = tab[0];
+            double best = phase_dot(zb, s);
+            for (int k = 1; k < M; ++k) {
+                const double2 ck = tab[k];
+                const double cand = phase_dot(ck, s);
+                if (cand < best) { best = cand; zb = ck; }
+            }
+            const bool ch = best < now;
+            if (ch) Zw[(size_t)i * 64 + lane] = zb;
+            changes += __popcll(__ballot(ch));
+        }
+    }
+    if (!CIRCLE && changes && lane == 0) atomicAdd(&cur[w], changes);
+}
+
 // c_k = (cos, sin)(2 pi k / M), the angle evaluated as ((2 * pi) * k) / M in double and passed to the C library's cos / sin;
 // where 4 k is a multiple of M the entry is written as exactly (1, 0), (0, 1), (-1, 0), (0, -1) for 4 k / M = 0, 1, 2, 3.
 static void phase_table(int M, std::vector<double2>& tab) {
@@ -262,6 +308,39 @@ static int phase_values(msdp_handle h, const PhaseCost& c, const double2* Z, int
     return 0;
 }
 
+// Sweep s of the colour-ordered search: one launch per colour class on the handle's stream.  st holds two count rows of W words,
+// alternated by the parity of s: the row of this sweep is cleared on the stream in front of its launches, the other one still
+// holds the counts of sweep s - 1.  With `read` the host then reads the counts of this sweep, as after a serial sweep: hst[w] gains
+// one for every word that ran (the first sweep, or changes in its previous one), hst[W + w] is the count of its last sweep.
+// M = 0: every word runs every sweep and counts nothing; the counts are read once, after the last one.
+static int phase_sweep_color(msdp_handle h, const PhaseCost& c, double2* Z, int M, const double2* tab, int* st, int W, int s, bool read,
+                             std::vector<int>& hst) {
+    int* cur = st + (size_t)(s & 1) * W;
+    const int* prev = st + (size_t)((s & 1) ^ 1) * W;
+    HIPCHK(hipMemsetAsync(cur, 0, (size_t)W * sizeof(int), h->stream));
+    for (int cls = 0; cls < h->rc_ncolors; ++cls) {
+        const int rows = h->rc_offs[(size_t)cls + 1] - h->rc_offs[(size_t)cls];
+        const int Gc = std::max(1, std::min((rows + PHASE_WAVES - 1) / PHASE_WAVES, (4096 + W - 1) / W));   // about 16 384 waves per launch
+        if (M == 0)
+            hipLaunchKernelGGL(k_phase_sweep_color<true>, dim3(Gc, W), dim3(PHASE_WAVES * 64), 0, h->stream, c, Z, 0, tab,
+                               (const int*)h->rc_order_d, (const int*)h->rc_offs_d, cls, prev, cur, s == 0 ? 1 : 0);
+        else
+            hipLaunchKernelGGL(k_phase_sweep_color<false>, dim3(Gc, W), dim3(PHASE_WAVES * 64), 0, h->stream, c, Z, M, tab,
+                               (const int*)h->rc_order_d, (const int*)h->rc_offs_d, cls, prev, cur, s == 0 ? 1 : 0);
+    }
+    HIPCHK(hipGetLastError());
+    if (M == 0) for (int w = 0; w < W; ++w) hst[(size_t)w] += 1;
+    if (!read) return 0;
+    std::vector<int> cnt((size_t)W);
+    HIPCHK(msdp_memcpy_async(cnt.data(), cur, cnt.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int w = 0; w < W; ++w) {
+        if (M != 0 && (s == 0 || hst[(size_t)W + w] != 0)) hst[(size_t)w] += 1;   // (a word that did not run left its zero in place)
+        hst[(size_t)W + w] = cnt[(size_t)w];
+    }
+    return 0;
+}
+
 extern "C" int msdp_round_phases(msdp_handle h, int32_t M, int32_t trials, const double* R, int32_t sweeps, double* values0,
                                  double* values, int32_t* info, double* phases, int32_t* best, double* z, int32_t* k) {
     MSDP_CHECK_H(h);
@@ -279,6 +358,11 @@ extern "C" int msdp_round_phases(msdp_handle h, int32_t M, int32_t trials, const
     if (!h->have_point) { msdp_set_error("round_phases: no resident point"); return MSDP_ESTATE; }
     const int n = d.n, p = d.p / 2, T = trials, W = T / 64;
     if (n < 1 || p < 1) { msdp_set_error("round_phases: empty problem"); return MSDP_EINVAL; }
+    const bool color = h->tune.round_order == 1 && sweeps > 0;
+    if (color) {
+        const int rcc = msdp_round_color_plan(h, "round_phases");
+        if (rcc) return rcc;
+    }
     PhaseCost c{};
     c.n = n; c.rowptr = d.rowptr; c.colind = d.colind; c.cv = d.hzv;
     // row chunks of the value sums: about 2048 waves in flight, at least PHASE_ROWS rows each
@@ -324,7 +408,10 @@ extern "C" int msdp_round_phases(msdp_handle h, int32_t M, int32_t trials, const
     // launches; M = 0: exactly `sweeps` launches, the counts read once
     std::vector<int> hst((size_t)2 * W, 0);
     for (int s = 0; s < sweeps; ++s) {
-        if (M == 0) {
+        if (color) {
+            if ((rc = phase_sweep_color(h, c, Z, (int)M, (const double2*)tab, st, W, s, M != 0 || s + 1 == sweeps, hst))) { release(); return rc; }
+            if (M == 0) continue;
+        } else if (M == 0) {
             hipLaunchKernelGGL(k_phase_sweep<true>, dim3(W), dim3(64), 0, h->stream, c, Z, 0, (const double2*)tab, st, W, s == 0 ? 1 : 0);
             PHASE_HIP(hipGetLastError());
             if (s + 1 < sweeps) continue;
@@ -332,8 +419,10 @@ extern "C" int msdp_round_phases(msdp_handle h, int32_t M, int32_t trials, const
             hipLaunchKernelGGL(k_phase_sweep<false>, dim3(W), dim3(64), 0, h->stream, c, Z, (int)M, (const double2*)tab, st, W, s == 0 ? 1 : 0);
             PHASE_HIP(hipGetLastError());
         }
-        PHASE_HIP(msdp_memcpy_async(hst.data(), st, hst.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        PHASE_HIP(hipStreamSynchronize(h->stream));
+        if (!color) {
+            PHASE_HIP(msdp_memcpy_async(hst.data(), st, hst.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+            PHASE_HIP(hipStreamSynchronize(h->stream));
+        }
         bool any = false;
         for (int w = 0; w < W; ++w) any = any || hst[(size_t)W + w] != 0;
         if (M != 0 && !any) break;

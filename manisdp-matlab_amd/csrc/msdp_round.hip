@@ -263,6 +263,38 @@ __global__ __launch_bounds__(64) void k_round_1opt(RoundCost c, u64* M, int* st,
     if (lane == 0) { st[w] += 1; st[W + w] = flips; }
 }
 
+// One colour class of a 1-opt sweep in colour order (option "round_order" = 1): the rows order[offs[cls]] .. order[offs[cls + 1] - 1]
+// for every word at once.  Grid: (row groups, words); a wave takes one row of the class at a time for the word of its workgroup,
+// lane = trial.  The row's number and the flip rule are those of k_round_1opt.  No stored off-diagonal entry joins two rows of a
+// class (msdp_roundcolor.hip), so no wave of the launch writes a word that another one reads, and the word of a wave's own row
+// is read and written by that wave alone: plain loads, the kernel boundary orders the classes.  cur[w] gains the flips of word w
+// (one integer atomic per wave: the sum does not depend on the order); a word whose previous sweep flipped nothing (prev[w] == 0)
+// skips the sweep.  CSR rows only: the dense and the low-rank kinds have no colour order.
+__global__ __launch_bounds__(ROUND_WAVES * 64) void k_round_1opt_color(RoundCost c, u64* M, const int* __restrict__ order,
+                                                                       const int* __restrict__ offs, int cls, const int* __restrict__ prev,
+                                                                       int* cur, int first) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int w = blockIdx.y;
+    if (!first && prev[w] == 0) return;
+    u64* Mw = M + (size_t)w * c.n;
+    const int q1 = offs[cls + 1];
+    int flips = 0;
+    for (int q = offs[cls] + blockIdx.x * ROUND_WAVES + wave; q < q1; q += gridDim.x * ROUND_WAVES) {
+        const int i = __builtin_amdgcn_readfirstlane(order[q]);
+        RoundRow r = round_row(c, i);
+        round_uniform(r);
+        const u64 mi = Mw[i];
+        const double xs = round_row_sum<false>(0.0, r, r.e0, Mw, i, mi, true, lane);
+        const u64 fl = __ballot(xs > 0.0);
+        if (fl) {
+            if (lane == 0) Mw[i] = mi ^ fl;
+            flips += __popcll(fl);
+        }
+    }
+    if (flips && lane == 0) atomicAdd(&cur[w], flips);
+}
+
 static int round_values(msdp_handle h, const RoundCost& c, const u64* M, int W, int G, int rows_per, double* part, double* partT, double* val) {
     const int T = W * 64;
     if (c.q > 0) {
@@ -273,6 +305,31 @@ static int round_values(msdp_handle h, const RoundCost& c, const u64* M, int W, 
         hipLaunchKernelGGL(k_round_sum<false>, dim3((T + 255) / 256), dim3(256), 0, h->stream, (const double*)part, (const double*)nullptr, 0, (const double*)nullptr, G, T, val);
     }
     HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// Sweep s of the colour-ordered search: one launch per colour class on the handle's stream.  st holds two count rows of W
+// words, alternated by the parity of s: the row of this sweep is cleared on the stream in front of its launches, the other one
+// still holds the counts of sweep s - 1.  The host then reads the counts of this sweep, as after a serial sweep: hst[w] gains
+// one for every word that ran (the first sweep, or flips in its previous one), hst[W + w] is the count of its last sweep.
+static int round_sweep_color(msdp_handle h, const RoundCost& c, u64* M, int* st, int W, int s, std::vector<int>& hst) {
+    int* cur = st + (size_t)(s & 1) * W;
+    const int* prev = st + (size_t)((s & 1) ^ 1) * W;
+    HIPCHK(hipMemsetAsync(cur, 0, (size_t)W * sizeof(int), h->stream));
+    for (int cls = 0; cls < h->rc_ncolors; ++cls) {
+        const int rows = h->rc_offs[(size_t)cls + 1] - h->rc_offs[(size_t)cls];
+        const int Gc = std::max(1, std::min((rows + ROUND_WAVES - 1) / ROUND_WAVES, (4096 + W - 1) / W));   // about 16 384 waves per launch
+        hipLaunchKernelGGL(k_round_1opt_color, dim3(Gc, W), dim3(ROUND_WAVES * 64), 0, h->stream, c, M, (const int*)h->rc_order_d,
+                           (const int*)h->rc_offs_d, cls, prev, cur, s == 0 ? 1 : 0);
+    }
+    HIPCHK(hipGetLastError());
+    std::vector<int> cnt((size_t)W);
+    HIPCHK(msdp_memcpy_async(cnt.data(), cur, cnt.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int w = 0; w < W; ++w) {
+        if (s == 0 || hst[(size_t)W + w] != 0) hst[(size_t)w] += 1;   // (a word that did not run left its zero in place)
+        hst[(size_t)W + w] = cnt[(size_t)w];
+    }
     return 0;
 }
 
@@ -293,6 +350,11 @@ extern "C" int msdp_round_hyperplane(msdp_handle h, int32_t trials, const double
     if (!h->have_point) { msdp_set_error("round_hyperplane: no resident point"); return MSDP_ESTATE; }
     const int n = d.n, p = d.p, T = trials, W = T / 64;
     if (n < 1) { msdp_set_error("round_hyperplane: empty problem"); return MSDP_EINVAL; }
+    const bool color = h->tune.round_order == 1 && sweeps > 0;
+    if (color) {                                               // (the option is refused on the dense and the low-rank kinds)
+        const int rcc = msdp_round_color_plan(h, "round_hyperplane");
+        if (rcc) return rcc;
+    }
     RoundCost c{};
     c.n = n; c.dense = d.costkind == COST_DENSE; c.nS = msdp_dense_nS(n);
     c.rowptr = d.rowptr; c.colind = d.colind; c.cval = d.cval; c.Cd = d.Cd;
@@ -335,11 +397,15 @@ extern "C" int msdp_round_hyperplane(msdp_handle h, int32_t trials, const double
     // the host reads the flip counts after every sweep: it stops when no word flipped anything, or after `sweeps` launches
     std::vector<int> hst((size_t)2 * W, 0);
     for (int s = 0; s < sweeps; ++s) {
-        if (lr) hipLaunchKernelGGL(k_round_1opt<true>, dim3(W), dim3(64), 0, h->stream, c, M, st, W, s == 0 ? 1 : 0);
-        else hipLaunchKernelGGL(k_round_1opt<false>, dim3(W), dim3(64), 0, h->stream, c, M, st, W, s == 0 ? 1 : 0);
-        ROUND_HIP(hipGetLastError());
-        ROUND_HIP(msdp_memcpy_async(hst.data(), st, hst.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        ROUND_HIP(hipStreamSynchronize(h->stream));
+        if (color) {
+            if ((rc = round_sweep_color(h, c, M, st, W, s, hst))) { release(); return rc; }
+        } else {
+            if (lr) hipLaunchKernelGGL(k_round_1opt<true>, dim3(W), dim3(64), 0, h->stream, c, M, st, W, s == 0 ? 1 : 0);
+            else hipLaunchKernelGGL(k_round_1opt<false>, dim3(W), dim3(64), 0, h->stream, c, M, st, W, s == 0 ? 1 : 0);
+            ROUND_HIP(hipGetLastError());
+            ROUND_HIP(msdp_memcpy_async(hst.data(), st, hst.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+            ROUND_HIP(hipStreamSynchronize(h->stream));
+        }
         bool any = false;
         for (int w = 0; w < W; ++w) any = any || hst[(size_t)W + w] != 0;
         if (!any) break;

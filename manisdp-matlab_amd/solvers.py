@@ -203,18 +203,27 @@ def _escape_rr_option(o):
     return 1 if rr == "device" else 0
 
 
+def _round_order(order, where):
+    """The visiting order of a rounding's local search: "index" (rows 0 .. n-1, the default) or "color" (rows by colour class,
+    set_option("round_order", 1)); anything else is a ValueError."""
+    if not isinstance(order, str) or order not in ("index", "color"):
+        raise ValueError(f"{where} must be 'index' or 'color', not {order!r}")
+    return order
+
+
 def _round_option(o):
-    """options["round"] = {"trials", "sweeps", "seed"}: round the solution to +1/-1 vectors on the device after the solve
+    """options["round"] = {"trials", "sweeps", "seed", "order"}: round the solution to +1/-1 vectors on the device after the solve
     (msdp_round_hyperplane; not in the reference, so no DEFAULTS entry).  Returns None when the option is absent, else
-    (trials, sweeps, seed) -- trials a multiple of 64 up to _lib.ROUND_MAX_TRIALS, sweeps >= 0 (0: no local search)."""
+    (trials, sweeps, seed, order) -- trials a multiple of 64 up to _lib.ROUND_MAX_TRIALS, sweeps >= 0 (0: no local search),
+    order "index" (default) or "color"."""
     r = o.get("round")
     if r is None:
         return None
     if not isinstance(r, dict):
         raise ValueError(f"options['round'] must be a dict with 'trials', 'sweeps' and 'seed', not {r!r}")
-    unknown = sorted(set(r) - {"trials", "sweeps", "seed"})
+    unknown = sorted(set(r) - {"trials", "sweeps", "seed", "order"})
     if unknown:
-        raise ValueError(f"options['round'] has unknown fields {unknown} (known: 'trials', 'sweeps', 'seed')")
+        raise ValueError(f"options['round'] has unknown fields {unknown} (known: 'trials', 'sweeps', 'seed', 'order')")
     trials, sweeps, seed = r.get("trials", 256), r.get("sweeps", 50), r.get("seed", 0)
     for name, v in (("trials", trials), ("sweeps", sweeps), ("seed", seed)):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
@@ -225,15 +234,17 @@ def _round_option(o):
         raise ValueError(f"options['round']['sweeps'] and ['seed'] must be >= 0, not {sweeps} and {seed}")
     if o.get("comm") is not None:
         raise ValueError("options['round'] needs a single-rank solve (no options['comm'])")
-    return int(trials), int(sweeps), int(seed)
+    return int(trials), int(sweeps), int(seed), _round_order(r.get("order", "index"), "options['round']['order']")
 
 
-def round_unitdiag(C, Y, trials=256, sweeps=50, rng=None, R=None):
+def round_unitdiag(C, Y, trials=256, sweeps=50, rng=None, R=None, order="index"):
     """Round the factor Y (n x p, unit rows) of a unit-diagonal SDP with cost C to a +1/-1 vector on the device: `trials`
     hyperplane roundings x = sign(Y r) with Gaussian r (drawn from `rng` unless R, trials x p, is given), each improved by up
     to `sweeps` sweeps of 1-opt local search; the best of them is returned.  Returns (x, value, info): x int8 of length n,
     value = x' C x, info the dict of Handle.round_hyperplane (all values, sweeps and flips per word of 64 trials).  C: sparse,
-    dense, or a problems.SparsePlusLowRank."""
+    dense, or a problems.SparsePlusLowRank.  order: "index" -- a sweep visits the rows 0 .. n-1 -- or "color": by colour class,
+    one launch per colour over the whole device (sparse C only; the library refuses the other two)."""
+    order = _round_order(order, "round_unitdiag: order")
     Y = np.ascontiguousarray(Y, dtype=np.float64)
     if R is None:
         R = (rng or np.random.default_rng(0)).standard_normal((int(trials), Y.shape[1]))
@@ -244,6 +255,8 @@ def round_unitdiag(C, Y, trials=256, sweeps=50, rng=None, R=None):
         h = _lib.Handle.onlyunitdiag(C.tocsr() if sp.issparse(C) else np.asarray(C, dtype=np.float64), pcap=max(32, Y.shape[1]))
     try:
         h.set_point(Y)
+        if order == "color":
+            h.set_option("round_order", 1)
         res = h.round_hyperplane(R, sweeps=sweeps)
     finally:
         h.close()
@@ -251,18 +264,19 @@ def round_unitdiag(C, Y, trials=256, sweeps=50, rng=None, R=None):
 
 
 def _round_phases_option(o):
-    """options["round_phases"] = {"M", "trials", "sweeps", "seed"} of a complex Hermitian C: round the solution to phases on the
-    device after the solve (msdp_round_phases; not in the reference, so no DEFAULTS entry).  Returns None when the option is
-    absent, else (M, trials, sweeps, seed) -- M = 0 (the unit circle) or 2 .. _lib.ROUND_PHASES_MAX_M (the M-th roots of unity),
-    trials a multiple of 64 up to _lib.ROUND_PHASES_MAX_TRIALS, sweeps >= 0 (0: no local search)."""
+    """options["round_phases"] = {"M", "trials", "sweeps", "seed", "order"} of a complex Hermitian C: round the solution to phases
+    on the device after the solve (msdp_round_phases; not in the reference, so no DEFAULTS entry).  Returns None when the option
+    is absent, else (M, trials, sweeps, seed, order) -- M = 0 (the unit circle) or 2 .. _lib.ROUND_PHASES_MAX_M (the M-th roots of
+    unity), trials a multiple of 64 up to _lib.ROUND_PHASES_MAX_TRIALS, sweeps >= 0 (0: no local search), order "index" (default)
+    or "color"."""
     r = o.get("round_phases")
     if r is None:
         return None
     if not isinstance(r, dict):
         raise ValueError(f"options['round_phases'] must be a dict with 'M', 'trials', 'sweeps' and 'seed', not {r!r}")
-    unknown = sorted(set(r) - {"M", "trials", "sweeps", "seed"})
+    unknown = sorted(set(r) - {"M", "trials", "sweeps", "seed", "order"})
     if unknown:
-        raise ValueError(f"options['round_phases'] has unknown fields {unknown} (known: 'M', 'trials', 'sweeps', 'seed')")
+        raise ValueError(f"options['round_phases'] has unknown fields {unknown} (known: 'M', 'trials', 'sweeps', 'seed', 'order')")
     M, trials, sweeps, seed = r.get("M", 0), r.get("trials", 256), r.get("sweeps", 20), r.get("seed", 0)
     for name, v in (("M", M), ("trials", trials), ("sweeps", sweeps), ("seed", seed)):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
@@ -273,7 +287,7 @@ def _round_phases_option(o):
         raise ValueError(f"options['round_phases']['trials'] must be a multiple of 64 in 64..{_lib.ROUND_PHASES_MAX_TRIALS}, not {trials}")
     if sweeps < 0 or seed < 0:
         raise ValueError(f"options['round_phases']['sweeps'] and ['seed'] must be >= 0, not {sweeps} and {seed}")
-    return int(M), int(trials), int(sweeps), int(seed)
+    return int(M), int(trials), int(sweeps), int(seed), _round_order(r.get("order", "index"), "options['round_phases']['order']")
 
 
 def _hermitian_factor_option(o):
@@ -291,18 +305,22 @@ def _draw_phase_R(rng, trials, p):
     return Rr + 1j * rng.standard_normal((int(trials), int(p)))
 
 
-def round_phases(C, Y, M=0, trials=256, sweeps=20, rng=None, R=None):
+def round_phases(C, Y, M=0, trials=256, sweeps=20, rng=None, R=None, order="index"):
     """Round the factor Y (n x p complex, rows of unit norm) of a complex unit-diagonal SDP with Hermitian cost C to phases on
     the device: `trials` roundings of Y r with complex Gaussian r (drawn from `rng`, the real parts first, unless R, trials x p
     complex, is given) to the unit circle (M = 0) or the M-th roots of unity, each improved by up to `sweeps` Gauss-Seidel
     sweeps of coordinate minimisation; the best of them is returned.  Returns (z, value, info): z complex of length n,
-    value = z^H C z, info the dict of Handle.round_phases."""
+    value = z^H C z, info the dict of Handle.round_phases.  order: "index" -- a sweep visits the rows 0 .. n-1 -- or "color": by
+    colour class, one launch per colour over the whole device."""
+    order = _round_order(order, "round_phases: order")
     Y = np.ascontiguousarray(Y, dtype=np.complex128)
     if R is None:
         R = _draw_phase_R(rng or np.random.default_rng(0), trials, Y.shape[1])
     h = _lib.Handle.onlyunitdiag_hermitian(C, pcap=max(32, Y.shape[1]))
     try:
         h.set_point(Y)
+        if order == "color":
+            h.set_option("round_order", 1)
         res = h.round_phases(R, M=M, sweeps=sweeps)
     finally:
         h.close()
@@ -396,8 +414,10 @@ def _onlyunitdiag_impl(C, options=None, verbose=True, rng=None):
         if eig_mode == "device":
             run.data["escape_rr_stages"] = h.ritz_stages()     # Rayleigh-Ritz stages: (device, host, host after fallback)
         if rounding is not None and run.obj is not None:       # options["round"]: +1/-1 vectors from the evaluated point
-            trials, sweeps, seed = rounding
+            trials, sweeps, seed, order = rounding
             h.set_point(run.Y)
+            if order == "color":                               # (refused by the library for a dense or a low-rank C)
+                h.set_option("round_order", 1)
             res = h.round_hyperplane(np.random.default_rng(seed).standard_normal((trials, run.Y.shape[1])), sweeps=sweeps)
             run.data["round"] = {"x": res["x"], "value": float(res["values"][res["best"]]), "values": res["values"],
                                  "best": res["best"], "info": res["info"]}
@@ -470,8 +490,10 @@ def _onlyunitdiag_hermitian_impl(C, o, verbose, rng):
 
     def finish(run):
         if rounding is not None and run.obj is not None:       # options["round_phases"]: phases from the evaluated point
-            M, trials, sweeps, seed = rounding
+            M, trials, sweeps, seed, order = rounding
             h.set_point(run.Y)
+            if order == "color":
+                h.set_option("round_order", 1)
             res = h.round_phases(_draw_phase_R(np.random.default_rng(seed), trials, run.Y.shape[1]), M=M, sweeps=sweeps)
             run.data["round"] = {"z": res["z"], "value": float(res["values"][res["best"]]), "values": res["values"],
                                  "best": res["best"], "info": res["info"]}

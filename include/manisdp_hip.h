@@ -209,6 +209,11 @@ int msdp_debug_get_tcg_step(msdp_handle h, double* eta, double* Heta);
  * row-major, column j = coefficients of Ritz vector j, W'GW = I on the first *rank columns) of the block eigen-solver. */
 int msdp_debug_sym_eig(int32_t n, const double* A, double* w, double* Z);
 int msdp_debug_ritz(int32_t b, const double* G, const double* H, double* theta, double* W, int32_t* rank);
+/* Test-only, host code only: the same problem for the complex panel of a Hermitian cost matrix (be_ritz_herm: complex Cholesky,
+ * Householder to a real tridiagonal form, the same QL).  G, H, W: bc x bc complex, row-major, (re, im) interleaved, G and H
+ * Hermitian; theta[bc] ascending, +inf beyond *rank; W^H G W = I on the first *rank columns, zero columns beyond.  Every complex
+ * direction appears once. */
+int msdp_debug_ritz_herm(int32_t bc, const double* G, const double* H, double* theta, double* W, int32_t* rank);
 /* Test-only GPU twin of msdp_debug_ritz: uploads G and H and runs the kernel of the device Rayleigh-Ritz stage (option
  * "escape_rr" = 1; k_be_ritz, msdp_beritz.hip) alone on the current device -- no handle, no fallback to the host stage.  b = 32
  * or 64 (else MSDP_EUNSUPPORTED: the three b x b matrices of a 128-wide panel do not fit the LDS).  *status: 0 = ok (theta
@@ -510,7 +515,14 @@ int msdp_round_coloring(msdp_handle h, int32_t* ncolors, int32_t* color);
  * counted with multiplicity.  The sequential deflation ends when the
  * complement of what was found is non-negative or empty (n <= k, or every eigenvalue
  * negative and none left).  Values that do not exist are +inf with a zero vector, and
- * msdp_escape_info reports how many are real: never more than n. */
+ * msdp_escape_info reports how many are real: never more than n.
+ * Hermitian C (msdp_create_onlyunitdiag_csc_hermitian): V is k complex vectors in the real view, column-major with stride 2n
+ * ((re, im) of row i of vector c at V[c*2n + 2i], V[c*2n + 2i + 1]), orthonormal in the complex inner product, every eigenvalue
+ * of S reported as often as S has it.  By default the Lanczos path runs on the real view of length 2n.  With option
+ * "escape_method" = 2, on a single rank and n >= 256, the block eigen-solver runs on a complex panel of 32 or 64 columns (the
+ * complex columns of the factor in its start block, a complex gather per filter step, the Rayleigh-Ritz problem of order 32 /
+ * 64 in complex algebra on the host); lambda_max still comes from a short Lanczos run on the real view.  At most 56 pairs per
+ * call on that route (k + 8 <= 64, else MSDP_EINVAL). */
 int msdp_escape_eigs(msdp_handle h, int32_t k, double tol, int32_t maxit,
                      double* lam_min, double* V, double* lam_max, int32_t* iters);
 
@@ -521,7 +533,8 @@ int msdp_escape_eigs_matrix(msdp_handle h, const double* S, int32_t k, double to
 
 /* Which eigen-solver the LAST escape call on this handle ran: 1 = block Chebyshev-filtered subspace iteration
  * (msdp_blockeig.hip: sparse C; a 64- or 128-wide panel, reduction-free filter steps on the S*U kernel, Rayleigh-Ritz every
- * few hundred steps), 0 = deflated single-vector Lanczos runs (msdp_escape.hip: dense S, pre-sharded dense C, small n). */
+ * few hundred steps; Hermitian C with "escape_method" = 2: a complex panel of 32 or 64 columns), 0 = deflated single-vector
+ * Lanczos runs (msdp_escape.hip: dense S, pre-sharded dense C, small n, Hermitian C unless asked). */
 int msdp_escape_method(msdp_handle h, int32_t* method);
 
 /* Collective calls this handle has issued on its communicator so far (row exchange, all-reduce, all-gather; operations grouped
@@ -713,15 +726,19 @@ int msdp_block_reshape(msdp_handle h, int32_t nb, const int64_t* row0, const int
  *                       msdp_trip2.hip) instead of three (17 passes): 1 = where it pays, from 2^21 vector entries on (default);
  *                       2 = always (tests); 0 = never
  *   "escape_method" 0 = block eigen-solver where it applies (sparse C, n >= 512), Lanczos otherwise (default); 1 = Lanczos
- *                       always; 2 = block also for small n (tests)
+ *                       always; 2 = block also for small n (tests).  Hermitian C: 0 and 1 = Lanczos on the real view; 2 = the
+ *                       block eigen-solver on a complex panel (single rank, n >= 256; Lanczos below that)
  *   "escape_rr"    0/1  block eigen-solver, dense algebra of a Rayleigh-Ritz stage (b x b problem H c = theta G c, residual
  *                       sums): 0 = on the host (default: Cholesky + tred2 / tql2 on one thread between two copies and two
  *                       synchronisations), 1 = on the device for panels of 32 / 64 columns (one workgroup, Cholesky + cyclic
  *                       Jacobi in LDS; the stage reads one record of 2b + 2 doubles behind one synchronisation).  128-wide
  *                       panels keep the host stage, and so does a stage whose kernel reports dependent columns or a breakdown
- *                       (msdp_debug_ritz_stages counts them).  Any other value: MSDP_EINVAL
+ *                       (msdp_debug_ritz_stages counts them).  The complex panel of a Hermitian C always takes the host
+ *                       stage (counted as such).  Any other value: MSDP_EINVAL
  *   "be_width" 0/32/64/128, "be_degree", "be_grid", "be_lpr"  block eigen-solver: panel width, filter degree per round,
- *                       workgroups and lanes per row of the filter step (0 = automatic; measurement and tests)
+ *                       workgroups and lanes per row of the filter step (0 = automatic; measurement and tests).  "be_width"
+ *                       counts REAL columns for a Hermitian C too: 32 / 64 / 128 = 16 / 32 / 64 complex columns (automatic:
+ *                       32 complex columns where the factor's and the previous call's columns plus 8, and k + 8, fit; else 64)
  *   "escape_start_y" 1/0  undeflated cold-start escape runs start from a random combination of the columns of Y plus 5 %
  *                       noise instead of pure noise (default 0; the independent lambda_min check of the host loops sets it)
  *   "lanczos_onesync" 1/0  undeflated persistent Lanczos runs use one grid synchronisation per step (default 1; 0 = the

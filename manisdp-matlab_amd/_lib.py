@@ -110,6 +110,7 @@ SIGNATURES = {
     "msdp_debug_get_tcg_step": (C.c_int, [C.c_void_p, _dp, _dp]),
     "msdp_debug_sym_eig": (C.c_int, [C.c_int32, _dp, _dp, _dp]),
     "msdp_debug_ritz": (C.c_int, [C.c_int32, _dp, _dp, _dp, _dp, _P(C.c_int32)]),
+    "msdp_debug_ritz_herm": (C.c_int, [C.c_int32, _dp, _dp, _dp, _dp, _P(C.c_int32)]),
     "msdp_debug_ritz_device": (C.c_int, [C.c_int32, _dp, _dp, _dp, _dp, _P(C.c_int32), _P(C.c_int32)]),
     "msdp_debug_ritz_stages": (C.c_int, [C.c_void_p, _P(C.c_int64), _P(C.c_int64), _P(C.c_int64)]),
     "msdp_get_dual_slack": (C.c_int, [C.c_void_p, _dp]),
@@ -260,6 +261,21 @@ def ritz_device(G, H):
     rank, status = C.c_int32(), C.c_int32()
     _check(load().msdp_debug_ritz_device(b, _dptr(G), _dptr(H), _dptr(theta), _dptr(W), C.byref(rank), C.byref(status)))
     return theta, W, rank.value, status.value
+
+
+def ritz_herm(G, H):
+    """The host Rayleigh-Ritz stage of the block eigen-solver's complex panel alone (msdp_debug_ritz_herm; no GPU touched):
+    H c = theta G c for complex Hermitian G, H of order bc.  Returns (theta, W, rank): theta ascending and +inf beyond rank, W
+    complex with W^H G W = I on its first rank columns and zero columns beyond."""
+    G = np.ascontiguousarray(G, dtype=np.complex128)
+    H = np.ascontiguousarray(H, dtype=np.complex128)
+    bc = G.shape[0]
+    if G.shape != (bc, bc) or H.shape != (bc, bc):
+        raise ValueError("ritz_herm: G and H must be square and of the same order")
+    theta, W = np.zeros(bc), np.zeros((bc, bc), dtype=np.complex128)
+    rank = C.c_int32()
+    _check(load().msdp_debug_ritz_herm(bc, _dptr(G), _dptr(H), _dptr(theta), _dptr(W), C.byref(rank)))
+    return theta, W, rank.value
 
 
 def hermitian_csc(Cmat):
@@ -855,6 +871,11 @@ class Handle:
         _check(self._lib.msdp_linesearch_accept(self._h))
 
     def escape_eigs(self, k, tol=1e-10, maxit=500):
+        """(lam, V, lambda_max, steps) of msdp_escape_eigs: the k bottom eigenpairs of S = C - diag(z) at the resident point
+        (missing pairs: +inf and a zero vector; escape_info() says how many are real).  V is (n, k), complex on an
+        onlyunitdiag_hermitian handle.  Which eigen-solver ran: escape_method().  A Hermitian handle takes the Lanczos path on the
+        real view unless set_option("escape_method", 2) asks for the block eigen-solver on a complex panel (single rank,
+        n >= 256, k <= 56); maxit is then the budget of filter steps."""
         lam = np.empty(k)
         V = np.empty((self.n, k), order="F", dtype=np.complex128 if self.hermitian else np.float64)   # complex: (re, im) pairs, column by column
         lmax = C.c_double()

@@ -29,6 +29,7 @@
 #include <math.h>
 #include <algorithm>
 #include <chrono>
+#include <complex>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -40,6 +41,8 @@ struct BeOp {                            // S = C - diag(z) with sparse C (all n
     const int* rp; const int* ci; const double* cv; const double* z;     // z may be null (explicit S of the affine kinds)
     int ellW; int64_t ell_stride; const int* ellc; const double* ellv;   // optional ELL copy of the same rows
     const double* M;                     // dense operand (n x nS row-major, msdp_dense.hip layout) or null
+    const double2* hzv; const double2* hzell;   // Hermitian C (COST_HERM): the complex values of the rows beside rp / ci and ellc (cv and ellv
+                                         //   are null); n then counts COMPLEX rows, a panel row is b/2 complex numbers, one per double2
 };
 
 #define BE_ELL_MAXW 8
@@ -110,6 +113,93 @@ __global__ __launch_bounds__(MSDP_BLOCK) void k_be_step(BeOp a, const double* __
             be_spmm_row<LPR, NCH, ELL>(a, row, sub, Xin, acc);
 #pragma unroll
             for (int ch = 0; ch < NCH; ++ch) {
+                double2 o2;
+                o2.x = fma(f1, acc[ch].x, fma(g, x[ch].x, -f2 * pv[ch].x));
+                o2.y = fma(f1, acc[ch].y, fma(g, x[ch].y, -f2 * pv[ch].y));
+                st2(Xio + (int64_t)row * a.b + 2 * sub + ch * 2 * LPR, o2);
+            }
+        }
+    }
+}
+
+// The same gather for a Hermitian C = A + iB: the panel form of spmm_row_herm (msdp_device.h).  A double2 of the panel is one
+// complex number, acc += c * x with the values of the stored ROW (the conjugate of the CSC column, msdp_hermitian.hip), entries
+// in ascending column order, the real-part product first; ELL padding is (row, 0 + 0i).
+template <int LPR, int NCH, bool ELL>
+__device__ __forceinline__ void be_spmm_row_herm(const BeOp& a, int row, int sub, const double* __restrict__ X, double2 (&acc)[NCH]) {
+    if (ELL) {
+        int c[BE_ELL_MAXW];
+        double2 v[BE_ELL_MAXW];
+#pragma unroll
+        for (int w = 0; w < BE_ELL_MAXW; ++w) {
+            const bool ok = w < a.ellW;
+            c[w] = ok ? a.ellc[(int64_t)w * a.ell_stride + row] : row;
+            v[w] = ok ? a.hzell[(int64_t)w * a.ell_stride + row] : make_double2(0.0, 0.0);
+        }
+#pragma unroll
+        for (int w = 0; w < BE_ELL_MAXW; ++w) {
+            if (w < a.ellW) {
+                const double* src = X + (int64_t)c[w] * a.b + 2 * sub;
+#pragma unroll
+                for (int ch = 0; ch < NCH; ++ch) {
+                    const double2 x = ld2(src + ch * 2 * LPR);
+                    acc[ch].x = fma(v[w].x, x.x, acc[ch].x); acc[ch].x = fma(-v[w].y, x.y, acc[ch].x);
+                    acc[ch].y = fma(v[w].x, x.y, acc[ch].y); acc[ch].y = fma(v[w].y, x.x, acc[ch].y);
+                }
+            }
+        }
+        return;
+    }
+    const int start = a.rp[row], end = a.rp[row + 1];
+#pragma unroll 4
+    for (int k = start; k < end; ++k) {
+        const int c = a.ci[k];
+        const double2 v = a.hzv[k];
+        const double* src = X + (int64_t)c * a.b + 2 * sub;
+#pragma unroll
+        for (int ch = 0; ch < NCH; ++ch) {
+            const double2 x = ld2(src + ch * 2 * LPR);
+            acc[ch].x = fma(v.x, x.x, acc[ch].x); acc[ch].x = fma(-v.y, x.y, acc[ch].x);
+            acc[ch].y = fma(v.x, x.y, acc[ch].y); acc[ch].y = fma(v.y, x.x, acc[ch].y);
+        }
+    }
+}
+
+// k_be_step for a Hermitian C: the same recurrence (z and the scalars are real, so the epilogue acts on the two halves of a
+// complex number alike), the complex gather.  a.n complex rows, a.b = 2 * (complex columns).
+template <int LPR, int NCH, bool ELL, bool PREV>
+__global__ __launch_bounds__(MSDP_BLOCK) void k_be_step_herm(BeOp a, const double* __restrict__ Xin, double* __restrict__ Xio,
+                                                              double f1, double cs, double f2) {
+    int lo, hi;
+    msdp_chunk_rows(a.n, a.G, lo, hi);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    constexpr int RPW = 64 / LPR;
+    const int sub = lane & (LPR - 1), rsub = lane / LPR;
+    for (int row0 = lo + wave * RPW; row0 < hi; row0 += MSDP_WAVES * RPW) {
+        const int row = row0 + rsub;
+        if (row < hi) {
+            // eight chunks a lane (64 complex columns on 8 lanes): the row's own entries of Xin and Xio are read behind the gather,
+            // not ahead of it -- three sets of 32 registers beside the gathered values do not fit the 128 of a 16-wave workgroup
+            constexpr bool LATE = NCH >= 8;
+            double2 acc[NCH], x[NCH], pv[NCH];
+#pragma unroll
+            for (int ch = 0; ch < NCH; ++ch) {
+                acc[ch] = make_double2(0.0, 0.0);
+                if (!LATE) {
+                    const int64_t o = (int64_t)row * a.b + 2 * sub + ch * 2 * LPR;
+                    x[ch] = ld2(Xin + o);
+                    pv[ch] = PREV ? ld2(Xio + o) : make_double2(0.0, 0.0);
+                }
+            }
+            const double g = -f1 * (a.z[row] + cs);
+            be_spmm_row_herm<LPR, NCH, ELL>(a, row, sub, Xin, acc);
+#pragma unroll
+            for (int ch = 0; ch < NCH; ++ch) {
+                if (LATE) {
+                    const int64_t o = (int64_t)row * a.b + 2 * sub + ch * 2 * LPR;
+                    x[ch] = ld2(Xin + o);
+                    pv[ch] = PREV ? ld2(Xio + o) : make_double2(0.0, 0.0);
+                }
                 double2 o2;
                 o2.x = fma(f1, acc[ch].x, fma(g, x[ch].x, -f2 * pv[ch].x));
                 o2.y = fma(f1, acc[ch].y, fma(g, x[ch].y, -f2 * pv[ch].y));
@@ -290,10 +380,21 @@ __global__ void k_be_extract(int n, int b, int k, const double* __restrict__ X, 
     }
 }
 
+// Hermitian C: the first k complex columns of the panel (n complex rows, b doubles a row) -> k vectors in the real view,
+// column-major with stride 2n -- V[c*2n + 2*row + {0, 1}] = X[row*b + 2c + {0, 1}], what msdp_escape_eigs returns for the kind
+__global__ void k_be_extract_herm(int n, int b, int k, const double* __restrict__ X, double* __restrict__ V) {
+    const int64_t tot = (int64_t)n * k;
+    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < tot; e += (int64_t)gridDim.x * blockDim.x) {
+        const int c = (int)(e / n), row = (int)(e - (int64_t)c * n);
+        st2(V + 2 * e, ld2(X + (int64_t)row * b + 2 * c));
+    }
+}
+
 // ---------------------------------------------------------------- host side: small dense symmetric algebra
 // Symmetric eigen-decomposition, Householder tridiagonalisation + implicit QL (the classical EISPACK tred2 / tql2 pair).
 // A: n x n row-major, symmetric, destroyed.  w ascending, Z row-major with the eigenvectors in its ROWS
 // (row i of Z = eigenvector of w[i]): the QL rotations then act on two contiguous rows.
+static void be_tridiag_ql(int n, std::vector<double>& d, std::vector<double>& e, std::vector<double>& w, std::vector<double>& Z);
 static void be_sym_eig(int n, std::vector<double>& A, std::vector<double>& w, std::vector<double>& Z) {
     std::vector<double> d(n), e(n);
     auto V = [&](int i, int j) -> double& { return A[(size_t)i * n + j]; };
@@ -347,6 +448,13 @@ static void be_sym_eig(int n, std::vector<double>& A, std::vector<double>& w, st
     for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) Z[(size_t)j * n + i] = A[(size_t)i * n + j];
     for (int i = 1; i < n; ++i) e[i - 1] = e[i];
     e[n - 1] = 0.0;
+    be_tridiag_ql(n, d, e, w, Z);
+}
+
+// Implicit QL on the real symmetric tridiagonal matrix (d: diagonal, e[i]: the entry between i and i + 1, e[n-1] = 0; both
+// destroyed).  Z (n x n row-major) holds in its ROWS the basis the tridiagonal form refers to and ends with the eigenvectors in
+// its rows, sorted like w (ascending).
+static void be_tridiag_ql(int n, std::vector<double>& d, std::vector<double>& e, std::vector<double>& w, std::vector<double>& Z) {
     double f = 0.0, tst1 = 0.0;
     const double eps = 2.220446049250313e-16;
     for (int l = 0; l < n; ++l) {
@@ -487,11 +595,188 @@ static int be_ritz(int b, std::vector<double>& Gm, std::vector<double>& Hm, std:
     return r;
 }
 
+// ---------------------------------------------------------------- host side: the same algebra for a complex panel (COST_HERM)
+typedef std::complex<double> becx;
+
+// Hermitian eigen-decomposition: Householder reflections to a Hermitian tridiagonal form, a diagonal of phases that makes its
+// off-diagonal real, be_tridiag_ql on that, and the back-transformation.  A: n x n row-major, Hermitian, destroyed.  w ascending,
+// U row-major with the eigenvectors in its COLUMNS (orthonormal also inside a repeated eigenvalue: each complex direction once).
+static void be_herm_eig(int n, std::vector<becx>& A, std::vector<double>& w, std::vector<becx>& U) {
+    auto a = [&](int i, int j) -> becx& { return A[(size_t)i * n + j]; };
+    std::vector<becx> Q((size_t)n * n, becx(0.0)), v(n), pvec(n);
+    for (int i = 0; i < n; ++i) Q[(size_t)i * n + i] = 1.0;
+    for (int k = 0; k + 2 < n; ++k) {
+        // reflection H = I - 2 v v^H on the indices k+1 .. n-1 that sends A[k+1:, k] to alpha e_1
+        const int m0 = k + 1;
+        double xn = 0.0;
+        for (int i = m0; i < n; ++i) xn += std::norm(a(i, k));
+        xn = sqrt(xn);
+        double tail = 0.0;
+        for (int i = m0 + 1; i < n; ++i) tail += std::norm(a(i, k));
+        if (!(tail > 0.0)) continue;                      // already tridiagonal in this column
+        const becx x0 = a(m0, k);
+        const becx ph = std::abs(x0) > 0.0 ? x0 / std::abs(x0) : becx(1.0);
+        const becx alpha = -ph * xn;
+        double vn = 0.0;
+        for (int i = m0; i < n; ++i) { v[i] = a(i, k) - (i == m0 ? alpha : becx(0.0)); vn += std::norm(v[i]); }
+        vn = 1.0 / sqrt(vn);
+        for (int i = m0; i < n; ++i) v[i] *= vn;
+        a(m0, k) = alpha; a(k, m0) = std::conj(alpha);
+        for (int i = m0 + 1; i < n; ++i) { a(i, k) = 0.0; a(k, i) = 0.0; }
+        // trailing block B <- H B H = B - v q^H - q v^H,  p = 2 B v,  q = p - (v^H p) v
+        double vp = 0.0;                                  // v^H p is real for a Hermitian B
+        for (int i = m0; i < n; ++i) {
+            becx s = 0.0;
+            for (int j = m0; j < n; ++j) s += a(i, j) * v[j];
+            pvec[i] = 2.0 * s;
+            vp += (std::conj(v[i]) * pvec[i]).real();
+        }
+        for (int i = m0; i < n; ++i) pvec[i] -= vp * v[i];
+        for (int i = m0; i < n; ++i)
+            for (int j = m0; j < n; ++j) a(i, j) -= v[i] * std::conj(pvec[j]) + pvec[i] * std::conj(v[j]);
+        // Q <- Q H
+        for (int i = 0; i < n; ++i) {
+            becx s = 0.0;
+            for (int j = m0; j < n; ++j) s += Q[(size_t)i * n + j] * v[j];
+            s *= 2.0;
+            for (int j = m0; j < n; ++j) Q[(size_t)i * n + j] -= s * std::conj(v[j]);
+        }
+    }
+    // T = D T_real D^H with D = diag(ph_j), ph_0 = 1, ph_{j+1} = ph_j * t_j / |t_j| for the sub-diagonal entries t_j
+    std::vector<double> d(n), e(n, 0.0), Z((size_t)n * n, 0.0);
+    std::vector<becx> phs(n, becx(1.0));
+    for (int j = 0; j < n; ++j) d[j] = a(j, j).real();
+    for (int j = 0; j + 1 < n; ++j) {
+        const becx t = a(j + 1, j);
+        const double at = std::abs(t);
+        e[j] = at;
+        phs[j + 1] = at > 0.0 ? phs[j] * (t / at) : phs[j];
+    }
+    for (int i = 0; i < n; ++i) Z[(size_t)i * n + i] = 1.0;
+    be_tridiag_ql(n, d, e, w, Z);
+    // eigenvector j = Q D z_j (z_j: row j of Z)
+    U.assign((size_t)n * n, becx(0.0));
+    for (int i = 0; i < n; ++i)
+        for (int c = 0; c < n; ++c) {
+            const becx qd = Q[(size_t)i * n + c] * phs[c];
+            if (qd == becx(0.0)) continue;
+            for (int j = 0; j < n; ++j) U[(size_t)i * n + j] += qd * Z[(size_t)j * n + c];
+        }
+}
+
+// be_ritz for a complex panel: H c = theta G c with complex Hermitian G = X^H X, H = X^H S X of order bc (row-major, made
+// Hermitian here).  The contract of be_ritz: theta ascending (+inf beyond r), W (bc x bc row-major) with W^H G W = I on its first r
+// columns and zeros beyond, r returned.  Complex Cholesky of G where it is well conditioned, else the eigen-basis of G with the
+// directions below 1e-13 * max dropped.  Every complex direction appears once: nothing here sees the real view, on which each
+// eigenvalue would come twice (v and i v).
+static int be_ritz_herm(int bc, std::vector<becx>& Gm, std::vector<becx>& Hm, std::vector<double>& theta, std::vector<becx>& W) {
+    const int b = bc;
+    for (int i = 0; i < b; ++i) {
+        Gm[(size_t)i * b + i] = Gm[(size_t)i * b + i].real(); Hm[(size_t)i * b + i] = Hm[(size_t)i * b + i].real();
+        for (int j = i + 1; j < b; ++j) {
+            const becx g = 0.5 * (Gm[(size_t)i * b + j] + std::conj(Gm[(size_t)j * b + i])); Gm[(size_t)i * b + j] = g; Gm[(size_t)j * b + i] = std::conj(g);
+            const becx hh = 0.5 * (Hm[(size_t)i * b + j] + std::conj(Hm[(size_t)j * b + i])); Hm[(size_t)i * b + j] = hh; Hm[(size_t)j * b + i] = std::conj(hh);
+        }
+    }
+    double dmax = 0.0;
+    for (int i = 0; i < b; ++i) dmax = std::max(dmax, Gm[(size_t)i * b + i].real());
+    if (!(dmax > 0.0) || !std::isfinite(dmax)) return -1;
+    // T (b x r, row-major): X*T is orthonormal
+    std::vector<becx> T;
+    int r = b;
+    {
+        std::vector<becx> L(Gm);                         // lower Cholesky factor G = L L^H, row-major
+        bool ok = true;
+        for (int j = 0; j < b && ok; ++j) {
+            double s = L[(size_t)j * b + j].real();
+            for (int k = 0; k < j; ++k) s -= std::norm(L[(size_t)j * b + k]);
+            if (!(s > 1e-11 * dmax)) { ok = false; break; }
+            const double ljj = sqrt(s);
+            L[(size_t)j * b + j] = ljj;
+            for (int i = j + 1; i < b; ++i) {
+                becx t = L[(size_t)i * b + j];
+                for (int k = 0; k < j; ++k) t -= L[(size_t)i * b + k] * std::conj(L[(size_t)j * b + k]);
+                L[(size_t)i * b + j] = t / ljj;
+            }
+        }
+        if (ok) {
+            // T = L^{-H}: solve L^H T = I column by column (upper triangular result)
+            T.assign((size_t)b * b, becx(0.0));
+            for (int c = 0; c < b; ++c) {
+                for (int i = c; i >= 0; --i) {
+                    becx t = (i == c) ? 1.0 : 0.0;
+                    for (int k = i + 1; k <= c; ++k) t -= std::conj(L[(size_t)k * b + i]) * T[(size_t)k * b + c];
+                    T[(size_t)i * b + c] = t / L[(size_t)i * b + i].real();
+                }
+            }
+        } else {
+            std::vector<becx> Gc(Gm), gu;
+            std::vector<double> gw;
+            be_herm_eig(b, Gc, gw, gu);
+            const double gtop = gw[b - 1];
+            std::vector<int> keep;
+            for (int i = b - 1; i >= 0; --i) if (gw[i] > 1e-13 * gtop) keep.push_back(i);
+            r = (int)keep.size();
+            if (r < 1) return -1;
+            T.assign((size_t)b * r, becx(0.0));
+            for (int c = 0; c < r; ++c) {
+                const double sc = 1.0 / sqrt(gw[keep[c]]);
+                for (int i = 0; i < b; ++i) T[(size_t)i * r + c] = gu[(size_t)i * b + keep[c]] * sc;
+            }
+        }
+    }
+    // A = T^H H T (r x r)
+    std::vector<becx> HT((size_t)b * r, becx(0.0)), A((size_t)r * r, becx(0.0));
+    for (int i = 0; i < b; ++i)
+        for (int k = 0; k < b; ++k) {
+            const becx hik = Hm[(size_t)i * b + k];
+            if (hik == becx(0.0)) continue;
+            const becx* tk = &T[(size_t)k * r];
+            becx* o = &HT[(size_t)i * r];
+            for (int c = 0; c < r; ++c) o[c] += hik * tk[c];
+        }
+    for (int i = 0; i < b; ++i) {
+        const becx* ti = &T[(size_t)i * r];
+        const becx* hi = &HT[(size_t)i * r];
+        for (int a2 = 0; a2 < r; ++a2) {
+            const becx t = std::conj(ti[a2]);
+            if (t == becx(0.0)) continue;
+            becx* o = &A[(size_t)a2 * r];
+            for (int c = 0; c < r; ++c) o[c] += t * hi[c];
+        }
+    }
+    for (int i = 0; i < r; ++i) {
+        A[(size_t)i * r + i] = A[(size_t)i * r + i].real();
+        for (int j = i + 1; j < r; ++j) {
+            const becx s = 0.5 * (A[(size_t)i * r + j] + std::conj(A[(size_t)j * r + i])); A[(size_t)i * r + j] = s; A[(size_t)j * r + i] = std::conj(s);
+        }
+    }
+    std::vector<double> aw;
+    std::vector<becx> au;
+    be_herm_eig(r, A, aw, au);
+    theta.assign(b, INFINITY);
+    W.assign((size_t)b * b, becx(0.0));
+    for (int j = 0; j < r; ++j) theta[j] = aw[j];
+    for (int i = 0; i < b; ++i) {
+        const becx* ti = &T[(size_t)i * r];
+        becx* o = &W[(size_t)i * b];
+        for (int c = 0; c < r; ++c) {
+            const becx t = ti[c];
+            if (t == becx(0.0)) continue;
+            const becx* q = &au[(size_t)c * r];           // row c of the eigenvector matrix: entry c of every eigenvector
+            for (int j = 0; j < r; ++j) o[j] += t * q[j];
+        }
+    }
+    return r;
+}
+
 // ---------------------------------------------------------------- host side: the iteration
 struct BeMem {                                          // device workspace of one handle (msdp_handle_s::be)
     double* base = nullptr; size_t cap = 0;             // doubles
     double* hpin = nullptr; size_t hpin_cap = 0;        // pinned host staging (Gram matrices, residual partials, W, theta)
     double* prevV = nullptr; int prev_n = 0, prev_k = 0;   // bottom vectors of the previous call (n x prev_k column-major), own allocation
+    int prev_cw = 1;                                    // 2 where they are panel columns of a complex panel (Hermitian C): n complex rows, real
+                                                        //   columns 2c / 2c + 1 = re / im of vector c -- what k_be_init copies back as it stands
     double prev_a = 0.0;                                // lower filter edge the previous call ended with
     int64_t rr_device = 0, rr_host = 0, rr_fallback = 0;   // Rayleigh-Ritz stages since the handle was created, by where their algebra
                                                         //   ran: device (k_be_ritz), host, host after the device kernel handed the stage back
@@ -513,6 +798,16 @@ void msdp_blockeig_release(msdp_handle h) {
 template <int LPR, int NCH>
 static void be_launch_step(msdp_handle h, const BeOp& a, const double* Xin, double* Xio, double f1, double cs, double f2, bool prev) {
     const dim3 grid(a.G), block(MSDP_BLOCK);
+    if (a.hzv) {                                         // Hermitian C: the complex gather
+        if (a.ellW > 0) {
+            if (prev) hipLaunchKernelGGL((k_be_step_herm<LPR, NCH, true, true>), grid, block, 0, h->stream, a, Xin, Xio, f1, cs, f2);
+            else hipLaunchKernelGGL((k_be_step_herm<LPR, NCH, true, false>), grid, block, 0, h->stream, a, Xin, Xio, f1, cs, f2);
+        } else {
+            if (prev) hipLaunchKernelGGL((k_be_step_herm<LPR, NCH, false, true>), grid, block, 0, h->stream, a, Xin, Xio, f1, cs, f2);
+            else hipLaunchKernelGGL((k_be_step_herm<LPR, NCH, false, false>), grid, block, 0, h->stream, a, Xin, Xio, f1, cs, f2);
+        }
+        return;
+    }
     if (a.ellW > 0) {
         if (prev) hipLaunchKernelGGL((k_be_step<LPR, NCH, true, true>), grid, block, 0, h->stream, a, Xin, Xio, f1, cs, f2);
         else hipLaunchKernelGGL((k_be_step<LPR, NCH, true, false>), grid, block, 0, h->stream, a, Xin, Xio, f1, cs, f2);
@@ -574,6 +869,58 @@ static int be_rotate(msdp_handle h, int b, int n, const double* X, const double*
     return 0;
 }
 
+// The host part of a Rayleigh-Ritz stage on a complex panel (Hermitian C; bc = b/2 complex columns), from the real b x b Gram
+// matrices in gout: G = X^H X and H = X^H S X are packed as in msdp_hfactor_gram (Re G_ab = Gr[2a,2b] + Gr[2a+1,2b+1],
+// Im G_ab = Gr[2a,2b+1] - Gr[2a+1,2b]), be_ritz_herm solves the order-bc problem, and W goes back as the real b x b matrix with
+// the block [wr, wi; -wi, wr] per complex entry (msdp_hfactor_rotate) with theta[2a] = theta[2a+1], so that k_be_rotate<b> forms
+// X*W and the residual partials unchanged.  out.theta / out.res / out.rank count COMPLEX columns; noise refill from real column 2r.
+static int be_rayleigh_ritz_herm(msdp_handle h, const BeOp& a, BeMem& m, const double* X, const double* SX, double* Xn, const double* gout,
+                                 double* Wd, double* rpart, unsigned seed, BeRR& out, double* host_s) {
+    const int b = a.b, bc = a.b / 2, n = a.n;
+    double* hp = m.hpin;
+    HIPCHK(msdp_memcpy_async(hp, gout, (size_t)2 * b * b * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<becx> Gm((size_t)bc * bc), Hm((size_t)bc * bc), W;
+    for (int q = 0; q < 2; ++q) {
+        const double* Gr = hp + (size_t)q * b * b;
+        std::vector<becx>& dst = q ? Hm : Gm;
+        for (int i = 0; i < bc; ++i)
+            for (int j = 0; j < bc; ++j)
+                dst[(size_t)i * bc + j] = becx(Gr[(size_t)(2 * i) * b + 2 * j] + Gr[(size_t)(2 * i + 1) * b + 2 * j + 1],
+                                               Gr[(size_t)(2 * i) * b + 2 * j + 1] - Gr[(size_t)(2 * i + 1) * b + 2 * j]);
+    }
+    const int r = be_ritz_herm(bc, Gm, Hm, out.theta, W);
+    if (r < 1) { msdp_set_error("block eigen-solver: the Rayleigh-Ritz stage broke down (non-finite or zero Gram matrix)"); return MSDP_EHIP; }
+    out.rank = r;
+    double* hw = hp + (size_t)2 * b * b;                 // W as a real b x b matrix, then theta (finite values only)
+    for (int i = 0; i < bc; ++i)
+        for (int j = 0; j < bc; ++j) {
+            const double wr = W[(size_t)i * bc + j].real(), wi = W[(size_t)i * bc + j].imag();
+            hw[(size_t)(2 * i) * b + 2 * j] = wr;      hw[(size_t)(2 * i) * b + 2 * j + 1] = wi;
+            hw[(size_t)(2 * i + 1) * b + 2 * j] = -wi; hw[(size_t)(2 * i + 1) * b + 2 * j + 1] = wr;
+        }
+    for (int j = 0; j < bc; ++j) hw[(size_t)b * b + 2 * j] = hw[(size_t)b * b + 2 * j + 1] = j < r ? out.theta[j] : 0.0;
+    if (host_s) *host_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    HIPCHK(msdp_memcpy_async(Wd, hw, ((size_t)b * b + b) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    int rc = be_rotate(h, b, n, X, SX, Wd, Xn, rpart);
+    if (rc) return rc;
+    if (r < bc) {
+        hipLaunchKernelGGL(k_be_init, dim3(1024), dim3(256), 0, h->stream, n, b, (const double*)nullptr, 0, 0, (const double*)nullptr, 0, seed, 2 * r, Xn);
+        HIPCHK(hipGetLastError());
+    }
+    double* hr = hw + (size_t)b * b + b;
+    HIPCHK(msdp_memcpy_async(hr, rpart, (size_t)BE_ROT_BLOCKS * b * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    out.res.assign(bc, INFINITY);
+    for (int j = 0; j < r; ++j) {
+        double s = 0.0;
+        for (int q = 0; q < BE_ROT_BLOCKS; ++q) s += hr[(size_t)q * b + 2 * j] + hr[(size_t)q * b + 2 * j + 1];
+        out.res[j] = sqrt(s > 0.0 ? s : 0.0);
+    }
+    return 0;
+}
+
 // Rayleigh-Ritz on the panel X (SX = scratch, receives S*X; Xn receives the Ritz vectors, columns >= rank refilled with
 // noise).  X, SX and Xn are three different panels.
 static int be_rayleigh_ritz(msdp_handle h, const BeOp& a, BeMem& m, const double* X, double* SX, double* Xn,
@@ -588,6 +935,7 @@ static int be_rayleigh_ritz(msdp_handle h, const BeOp& a, BeMem& m, const double
     hipLaunchKernelGGL(k_be_gram_sum, dim3((2 * b * b + 255) / 256), dim3(256), 0, h->stream, 2 * b * b, BE_GRAM_BLOCKS, (const double*)gpart, gout);
     HIPCHK(hipGetLastError());
     double* hp = m.hpin;
+    if (a.hzv) { ++m.rr_host; return be_rayleigh_ritz_herm(h, a, m, X, SX, Xn, gout, Wd, rpart, seed, out, host_s); }   // complex panel: host stage only
     if (h->tune.escape_rr == 1 && msdp_beritz_supported(b)) {
         // The whole stage enqueued back to back; ONE copy (theta[b], res[b], rank, status) and ONE synchronisation.  k_be_rotate
         // writes Xn and rpart only, never X or SX, and k_be_ritz leaves gout as it found it: a stage the kernel hands back
@@ -641,6 +989,13 @@ static int be_rayleigh_ritz(msdp_handle h, const BeOp& a, BeMem& m, const double
 int msdp_blockeig_eligible(msdp_handle h, const double* Mdev, bool w_loc) {
     if (h->tune.escape_method == 1) return 0;
     if (w_loc) return 0;                                                  // sharded dense product: Lanczos path
+    if (!Mdev && h->d.costkind == COST_HERM) {
+        // Hermitian C: the complex panel (k_be_step_herm, be_ritz_herm) on request only -- auto keeps the Lanczos path on the real
+        // view until the route is timed on the device; single rank (the kind has no sharded form), the real kind's lower limit
+        if (h->tune.escape_method != 2) return 0;
+        if (h->nranks != 1 || h->use_comm || h->lgroup) return 0;
+        return h->d.n >= 256;
+    }
     if (Mdev || h->d.costkind != COST_SPARSE) {
         // dense operand (explicit S of the affine kinds, dense C): the filter step is the fp64-MFMA panel product; single rank,
         // matrix order a multiple of nothing in particular (the contraction pads), panels of 64 columns
@@ -681,16 +1036,22 @@ int msdp_blockeig_run(msdp_handle h, int n, const int* rp, const int* ci, const 
     const bool dbg = h->tune.esc_debug != 0;
     const auto t_start = std::chrono::steady_clock::now();
     // ---- block width
+    // Hermitian C: n complex rows, Ypt the factor at its real stride (p = 2 * complex width real columns: a complex column of Y is
+    // two adjacent real columns of the panel, as k_be_init copies them), cw = 2 doubles per panel column and per stored vector entry
+    const bool herm = !Mdense && h->d.costkind == COST_HERM;
+    const int cw = herm ? 2 : 1;
     int ny = (use_y && Ypt) ? p : 0;
-    int nprev = (!cold && h->tune.escape_warm && m.prevV && m.prev_n == n) ? m.prev_k : 0;
+    int nprev = (!cold && h->tune.escape_warm && m.prevV && m.prev_n == n && m.prev_cw == cw) ? m.prev_k : 0;   // (panel columns, like ny)
     int b = h->tune.be_width > 0 ? h->tune.be_width : 64;
     if (b != 32 && b != 64 && b != 128) b = 64;
-    if (h->tune.be_width <= 0 && ny + nprev + 8 > b && !Mdense) b = 128;
-    if (k + 8 > b && !Mdense) b = 128;
+    if (h->tune.be_width <= 0 && ny + nprev + 8 * cw > b && !Mdense) b = 128;
+    if (cw * (k + 8) > b && !Mdense) b = 128;
     if (Mdense) b = 64;
+    if (herm && k + 8 > 64) { msdp_set_error("block eigen-solver: at most 56 eigenpairs per call for a Hermitian cost matrix (panels of 64 complex columns; k = %d)", k); return MSDP_EINVAL; }
     if (k > 64) { msdp_set_error("block eigen-solver: at most 64 eigenpairs per call"); return MSDP_EINVAL; }
-    if (ny > b - 8 - std::min(nprev, 8)) ny = b - 8 - std::min(nprev, 8);     // leave room for noise columns (and some warm ones)
-    if (ny + nprev > b - 8) nprev = b - 8 - ny;
+    if (ny > b - cw * (8 + std::min(nprev / cw, 8))) ny = b - cw * (8 + std::min(nprev / cw, 8));     // leave room for noise columns (and some warm ones)
+    if (ny + nprev > b - 8 * cw) nprev = b - 8 * cw - ny;
+    const int bw = b / cw;                               // vectors in the panel
     // ---- workspace: three panels, Gram partials, Gram sums, [W | theta], residual partials, the result record of the device stage
     const size_t panel = (size_t)n * b;
     const size_t need = 3 * panel + (size_t)BE_GRAM_BLOCKS * 2 * b * b + (size_t)2 * b * b + (size_t)b * b + b + (size_t)BE_ROT_BLOCKS * b + 2 * b + 2 + 64;
@@ -723,8 +1084,11 @@ int msdp_blockeig_run(msdp_handle h, int n, const int* rp, const int* ci, const 
     a.n = n; a.b = b; a.rp = rp; a.ci = ci; a.cv = cv; a.z = z;
     a.ellW = 0; a.ell_stride = 0; a.ellc = nullptr; a.ellv = nullptr;
     a.M = Mdense;
+    a.hzv = herm ? h->d.hzv : nullptr; a.hzell = nullptr;
+    if (herm && (!a.hzv || n != h->d.n)) { msdp_set_error("block eigen-solver: a Hermitian handle runs on its own %d complex rows", h->d.n); return MSDP_ESTATE; }
     if (Mdense && b != 64) { msdp_set_error("block eigen-solver: the dense route works on 64-wide panels"); return MSDP_EUNSUPPORTED; }
-    if (!Mdense && own_rows && h->d.ellW > 0 && h->d.n_loc == n) { a.ellW = h->d.ellW; a.ell_stride = h->d.ell_stride; a.ellc = h->d.ellc; a.ellv = h->d.ellv; }
+    if (!Mdense && own_rows && h->d.ellW > 0 && h->d.n_loc == n) { a.ellW = h->d.ellW; a.ell_stride = h->d.ell_stride; a.ellc = h->d.ellc; a.ellv = h->d.ellv; a.hzell = herm ? h->d.hzell : nullptr; }
+    if (herm && !a.hzell) a.ellW = 0;                    // (the fixed-width copy exists with its complex values or not at all)
     {
         // grid: one workgroup per CU while its rows fit one pass of eight lanes per row (16 waves x 8 rows = 128 rows), two
         // beyond; measured on G81 (tools/archive/blockeig_tune.py): 256 workgroups x 8 lanes 19.2 ms for the cold check, 512 x 16 lanes
@@ -810,7 +1174,7 @@ int msdp_blockeig_run(msdp_handle h, int n, const int* rp, const int* ci, const 
         const int rk = rr.rank;
         const double gap_ref = rr.theta[std::min(rk - 1, std::max(k, rk / 2))];   // a Ritz value well inside the block: converged far better than the top
         worst = 0.0;
-        bool ok = rk >= std::min(k, b);
+        bool ok = rk >= std::min(k, bw);
         for (int i = 0; i < std::min(k, rk) && ok; ++i) {
             if (i > 0 && !(rr.theta[i] < 0.0)) break;
             // Beyond index 0 only SIGNIFICANTLY negative values are waited for.  The near-kernel of S can be wider than the block
@@ -843,22 +1207,37 @@ int msdp_blockeig_run(msdp_handle h, int n, const int* rp, const int* ci, const 
                          rounds, degree, aedge, a0, rr.theta[0], rr.theta[std::min(k, rk) - 1], rr.theta[rk - 1], rr.res[0], rk, worst, ok ? "converged" : "");
         if (ok && rounds >= (cold ? 3 : 2)) { converged = true; break; }
     }
+    if (herm) {
+        // The Ritz vectors of the last stage are X*W with W from the Gram matrix of a FILTERED block, whose condition number the
+        // filter drives up to the 1e11 the Cholesky route accepts: they are orthonormal to eps * cond(G) only (3.8e-8 seen on the
+        // norm of a returned vector at n = 1031, "hub" rows).  msdp_escape_eigs promises vectors orthonormal in the complex inner
+        // product for this kind, so one more stage runs on the Ritz vectors themselves -- G = I to that error, the same subspace
+        // and Ritz values, vectors orthonormal to rounding -- for one product, one Gram pass and one order-bc problem per call.
+        BeRR rp;
+        if ((rc = be_rayleigh_ritz(h, a, m, X, T1, T2, gpart, gout, Wd, rpart, seed + 7919u, rp, &host_s))) return rc;
+        degree += 1;
+        if (rp.rank >= rr.rank) { std::swap(X, T2); rr = rp; }
+    }
     // ---- outputs
     const int rk = rr.rank;
     for (int t = 0; t < k; ++t) lam[t] = t < rk ? rr.theta[t] : INFINITY;
-    hipLaunchKernelGGL(k_be_extract, dim3(1024), dim3(256), 0, h->stream, n, b, std::min(k, rk), (const double*)X, V_dev);
+    if (herm) hipLaunchKernelGGL(k_be_extract_herm, dim3(1024), dim3(256), 0, h->stream, n, b, std::min(k, rk), (const double*)X, V_dev);
+    else hipLaunchKernelGGL(k_be_extract, dim3(1024), dim3(256), 0, h->stream, n, b, std::min(k, rk), (const double*)X, V_dev);
     HIPCHK(hipGetLastError());
-    if (rk < k) HIPCHK(hipMemsetAsync(V_dev + (size_t)rk * n, 0, (size_t)(k - rk) * n * sizeof(double), h->stream));
+    if (rk < k) HIPCHK(hipMemsetAsync(V_dev + (size_t)rk * n * cw, 0, (size_t)(k - rk) * n * cw * sizeof(double), h->stream));
     if (!cold) {
         // warm start of the next call: the bottom vectors found now, and the filter edge reached
-        const int kp = std::min(std::min(k, rk), 16);
-        if (!m.prevV || m.prev_n != n || m.prev_k < kp) {
+        const int kp = cw * std::min(std::min(k, rk), 16);
+        if (!m.prevV || m.prev_n != n || m.prev_cw != cw || m.prev_k < kp) {
             if (m.prevV) { (void)hipStreamSynchronize(h->stream); (void)hipFree(m.prevV); m.prevV = nullptr; }
-            if (hipMalloc((void**)&m.prevV, (size_t)n * 16 * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); m.prevV = nullptr; m.prev_n = 0; m.prev_k = 0; }
+            if (hipMalloc((void**)&m.prevV, (size_t)n * 16 * cw * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); m.prevV = nullptr; m.prev_n = 0; m.prev_k = 0; }
         }
         if (m.prevV) {
-            HIPCHK(msdp_memcpy_async(m.prevV, V_dev, (size_t)n * kp * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-            m.prev_n = n; m.prev_k = kp; m.prev_a = rr.theta[rk - 1];
+            // Hermitian C: the first kp REAL columns of the panel as they stand (column-major over the n complex rows), which
+            // k_be_init puts back at the same parity whatever the width of the next call's panel
+            if (herm) { hipLaunchKernelGGL(k_be_extract, dim3(1024), dim3(256), 0, h->stream, n, b, kp, (const double*)X, m.prevV); HIPCHK(hipGetLastError()); }
+            else HIPCHK(msdp_memcpy_async(m.prevV, V_dev, (size_t)n * kp * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+            m.prev_n = n; m.prev_k = kp; m.prev_cw = cw; m.prev_a = rr.theta[rk - 1];
         }
     }
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -889,6 +1268,20 @@ extern "C" int msdp_debug_ritz(int32_t b, const double* G, const double* H, doub
     if (r < 1) { msdp_set_error("debug_ritz: breakdown"); return MSDP_EINVAL; }
     memcpy(theta, th.data(), (size_t)b * sizeof(double));
     memcpy(W, w.data(), (size_t)b * b * sizeof(double));
+    *rank = r;
+    return 0;
+}
+// G, H, W: bc x bc complex, row-major, (re, im) interleaved
+extern "C" int msdp_debug_ritz_herm(int32_t bc, const double* G, const double* H, double* theta, double* W, int32_t* rank) {
+    if (bc < 1 || !G || !H || !theta || !W || !rank) { msdp_set_error("debug_ritz_herm: bad argument"); return MSDP_EINVAL; }
+    const size_t nn = (size_t)bc * bc;
+    std::vector<becx> g(nn), hm(nn), w;
+    for (size_t e = 0; e < nn; ++e) { g[e] = becx(G[2 * e], G[2 * e + 1]); hm[e] = becx(H[2 * e], H[2 * e + 1]); }
+    std::vector<double> th;
+    const int r = be_ritz_herm(bc, g, hm, th, w);
+    if (r < 1) { msdp_set_error("debug_ritz_herm: breakdown"); return MSDP_EINVAL; }
+    memcpy(theta, th.data(), (size_t)bc * sizeof(double));
+    for (size_t e = 0; e < nn; ++e) { W[2 * e] = w[e].real(); W[2 * e + 1] = w[e].imag(); }
     *rank = r;
     return 0;
 }

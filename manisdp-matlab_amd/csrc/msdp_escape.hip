@@ -993,6 +993,11 @@ static int escape_impl_once(msdp_handle h, int k, double tol, int maxit, double*
         const auto tb1 = std::chrono::steady_clock::now();
         // dense operand: the explicit S of the affine kinds (no z), or the dense cost matrix of onlyunitdiag (S = C - diag(z))
         const double* Mdense = Mdev ? Mdev : (d.costkind == COST_DENSE ? (const double*)d.Cd : (const double*)nullptr);
+        // Hermitian C: the lambda_max run above worked on the real view (length n = 2 d.n); the block iteration takes the d.n
+        // complex rows and the factor itself (real stride, 2 * complex width real columns) and writes k vectors of length n to Q
+        if (!rc && herm) rc = msdp_blockeig_run(h, d.n, d.rowptr, d.colind, nullptr, c.z, true, d.Y[cur], d.ld, d.p, k, tol, maxdeg, lmx, lres, lmin_est,
+                                                cold, use_y, lam_out, Q, &deg, &conv, &err, &lower, nullptr);
+        else
         if (!rc) rc = msdp_blockeig_run(h, n, c.rp, c.ci, c.cv, c.z, !rep_sparse, c.Ypt, c.ld, c.p, k, tol, maxdeg, lmx, lres, lmin_est, cold, use_y,
                                         lam_out, Q, &deg, &conv, &err, &lower, Mdense);
         if (!rc) {

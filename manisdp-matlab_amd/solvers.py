@@ -459,7 +459,8 @@ def _onlyunitdiag_hermitian_impl(C, o, verbose, rng):
     library call.  Extra option fields: ``hermitian_factor`` ("host" | "device": the rank decision, the cut and the widening through
     msdp_hfactor_gram / _rotate / _append, the factor resident between the trustregions() calls) and ``round_phases`` = {"M",
     "trials", "sweeps", "seed"} (msdp_round_phases on the evaluated point: ``data["round"]`` = z, value, values, best, info, and k
-    for M >= 2).  ``data["factor_seconds"]``: what the factor costs between the trustregions() calls -- its transfers (after the
+    for M >= 2) and ``escape_method`` (device escape: 0 / 1 = Lanczos on the real view, the default; 2 = the block eigen-solver
+    on a complex panel where n >= 256; ``data["escape_method"]`` reports what the last escape call ran).  ``data["factor_seconds"]``: what the factor costs between the trustregions() calls -- its transfers (after the
     first upload), the rank decision, the cut and the widening."""
     Csp = _lib.hermitian_csc(sp.csc_matrix(C) if not sp.issparse(C) else C).tocsr()   # ValueError unless C == C^H exactly
     for name, what in (("round", "+1/-1 rounding belongs to the real problem"), ("comm", "a single-rank solve is needed")):
@@ -488,6 +489,11 @@ def _onlyunitdiag_hermitian_impl(C, o, verbose, rng):
     p = Y.shape[1]
     h = _lib.Handle.onlyunitdiag_hermitian(Csp, pcap=max(32, p + 2 * int(o["delta"])))
 
+    def setup():
+        if "escape_method" in o:                           # 0 auto and 1: Lanczos on the real view; 2: block eigen-solver on a complex panel (n >= 256)
+            h.set_option("escape_method", int(o["escape_method"]))
+        _set_device_options(h, o)
+
     def finish(run):
         if rounding is not None and run.obj is not None:       # options["round_phases"]: phases from the evaluated point
             M, trials, sweeps, seed, order = rounding
@@ -505,7 +511,7 @@ def _onlyunitdiag_hermitian_impl(C, o, verbose, rng):
         host_S=lambda z, Lam: Csp - sp.diags(z),           # (eigh of the complex S)
         fetch=h.get_point, normalise=_rows_complex, host_gram=lambda Y: Y.conj().T @ Y,   # :52-54 from Y^H Y
         device=(h.hfactor_gram, h.hfactor_rotate, h.hfactor_append) if device_factor else None,
-        setup=lambda: _set_device_options(h, o), finish=finish, reshape_last=True)
+        setup=setup, finish=finish, reshape_last=True)
     run = _manifold_loop(h, o, kind, Y, p, eig_mode, verbose)
     Y, z, data = run.Y, run.z, run.data
     data.update({"Y": Y, "S": (Csp - sp.diags(z)) if z is not None else None, "z": z, "dinf": run.dinf, "gradnorm": run.gradnorm,

@@ -7,7 +7,8 @@ width p = 16:
   (c) with --solve: ManiSDP_onlyunitdiag with the defaults on both forms (median of --runs solves after one warm-up solve).
 Both Hess-vecs run the stand-alone row kernels of msdp_launch_hess; tcg_path / persist_form tell which path the handle's
 trustregions() calls take (the embedded handle may take the persistent one, the Hermitian one cannot).  One JSON line.
-Usage: python tools/time_hermitian.py [--reps N] [--runs N] [--solve] [--n N] [--p P]"""
+--escape-method 2: the solves of the Hermitian form run the block eigen-solver of the escape on a complex panel (0: Lanczos).
+Usage: python tools/time_hermitian.py [--reps N] [--runs N] [--solve] [--n N] [--p P] [--escape-method {0,2}]"""
 import argparse
 import json
 import os
@@ -29,16 +30,16 @@ def _bench(h, Y, reps):
             "tcg_path": h.tcg_path(), "persist_form": h.persist_form()}
 
 
-def _solve(solvers, C, runs):
+def _solve(solvers, C, runs, extra=None):
     ts, out = [], None
     for rep in range(runs + 1):
         t0 = time.perf_counter()
-        Y, fval, data = solvers.ManiSDP_onlyunitdiag(C, {"tol": 1e-8}, verbose=False)
+        Y, fval, data = solvers.ManiSDP_onlyunitdiag(C, dict({"tol": 1e-8}, **(extra or {})), verbose=False)
         if rep:
             ts.append(time.perf_counter() - t0)
         out = {"fval": float(fval), "dinf": float(data["dinf"]), "status": int(data["status"]), "p": int(Y.shape[1]),
                "hessvecs": int(data["hessvecs"]), "iters": int(data["iters"]), "rtr_seconds": float(data["rtr_seconds"]),
-               "eig_seconds": float(data["eig_seconds"])}
+               "eig_seconds": float(data["eig_seconds"]), "escape_method_ran": int(data.get("escape_method", -1))}
     out["seconds"] = float(np.median(ts))
     out["all_seconds"] = [float(t) for t in ts]
     return out
@@ -52,6 +53,7 @@ def main():
     ap.add_argument("--p", type=int, default=16)
     ap.add_argument("--sigma", type=float, default=1.0)
     ap.add_argument("--solve", action="store_true")
+    ap.add_argument("--escape-method", type=int, choices=(0, 2), default=0)
     a = ap.parse_args()
     from manisdp_matlab_amd import _lib, problems, solvers
     _lib.load()
@@ -74,7 +76,7 @@ def main():
         h.close()
     out["embedded_over_hermitian"] = out["b_embedded"]["us"] / out["a_hermitian"]["us"]
     if a.solve:
-        out["c_solve_hermitian"] = _solve(solvers, C, a.runs)
+        out["c_solve_hermitian"] = _solve(solvers, C, a.runs, {"escape_method": a.escape_method})
         out["c_solve_embedded"] = _solve(solvers, Ce, a.runs)
         out["solve_embedded_over_hermitian"] = out["c_solve_embedded"]["seconds"] / out["c_solve_hermitian"]["seconds"]
     print(json.dumps(out), flush=True)

@@ -379,7 +379,7 @@ extern "C" int msdp_create_onlyunitblockdiag_csc(int64_t N, int32_t d, const int
     return 0;
 }
 
-// The pose-graph problem, (X_[ii])_{1..d,1..d} = I_d with one free row per block (msdp_pose.hip): C of order N = n (d + 1) in
+// The pose-graph problem, (X_[ii])_{1..d,1..d} = I_d with one free row per block (msdp_stiefel.hip, d.efree = 1): C of order N = n (d + 1) in
 // block CSR of block order d + 1; the manifold is productmanifold.m:160-166 over stiefelstackedfactory.m:53 and euclideanfactory.m:57
 extern "C" int msdp_create_posegraph_csc(int64_t N, int32_t d, const int64_t* jc, const int64_t* ir, const double* val,
                                          int32_t pcap, msdp_handle* out) {

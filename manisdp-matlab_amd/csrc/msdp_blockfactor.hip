@@ -210,25 +210,16 @@ __global__ __launch_bounds__(BF_THREADS) void k_blk_round_rot(const double* __re
 }
 
 // ------------------------------------------------------------------ launchers
-// One instance per lanes-per-block count of the row stride `ld_` (the new one of a rotate / append), as STF_DISPATCH
+// One instance per lanes-per-block count of the row stride `ld_` (the new one of a rotate / append): MSDP_BLOCK_WIDTH_LADDER
 static int bf_grid(int nb, int lpr) {
     const int per_wg = (BF_THREADS / 64) * (64 / lpr);
     return std::max(1, std::min(1024, (nb + per_wg - 1) / per_wg));
 }
-#define BF_LAUNCH(KERNEL, DD, EE, L, N, h, nb_, ...) \
-    hipLaunchKernelGGL((KERNEL<DD, EE, L, N>), dim3(bf_grid(nb_, L)), dim3(BF_THREADS), 0, (h)->stream, __VA_ARGS__)
 #define BF_DISPATCH_L(KERNEL, DD, EE, h, nb_, ld_, ...)                                              \
     do {                                                                                             \
-        const int half = (ld_) / 2;                                                                  \
-        if (half <= 1) BF_LAUNCH(KERNEL, DD, EE, 1, 1, h, nb_, __VA_ARGS__);                         \
-        else if (half <= 2) BF_LAUNCH(KERNEL, DD, EE, 2, 1, h, nb_, __VA_ARGS__);                    \
-        else if (half <= 4) BF_LAUNCH(KERNEL, DD, EE, 4, 1, h, nb_, __VA_ARGS__);                    \
-        else if (half <= 8) BF_LAUNCH(KERNEL, DD, EE, 8, 1, h, nb_, __VA_ARGS__);                    \
-        else if (half <= 16) BF_LAUNCH(KERNEL, DD, EE, 16, 1, h, nb_, __VA_ARGS__);                  \
-        else if (half <= 32) BF_LAUNCH(KERNEL, DD, EE, 32, 1, h, nb_, __VA_ARGS__);                  \
-        else if (half <= 64) BF_LAUNCH(KERNEL, DD, EE, 64, 1, h, nb_, __VA_ARGS__);                  \
-        else if (half <= 128) BF_LAUNCH(KERNEL, DD, EE, 64, 2, h, nb_, __VA_ARGS__);                 \
-        else { msdp_set_error("block factor: row stride %d exceeds the supported maximum of 256", (int)(ld_)); return MSDP_EUNSUPPORTED; } \
+        MSDP_BLOCK_WIDTH_LADDER(ld_, hipLaunchKernelGGL((KERNEL<DD, EE, LPR_, NCH_>), dim3(bf_grid(nb_, LPR_)), dim3(BF_THREADS), 0, \
+                                                        (h)->stream, __VA_ARGS__))                  \
+        { msdp_set_error("block factor: row stride %d exceeds the supported maximum of 256", (int)(ld_)); return MSDP_EUNSUPPORTED; } \
     } while (0)
 #define BF_DISPATCH(KERNEL, h, nb_, ld_, ...)                                                        \
     do {                                                                                             \

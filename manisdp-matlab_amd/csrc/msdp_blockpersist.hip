@@ -1,9 +1,9 @@
 // msdp_blockpersist.hip -- the whole truncated-CG solve of one trust-region iteration in ONE launch for the block kinds
-// (MANI_STIEFEL / COST_BLOCK: the unit-block-diagonal kind of msdp_stiefel.hip and, with d.efree = 1, the pose-graph kind of
-// msdp_pose.hip): tCG.m:95-292 with the working set on chip, the counterpart of msdp_persist.hip for blocks of B = D + EF rows
+// (MANI_STIEFEL / COST_BLOCK, msdp_stiefel.hip: the unit-block-diagonal kind and, with d.efree = 1, the pose-graph kind):
+// tCG.m:95-292 with the working set on chip, the counterpart of msdp_persist.hip for blocks of B = D + EF rows
 // of which the first D are Stiefel rows and the last EF (0 or 1) is free.  Option "block_persist" (default off).
 //
-// The generic path runs a trip as three launches (k_stf_hess / k_pose_hess, k_tcg_upd1, k_stf_upd2 / k_pose_upd2) inside
+// The generic path runs a trip as three launches (k_stf_hess, k_tcg_upd1, k_stf_upd2) inside
 // hipGraph chunks with the host polling a progress word.  Here a lane group of LPR lanes owns one block per row slot (R slots),
 // one double2 per lane and row: the B rows of eta, Heta, r, mdelta and Hmdelta of its blocks stay in registers for the whole
 // launch (blocks of four rows in two slots keep Heta as r - grad: HDER below); the D rotation rows of Y, the B rows of the gradient and the D x D multiplier block Lambda_i of the current point are
@@ -59,7 +59,7 @@ __device__ __forceinline__ void bp_st2_sc1(__amdgpu_buffer_rsrc_t rs, unsigned v
 }
 
 // T = sym(A(1:D, :) Bm(1:D, :)') of two blocks a lane group holds, one double2 per lane and row: the sums of
-// msdp_block_symdot_lead at NCH = 1, in its order
+// msdp_block_symdot at NCH = 1, in its order
 template <int D, int LPR, int RA, int RB>
 __device__ __forceinline__ void bp_symdot(const double2 (&A)[RA], const double2 (&Bm)[RB], double (&T)[D][D]) {
 #pragma unroll

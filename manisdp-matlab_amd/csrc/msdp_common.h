@@ -189,7 +189,7 @@ struct Dev {
     // bval[k * d * d ..] row-major (zero where the caller's pattern is partial); Lam[slot] = the multiplier blocks
     // Lambda_i = sym((C Y)_i Y_i') of the point in that slot (nb * d * d doubles, each block row-major and symmetric); eG[slot]
     // carries their diagonals, row by row
-    // The pose-graph kind (msdp_pose.hip) is the same storage with efree = 1: blocks of blk = d + 1 rows, the last of them a free
+    // The pose-graph kind is the same storage with efree = 1: blocks of blk = d + 1 rows, the last of them a free
     // (Euclidean) row; Lambda stays d x d with d = blk - efree (nb * d * d doubles per slot), eG holds 0 in the free-row entries
     int blk, nb, efree;
     // fused own-column launch in its wide plan (k_tcg_pipe_ws, msdp_pipe.h): the waves [0, rw_split) of a workgroup compute all three row
@@ -507,7 +507,7 @@ int msdp_round_color_plan(msdp_handle h, const char* who);     // the colouring 
 int msdp_hermitian_setup(msdp_handle h, const double* val);   // the complex CSR / ELL values of a COST_HERM handle (val: nnz (re, im) pairs in CSC order)
 int msdp_hermitian_sv(msdp_handle h, const double* z, const double* v, double* w);   // w = C v - z .* v, v and w n complex entries (re, im interleaved)
 int msdp_hermitian_jcopy(msdp_handle h, const double* v, double* w);                 // w = i * v: (re, im) -> (-im, re)
-// msdp_stiefel.hip
+// msdp_stiefel.hip: the steps of a COST_BLOCK handle of either kind (d.efree = 0: unit-block-diagonal, 1: pose-graph)
 int msdp_stiefel_setup(msdp_handle h, int blk, int efree, const int64_t* jc, const int64_t* ir, const double* val);   // block CSR (block order blk, of which efree free rows) of a COST_BLOCK handle from the caller's CSC arrays; Lam[0..1]
 int msdp_stiefel_costgrad(msdp_handle h, int slot);           // Y[slot] -> Gr[slot], Lam[slot], eG[slot], P_F, P_GG (gather source: d.full)
 int msdp_stiefel_hess(msdp_handle h);
@@ -515,15 +515,7 @@ int msdp_stiefel_upd2(msdp_handle h);
 int msdp_stiefel_retract(msdp_handle h);
 int msdp_stiefel_proj(msdp_handle h, const double* Y, const double* U, double* V);
 int msdp_stiefel_retr(msdp_handle h, const double* Y, const double* U, double* Z, double alpha);
-int msdp_stiefel_sv(msdp_handle h, const double* Lam, const double* v, double* w);   // w = C v - blockdiag(Lam) v for vectors of n entries (the escape's S*v)
-// msdp_pose.hip: the same steps for a COST_BLOCK handle with d.efree = 1; the msdp_stiefel_* launchers above hand such a handle on
-int msdp_pose_costgrad(msdp_handle h, int slot);
-int msdp_pose_hess(msdp_handle h);
-int msdp_pose_upd2(msdp_handle h);
-int msdp_pose_retract(msdp_handle h);
-int msdp_pose_proj(msdp_handle h, const double* Y, const double* U, double* V);
-int msdp_pose_retr(msdp_handle h, const double* Y, const double* U, double* Z, double alpha);
-int msdp_pose_sv(msdp_handle h, const double* Lam, const double* v, double* w);      // w = C v - blockdiag(Lam (+) 0) v
+int msdp_stiefel_sv(msdp_handle h, const double* Lam, const double* v, double* w);   // w = C v - blockdiag(Lam (+) 0) v for vectors of n entries (the escape's S*v)
 // msdp_pose_precon.hip: the block-Jacobi preconditioned tCG of a pose-graph handle (option "precon"; d.pcM != nullptr selects it)
 int msdp_pose_precon_set(msdp_handle h, int on);              // the option: M_i^-1 on the host, once; MSDP_EUNSUPPORTED names the kind or the block
 int msdp_pose_precon_vectors(msdp_handle h);                  // (re)allocates z for the handle's row capacity

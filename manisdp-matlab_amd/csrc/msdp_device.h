@@ -477,29 +477,11 @@ __device__ __forceinline__ void spmm_block_via(const Dev& d, int k0, int k1, uns
     }
 }
 
-// T = sym(A B') of two D-row blocks held by a lane group: T[a][b] = (<A_a, B_b> + <A_b, B_a>) / 2, D (D + 1) / 2 group sums;
-// the same bits in every lane of the group
-template <int D, int LPR, int NCH>
-__device__ __forceinline__ void msdp_block_symdot(const double2 (&A)[D][NCH], const double2 (&B)[D][NCH], double (&T)[D][D]) {
-#pragma unroll
-    for (int a = 0; a < D; ++a)
-#pragma unroll
-        for (int b = a; b < D; ++b) {
-            double s = 0.0;
-#pragma unroll
-            for (int ch = 0; ch < NCH; ++ch) {
-                s += A[a][ch].x * B[b][ch].x + A[a][ch].y * B[b][ch].y;
-                if (b != a) s += A[b][ch].x * B[a][ch].x + A[b][ch].y * B[a][ch].y;
-            }
-            s = msdp_group_sum<LPR>(s);
-            T[a][b] = T[b][a] = (b != a) ? 0.5 * s : s;
-        }
-}
-
-// The same for the leading D rows of blocks that hold more (the pose-graph kind, msdp_pose.hip: D rotation rows and one free
-// row, RA / RB = D or D + 1): T = sym(A(1:D, :) B(1:D, :)'); the summation order of msdp_block_symdot
+// T = sym(A B') of the leading D rows of two blocks held by a lane group (RA / RB = D, or D + 1 where a block ends in a free
+// row: the pose-graph kind, d.efree = 1): T[a][b] = (<A_a, B_b> + <A_b, B_a>) / 2, D (D + 1) / 2 group sums; the same bits in
+// every lane of the group
 template <int D, int LPR, int NCH, int RA, int RB>
-__device__ __forceinline__ void msdp_block_symdot_lead(const double2 (&A)[RA][NCH], const double2 (&B)[RB][NCH], double (&T)[D][D]) {
+__device__ __forceinline__ void msdp_block_symdot(const double2 (&A)[RA][NCH], const double2 (&B)[RB][NCH], double (&T)[D][D]) {
     static_assert(RA >= D && RB >= D, "blocks of at least D rows");
 #pragma unroll
     for (int a = 0; a < D; ++a)
@@ -515,6 +497,30 @@ __device__ __forceinline__ void msdp_block_symdot_lead(const double2 (&A)[RA][NC
             T[a][b] = T[b][a] = (b != a) ? 0.5 * s : s;
         }
 }
+
+// Workgroup size of the row kernels of the block kinds (msdp_stiefel.hip, msdp_pose_precon.hip; B = the rows of a block): 16
+// waves hide the gather latency where a block fits 128 registers per lane (NCH = 1, widths up to 128); two chunks per lane
+// (widths up to 256) take 8 waves and twice the registers.  A kernel that keeps THREE vectors of a block resident beside the
+// B x B values of an entry (the Hess-vec: w, u, y; the preconditioned first update: r, z, y) takes 126-137 registers at B = 4
+// and spilled at the 128 of a 16-wave workgroup: its one-chunk instances run 8 waves there (DESIGN.md section 4 has the table)
+template <int B, int NCH> struct BlockRows { static constexpr int threads = NCH == 1 ? 1024 : 512; };
+template <int B, int NCH> struct BlockRows3 { static constexpr int threads = (NCH == 1 && B < 4) ? 1024 : 512; };
+
+// The width ladder of the block kinds: one kernel instance <LPR_, NCH_> per lanes-per-block count of the row stride ld_, widths
+// up to 2 * 64 * 2 = 256.  The arguments after ld_ are the caller's launch statement, which names LPR_ and NCH_.  The macro
+// ends in `else`: the statement that follows it is what the caller does with a wider stride,
+//     MSDP_BLOCK_WIDTH_LADDER(ld, hipLaunchKernelGGL((k<LPR_, NCH_>), ...)) { msdp_set_error(...); return MSDP_EUNSUPPORTED; }
+#define MSDP_BLOCK_WIDTH_RUNG(L, N, ...) { constexpr int LPR_ = L, NCH_ = N; __VA_ARGS__; }
+#define MSDP_BLOCK_WIDTH_LADDER(ld_, ...)                                    \
+    if ((ld_) / 2 <= 1) MSDP_BLOCK_WIDTH_RUNG(1, 1, __VA_ARGS__)             \
+    else if ((ld_) / 2 <= 2) MSDP_BLOCK_WIDTH_RUNG(2, 1, __VA_ARGS__)        \
+    else if ((ld_) / 2 <= 4) MSDP_BLOCK_WIDTH_RUNG(4, 1, __VA_ARGS__)        \
+    else if ((ld_) / 2 <= 8) MSDP_BLOCK_WIDTH_RUNG(8, 1, __VA_ARGS__)        \
+    else if ((ld_) / 2 <= 16) MSDP_BLOCK_WIDTH_RUNG(16, 1, __VA_ARGS__)      \
+    else if ((ld_) / 2 <= 32) MSDP_BLOCK_WIDTH_RUNG(32, 1, __VA_ARGS__)      \
+    else if ((ld_) / 2 <= 64) MSDP_BLOCK_WIDTH_RUNG(64, 1, __VA_ARGS__)      \
+    else if ((ld_) / 2 <= 128) MSDP_BLOCK_WIDTH_RUNG(64, 2, __VA_ARGS__)     \
+    else
 
 // R = G^(-1/2) of a symmetric positive definite D x D matrix in registers (the polar retraction: G = A A' of a block A = Y + eta,
 // G = I + eta eta' >= I for tangent eta).  Symmetric eigen-decomposition by Jacobi rotations -- for D = 2 a single rotation is

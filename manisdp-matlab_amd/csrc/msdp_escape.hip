@@ -407,7 +407,7 @@ static int sapply(EscCtx& c, const double* v, double* w) {
     // Hermitian C: v and w are complex vectors of d.n entries in their real view (c.n = 2 d.n), w = C v - z .* v (msdp_hermitian.hip)
     if (!c.M && d.costkind == COST_HERM) return msdp_hermitian_sv(h, c.z, v, w);
     // block CSR (COST_BLOCK): w = C v - blockdiag(Lambda) v with the multiplier blocks of the resident point (msdp_stiefel.hip), for a
-    // pose-graph handle w = C v - blockdiag(Lambda (+) 0) v with the d x d blocks zero-padded on the free rows (msdp_pose.hip); c.z is not read
+    // pose-graph handle w = C v - blockdiag(Lambda (+) 0) v with the d x d blocks zero-padded on the free rows; c.z is not read
     if (!c.M && d.costkind == COST_BLOCK) return msdp_stiefel_sv(h, d.Lam[h->h_ctl->cur], v, w);
     if (c.M)
         hipLaunchKernelGGL(k_sv_dense, dim3((c.n + 3) / 4), dim3(256), 0, h->stream, c.n, c.n, msdp_dense_nS(c.n), c.M, (const double*)nullptr, v, w, 0);

@@ -1,4 +1,4 @@
-// msdp_pose_precon.hip -- block-Jacobi preconditioned truncated CG for the pose-graph kind (msdp_pose.hip; option "precon" of
+// msdp_pose_precon.hip -- block-Jacobi preconditioned truncated CG for the pose-graph kind (msdp_stiefel.hip at EF = 1; option "precon" of
 // msdp_set_option, default off).  The device follows the preconditioned branch of Manopt's tCG (tCG.m:117-125, :260-287) where
 // the generic trips follow the identity branch:
 //   M_i = sym(C_[ii])     the diagonal block of order B = d + 1 of pose i -- fixed for the life of the handle, unscaled,
@@ -8,7 +8,7 @@
 // The trust region is measured in the M-norm (e_Pe, e_Pd, d_Pd of the frame are M-inner products, as in Manopt); Delta_bar and
 // Delta0 keep their values.  The stop test (:249) stays on norm_r = sqrt(<r, r>) and norm_r0 = sqrt(gg).
 //
-// A trip stays three launches: k_pose_hess as it is, then
+// A trip stays three launches: k_stf_hess as it is, then
 //   k_pose_pc_upd1   tCG.m:166-241, the decisions of k_tcg_upd1 block by block; with the rows of the new r of a block in registers
 //                    also z = tangent(M_i^-1 r) -> d.pcz and a fourth partial sum <z, r>
 //   k_pose_pc_upd2   tCG.m:227-287 with beta = <z, r> / <z_old, r_old> and mdelta = tangent(z + beta mdelta)
@@ -17,21 +17,17 @@
 // them where later ones read z_r and d_Pd from the frame -- no host synchronisation.  upd1 writes its <z, r_new> partials to
 // another array, P_ZRN, since the workgroups of that first launch still read P_ZR0.  Neither array is used by the kind otherwise.
 //
-// Lane layout and instances are those of msdp_pose.hip: LPR lanes own a block, NCH double2 per row and lane, widths up to 256
-// (workgroup sizes: PcBlock / PcUpd1Block below).  Only r_new, z and the D rotation rows of Y are resident per block; eta, Heta, mdelta, H mdelta and the
+// Lane layout and instances are those of msdp_stiefel.hip: LPR lanes own a block, NCH double2 per row and lane, widths up to 256
+// (the ladder and the workgroup sizes BlockRows / BlockRows3 of msdp_device.h; the first update holds four rows of the new r and
+// of z, three of y and the 4 x 4 values of M_i^-1 beside the six streamed operands at d = 3: the three-vector size).  Only r_new,
+// z and the D rotation rows of Y are resident per block; eta, Heta, mdelta, H mdelta and the
 // gradient stream through.  No instance uses scratch (DESIGN.md lists the registers per instance).
-// The kernels of msdp_pose.hip and msdp_kernels.hip are not touched (msdp_tcg_upd2_scalars serves both, by a compile-time switch): what selects these launchers is
+// The kernels of msdp_stiefel.hip and msdp_kernels.hip are not touched (msdp_tcg_upd2_scalars serves both, by a compile-time switch): what selects these launchers is
 // d.pcM != nullptr, a field of Dev, so the chunk graph (whose signature is the Dev) is captured again when the option flips.
 #include "msdp_device.h"
 #include <math.h>
 #include <cmath>
 #include <vector>
-
-// workgroup sizes: those of msdp_pose.hip (16 waves at one chunk per lane, 8 at two) for all but the d = 3 first update.  That one
-// holds four rows of the new r and of z, three of y and the 4 x 4 values of M_i^-1 beside the six streamed operands: its one-chunk
-// instances spilled at the 128 registers of a 16-wave workgroup, so it runs 8 waves (DESIGN.md section 4 has the table).
-template <int D, int NCH> struct PcBlock { static constexpr int threads = NCH == 1 ? 1024 : 512; };
-template <int D, int NCH> struct PcUpd1Block { static constexpr int threads = (NCH == 1 && D == 2) ? 1024 : 512; };
 
 // z = tangent_y(Minv r) for one block held by a lane group: z[a] = sum_b Minv[a][b] r[b] (b ascending), then the rotation rows
 // minus sym(z y') y; the free row stays.  mi: the B * B values of the block, row-major (the same addresses in every lane)
@@ -53,7 +49,7 @@ __device__ __forceinline__ void pc_apply_block(const double* __restrict__ mi, co
         }
     }
     double T[D][D];
-    msdp_block_symdot_lead<D, LPR, NCH>(z, y, T);
+    msdp_block_symdot<D, LPR, NCH>(z, y, T);
 #pragma unroll
     for (int a = 0; a < D; ++a)
 #pragma unroll
@@ -76,9 +72,9 @@ __device__ __forceinline__ void pc_load_rot(const Dev& d, const double* __restri
 
 // Z = tangent_Y(blockdiag(M_i^-1) R) for vectors in the handle's layout (msdp_precon_apply)
 template <int D, int LPR, int NCH>
-__global__ __launch_bounds__((PcBlock<D, NCH>::threads)) void k_pose_pc_apply(Dev d, const double* __restrict__ Yl,
+__global__ __launch_bounds__((BlockRows<D + 1, NCH>::threads)) void k_pose_pc_apply(Dev d, const double* __restrict__ Yl,
                                                                                const double* __restrict__ R, double* __restrict__ Z) {
-    constexpr int B = D + 1, WAVES = PcBlock<D, NCH>::threads / 64, BPW = 64 / LPR;
+    constexpr int B = D + 1, WAVES = BlockRows<D + 1, NCH>::threads / 64, BPW = 64 / LPR;
     int lo, hi;
     msdp_chunk_rows(d.nb, d.G, lo, hi);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -110,7 +106,7 @@ __global__ __launch_bounds__((PcBlock<D, NCH>::threads)) void k_pose_pc_apply(De
 // tCG.m:102-157: eta = 0, Heta = 0, r = grad, z = precon(r), mdelta = z; the partials of <z, r> -> P_ZR0.  The frame carries
 // gg in z_r and d_Pd until the first upd1 replaces them by that sum (`fresh`); norm_r0 = sqrt(gg)
 template <int D, int LPR, int NCH>
-__global__ __launch_bounds__((PcBlock<D, NCH>::threads)) void k_pose_pc_init(Dev d) {
+__global__ __launch_bounds__((BlockRows<D + 1, NCH>::threads)) void k_pose_pc_init(Dev d) {
     __shared__ double sh[3 * MSDP_WAVES];
     const Ctl* c = d.ctl;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -121,7 +117,7 @@ __global__ __launch_bounds__((PcBlock<D, NCH>::threads)) void k_pose_pc_init(Dev
         msdp_publish(d, c->k, 0, act);
     }
     if (c->done) return;
-    constexpr int B = D + 1, WAVES = PcBlock<D, NCH>::threads / 64, BPW = 64 / LPR;
+    constexpr int B = D + 1, WAVES = BlockRows<D + 1, NCH>::threads / 64, BPW = 64 / LPR;
     int lo, hi;
     msdp_chunk_rows(d.nb, d.G, lo, hi);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -166,7 +162,7 @@ __global__ __launch_bounds__((PcBlock<D, NCH>::threads)) void k_pose_pc_init(Dev
 // new_Heta, the new r and the sums s1, s2, r_r), and with the rows of the new r of a block in registers z = tangent(M_i^-1 r)
 // -> d.pcz and the fourth sum <z, r>
 template <int D, int LPR, int NCH>
-__global__ __launch_bounds__((PcUpd1Block<D, NCH>::threads)) void k_pose_pc_upd1(Dev d) {
+__global__ __launch_bounds__((BlockRows3<D + 1, NCH>::threads)) void k_pose_pc_upd1(Dev d) {
     __shared__ double sh[3 * MSDP_WAVES];
     __shared__ double sh4[3 * MSDP_WAVES];
     __shared__ double shb[2];
@@ -184,7 +180,7 @@ __global__ __launch_bounds__((PcUpd1Block<D, NCH>::threads)) void k_pose_pc_upd1
     const Ctl* c = d.ctl;
     const bool bench = c->bench_mode != 0;
     const double Delta = c->Delta;
-    constexpr int B = D + 1, WAVES = PcUpd1Block<D, NCH>::threads / 64, BPW = 64 / LPR;
+    constexpr int B = D + 1, WAVES = BlockRows3<D + 1, NCH>::threads / 64, BPW = 64 / LPR;
     int lo, hi;
     msdp_chunk_rows(d.nb, d.G, lo, hi);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -279,11 +275,11 @@ __global__ __launch_bounds__((PcUpd1Block<D, NCH>::threads)) void k_pose_pc_upd1
 // tCG.m:227-287: the scalar decisions (msdp_tcg_upd2_scalars in its preconditioned form: beta = z_r_new / z_r with z_r_new = <z, r>
 // of the upd1 launch, P_ZRN), then mdelta = tangent(z + beta mdelta) block by block (:273, :283)
 template <int D, int LPR, int NCH>
-__global__ __launch_bounds__((PcBlock<D, NCH>::threads)) void k_pose_pc_upd2(Dev d) {
+__global__ __launch_bounds__((BlockRows<D + 1, NCH>::threads)) void k_pose_pc_upd2(Dev d) {
     __shared__ double shb[4];
     double beta;
     if (!msdp_tcg_upd2_scalars<true>(d, shb, beta)) return;
-    constexpr int B = D + 1, WAVES = PcBlock<D, NCH>::threads / 64, BPW = 64 / LPR;
+    constexpr int B = D + 1, WAVES = BlockRows<D + 1, NCH>::threads / 64, BPW = 64 / LPR;
     int lo, hi;
     msdp_chunk_rows(d.nb, d.G, lo, hi);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -307,7 +303,7 @@ __global__ __launch_bounds__((PcBlock<D, NCH>::threads)) void k_pose_pc_upd2(Dev
                 }
             pc_load_rot<D, LPR, NCH>(d, Yl, blk, sub, y);
             double T[D][D];
-            msdp_block_symdot_lead<D, LPR, NCH>(v, y, T);
+            msdp_block_symdot<D, LPR, NCH>(v, y, T);
 #pragma unroll
             for (int a = 0; a < B; ++a)
 #pragma unroll
@@ -339,50 +335,38 @@ __global__ void k_pose_pc_diag(int nb, const int* __restrict__ brp, const int* _
 }
 
 // ------------------------------------------------------------------ launchers
-// the instances of POSE_DISPATCH (msdp_pose.hip): one per lanes-per-block count, widths up to 2 * 64 * 2 = 256
-#define PC_LAUNCH(BLOCK, KERNEL, DD, L, N, h, ...) \
-    hipLaunchKernelGGL((KERNEL<DD, L, N>), dim3((h)->d.G), dim3(BLOCK<DD, N>::threads), 0, (h)->stream, __VA_ARGS__)
-#define PC_DISPATCH_D(BLOCK, KERNEL, DD, h, ...)                                                                 \
-    do {                                                                                                    \
-        const int half = (h)->d.ld / 2;                                                                     \
-        if (half <= 1) PC_LAUNCH(BLOCK, KERNEL, DD, 1, 1, h, __VA_ARGS__);                                         \
-        else if (half <= 2) PC_LAUNCH(BLOCK, KERNEL, DD, 2, 1, h, __VA_ARGS__);                                    \
-        else if (half <= 4) PC_LAUNCH(BLOCK, KERNEL, DD, 4, 1, h, __VA_ARGS__);                                    \
-        else if (half <= 8) PC_LAUNCH(BLOCK, KERNEL, DD, 8, 1, h, __VA_ARGS__);                                    \
-        else if (half <= 16) PC_LAUNCH(BLOCK, KERNEL, DD, 16, 1, h, __VA_ARGS__);                                  \
-        else if (half <= 32) PC_LAUNCH(BLOCK, KERNEL, DD, 32, 1, h, __VA_ARGS__);                                  \
-        else if (half <= 64) PC_LAUNCH(BLOCK, KERNEL, DD, 64, 1, h, __VA_ARGS__);                                  \
-        else if (half <= 128) PC_LAUNCH(BLOCK, KERNEL, DD, 64, 2, h, __VA_ARGS__);                                 \
-        else {                                                                                              \
-            msdp_set_error("pose-graph handle: factor width p = %d exceeds the supported maximum of 256", (h)->d.p); \
-            return MSDP_EUNSUPPORTED;                                                                       \
-        }                                                                                                   \
-    } while (0)
-#define PC_DISPATCH(BLOCK, KERNEL, h, ...)                                                                       \
+// one instance per lanes-per-block count (MSDP_BLOCK_WIDTH_LADDER, widths up to 256) and d
+#define PC_LAUNCH_D(BLOCK, KERNEL, DD, h, ...)                                                              \
+    MSDP_BLOCK_WIDTH_LADDER((h)->d.ld, hipLaunchKernelGGL((KERNEL<DD, LPR_, NCH_>), dim3((h)->d.G), dim3(BLOCK<DD + 1, NCH_>::threads), \
+                                                          0, (h)->stream, __VA_ARGS__)) {                  \
+        msdp_set_error("pose-graph handle: factor width p = %d exceeds the supported maximum of 256", (h)->d.p); \
+        return MSDP_EUNSUPPORTED;                                                                           \
+    }
+#define PC_DISPATCH(BLOCK, KERNEL, h, ...)                                                                  \
     do {                                                                                                    \
         if ((h)->d.manifold != MANI_STIEFEL || !(h)->d.efree || !(h)->d.brp || !(h)->d.pcM || !(h)->d.pcz) { \
             msdp_set_error("preconditioned tCG: not a pose-graph handle with the option \"precon\" set");   \
             return MSDP_ESTATE;                                                                             \
         }                                                                                                   \
-        if ((h)->d.blk == 3) PC_DISPATCH_D(BLOCK, KERNEL, 2, h, __VA_ARGS__);                                      \
-        else PC_DISPATCH_D(BLOCK, KERNEL, 3, h, __VA_ARGS__);                                                      \
+        if ((h)->d.blk == 3) { PC_LAUNCH_D(BLOCK, KERNEL, 2, h, __VA_ARGS__) }                              \
+        else { PC_LAUNCH_D(BLOCK, KERNEL, 3, h, __VA_ARGS__) }                                              \
         HIPCHK(hipGetLastError());                                                                          \
     } while (0)
 
 int msdp_pose_precon_init(msdp_handle h) {
-    PC_DISPATCH(PcBlock, k_pose_pc_init, h, h->d);
+    PC_DISPATCH(BlockRows, k_pose_pc_init, h, h->d);
     return 0;
 }
 int msdp_pose_precon_upd1(msdp_handle h) {
-    PC_DISPATCH(PcUpd1Block, k_pose_pc_upd1, h, h->d);
+    PC_DISPATCH(BlockRows3, k_pose_pc_upd1, h, h->d);
     return 0;
 }
 int msdp_pose_precon_upd2(msdp_handle h) {
-    PC_DISPATCH(PcBlock, k_pose_pc_upd2, h, h->d);
+    PC_DISPATCH(BlockRows, k_pose_pc_upd2, h, h->d);
     return 0;
 }
 int msdp_pose_precon_apply(msdp_handle h, const double* Y, const double* R, double* Z) {
-    PC_DISPATCH(PcBlock, k_pose_pc_apply, h, h->d, Y, R, Z);
+    PC_DISPATCH(BlockRows, k_pose_pc_apply, h, h->d, Y, R, Z);
     return 0;
 }
 

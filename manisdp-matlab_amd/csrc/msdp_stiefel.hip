@@ -17,25 +17,31 @@
 // each in registers: per block entry the d rows of the neighbour block are gathered once and used d times, the index traffic is
 // 1 / d^2 of plain CSR.  Workgroup chunks are over blocks, so a block never straddles two workgroups.  Lambda lives per point
 // slot (d.Lam[slot], the slot scheme of eG), its diagonal in eG[slot] so that msdp_get_z serves the kind unchanged.
-// The kind runs the generic per-iteration path of msdp_rtr.hip (no persistent or fused trip, no row sharding).
-// SIBLINGS: msdp_pose.hip holds a copy of every kernel below for blocks of d + 1 rows whose last row is free (the pose-graph
-// kind, d.efree = 1; the launchers at the end of this file hand such a handle on).  The copies differ in B = D + 1, the a < D
-// guards and msdp_block_symdot_lead only: a fix to a kernel here belongs there too.
+// The kind runs the generic per-iteration path of msdp_rtr.hip (no fused trip, no row sharding; msdp_blockpersist.hip holds its
+// persistent tCG).
+//
+// The same kernels serve the pose-graph problem  (X_[ii])_{1..d,1..d} = I_d  of order N = n (d + 1)  (SE(d) synchronisation, the
+// non-marginalised form of SE-Sync / Cartan-Sync; d.efree = 1, msdp_create_posegraph_csc; manopt's productmanifold of
+// stiefelstackedfactory(n, d, p) and euclideanfactory(n, p)): every kernel is templated on EF, the free rows per block (0 or
+// 1), and a block is B = D + EF consecutive rows -- D rotation rows Y_i and, at EF = 1, one free row tau_i.  Whatever streams
+// runs over the rows 0 .. B-1; y, Lambda, the sym(.) and the polar factor over the rows 0 .. D-1, and the Stiefel part of a store
+// stands behind `a < D` (compile-time true at EF = 0).  With (C Y)_i = [G_i; g_i] the free row adds:
+//   multiplier  Lambda_i = sym(G_i Y_i') stays d x d      S = C - blockdiag(Lambda_i (+) 0); eG carries 0 in the free-row entry
+//   cost        2 f = sum_i tr Lambda_i + sum_i <g_i, tau_i>: the dual value sum tr Lambda is NOT <C, X> away from a critical point
+//   gradient    [G_i - Lambda_i Y_i ; g_i]                Hess-vec: the free row of W as it is
+//   tangent     identity on the free row                  retraction: tau_i + eta_tau (euclideanfactory.m:44)
+// The storage is the block CSR above at block order B.  No instance uses scratch (DESIGN.md section 4 lists the registers).
 #include "msdp_device.h"
 #include <algorithm>
 #include <math.h>
 #include <vector>
 
-// workgroup size of the row kernels: 16 waves hide the gather latency where a block fits 128 registers per lane (NCH = 1,
-// widths up to 128); two chunks per lane (widths up to 256) take 8 waves and twice the registers
-template <int NCH> struct StfBlock { static constexpr int threads = NCH == 1 ? 1024 : 512; };
-
 // cost + Riemannian gradient + Lambda at Y[slot] (gather source: d.full holds all rows of Y[slot])
-template <int D, int LPR, int NCH>
-__global__ __launch_bounds__(StfBlock<NCH>::threads) void k_stf_costgrad(Dev d, int slot) {
+template <int D, int EF, int LPR, int NCH>
+__global__ __launch_bounds__((BlockRows<D + EF, NCH>::threads)) void k_stf_costgrad(Dev d, int slot) {
     __shared__ double sh[3 * MSDP_WAVES];
     if (d.ctl->done) return;
-    constexpr int WAVES = StfBlock<NCH>::threads / 64, BPW = 64 / LPR;
+    constexpr int B = D + EF, WAVES = BlockRows<B, NCH>::threads / 64, BPW = 64 / LPR;
     int lo, hi;
     msdp_chunk_rows(d.nb, d.G, lo, hi);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -49,28 +55,32 @@ __global__ __launch_bounds__(StfBlock<NCH>::threads) void k_stf_costgrad(Dev d, 
     for (int b0 = lo + wave * BPW; b0 < hi; b0 += WAVES * BPW) {
         const int blk = b0 + rsub;
         if (blk < hi) {
-            double2 acc[D][NCH], y[D][NCH];
+            double2 acc[B][NCH], y[B][NCH];
 #pragma unroll
-            for (int a = 0; a < D; ++a)
+            for (int a = 0; a < B; ++a)
 #pragma unroll
                 for (int ch = 0; ch < NCH; ++ch) {
                     acc[a][ch] = make_double2(0.0, 0.0);
                     const int col = 2 * sub + ch * 2 * LPR;
-                    y[a][ch] = (col < d.ld) ? ld2(Yl + ((int64_t)blk * D + a) * d.ld + col) : make_double2(0.0, 0.0);
+                    y[a][ch] = (col < d.ld) ? ld2(Yl + ((int64_t)blk * B + a) * d.ld + col) : make_double2(0.0, 0.0);
                 }
-            spmm_block<D, LPR, NCH>(d, blk, sub, Xf, acc);
+            spmm_block<B, LPR, NCH, (B == 4 ? 1 : 2)>(d, blk, sub, Xf, acc);
             double L[D][D];
-            msdp_block_symdot<D, LPR, NCH>(acc, y, L);      // Lambda = sym((C Y)_i Y_i')
+            msdp_block_symdot<D, LPR, NCH>(acc, y, L);      // Lambda = sym(G_i Y_i'), rotation rows only
 #pragma unroll
-            for (int a = 0; a < D; ++a)
+            for (int a = 0; a < B; ++a)
 #pragma unroll
                 for (int ch = 0; ch < NCH; ++ch) {
                     const int col = 2 * sub + ch * 2 * LPR;
                     if (col < d.ld) {
                         double2 g = acc[a][ch];
+                        if (a < D) {
 #pragma unroll
-                        for (int b = 0; b < D; ++b) { g.x -= L[a][b] * y[b][ch].x; g.y -= L[a][b] * y[b][ch].y; }   // G = C Y - Lambda Y
-                        st2(Gr + ((int64_t)blk * D + a) * d.ld + col, g);
+                            for (int b = 0; b < D; ++b) { g.x -= L[a][b] * y[b][ch].x; g.y -= L[a][b] * y[b][ch].y; }   // G - Lambda Y
+                        } else {
+                            pf += 0.5 * (g.x * y[a][ch].x + g.y * y[a][ch].y);      // <g_i, tau_i> / 2: the free row's share of f
+                        }
+                        st2(Gr + ((int64_t)blk * B + a) * d.ld + col, g);
                         pgg += g.x * g.x + g.y * g.y;
                     }
                 }
@@ -79,21 +89,23 @@ __global__ __launch_bounds__(StfBlock<NCH>::threads) void k_stf_costgrad(Dev d, 
                 for (int a = 0; a < D; ++a) {
 #pragma unroll
                     for (int b = 0; b < D; ++b) Lam[(int64_t)blk * (D * D) + a * D + b] = L[a][b];
-                    eG[blk * D + a] = L[a][a];
+                    eG[blk * B + a] = L[a][a];
                     pf += 0.5 * L[a][a];
                 }
+                if constexpr (EF) eG[blk * B + D] = 0.0;
             }
         }
     }
     msdp_put_partials3(d.P, P_F, pf, P_GG, pgg, -1, 0.0, sh);
 }
 
-// Hess-vec: W = C md - blockdiag(Lambda) md, Hmd_i = W_i - sym(W_i Y_i') Y_i, partial <md, Hmd>
-template <int D, int LPR, int NCH>
-__global__ __launch_bounds__(StfBlock<NCH>::threads) void k_stf_hess(Dev d) {
+// Hess-vec: W = C md - blockdiag(Lambda (+) 0) md; rotation rows Hmd_i = W_i - sym(W_i Y_i') Y_i, a free row of W as it is;
+// partial <md, Hmd>
+template <int D, int EF, int LPR, int NCH>
+__global__ __launch_bounds__((BlockRows3<D + EF, NCH>::threads)) void k_stf_hess(Dev d) {
     __shared__ double sh[3 * MSDP_WAVES];
     if (!d.F[0].active) return;
-    constexpr int WAVES = StfBlock<NCH>::threads / 64, BPW = 64 / LPR;
+    constexpr int B = D + EF, WAVES = BlockRows3<B, NCH>::threads / 64, BPW = 64 / LPR;
     int lo, hi;
     msdp_chunk_rows(d.nb, d.G, lo, hi);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -110,24 +122,54 @@ __global__ __launch_bounds__(StfBlock<NCH>::threads) void k_stf_hess(Dev d) {
     for (int b0 = lo + wave * BPW; b0 < hi; b0 += WAVES * BPW) {
         const int blk = b0 + rsub;
         if (blk < hi) {
-            double2 w[D][NCH], y[D][NCH], u[D][NCH];
+            // a free row of Y is not needed: y holds the D rotation rows, w and u all B rows.  The ORDER of these loads is measured,
+            // per kind, and the compiler's schedule follows it: without a free row y, u and the row of Lambda come row by row (u
+            // for all rows first, then y, cost 4 % at d = 3, p = 8: 10.36 against 9.96 us); with one, u first and then y (row by
+            // row takes 2-6 registers more).  profiles/block_rowkernels_kernel_regs.md has both.
+            double2 w[B][NCH], y[D][NCH], u[B][NCH];
             double L[D][D];
+            if constexpr (EF == 0) {
 #pragma unroll
-            for (int a = 0; a < D; ++a) {
+                for (int a = 0; a < D; ++a) {
 #pragma unroll
-                for (int ch = 0; ch < NCH; ++ch) {
-                    w[a][ch] = make_double2(0.0, 0.0);
-                    const int col = 2 * sub + ch * 2 * LPR;
-                    const bool ok = col < d.ld;
-                    const int64_t o = ((int64_t)blk * D + a) * d.ld + (ok ? col : 0);
-                    y[a][ch] = ld2(Yl + o);
-                    u[a][ch] = ld2(Ul + o);
-                    if (!ok) { y[a][ch] = make_double2(0.0, 0.0); u[a][ch] = make_double2(0.0, 0.0); }
+                    for (int ch = 0; ch < NCH; ++ch) {
+                        w[a][ch] = make_double2(0.0, 0.0);
+                        const int col = 2 * sub + ch * 2 * LPR;
+                        const bool ok = col < d.ld;
+                        const int64_t o = ((int64_t)blk * D + a) * d.ld + (ok ? col : 0);
+                        y[a][ch] = ld2(Yl + o);
+                        u[a][ch] = ld2(Ul + o);
+                        if (!ok) { y[a][ch] = make_double2(0.0, 0.0); u[a][ch] = make_double2(0.0, 0.0); }
+                    }
+#pragma unroll
+                    for (int b = 0; b < D; ++b) L[a][b] = Lam[(int64_t)blk * (D * D) + a * D + b];
                 }
+            } else {
 #pragma unroll
-                for (int b = 0; b < D; ++b) L[a][b] = Lam[(int64_t)blk * (D * D) + a * D + b];
+                for (int a = 0; a < B; ++a)
+#pragma unroll
+                    for (int ch = 0; ch < NCH; ++ch) {
+                        w[a][ch] = make_double2(0.0, 0.0);
+                        const int col = 2 * sub + ch * 2 * LPR;
+                        const bool ok = col < d.ld;
+                        u[a][ch] = ld2(Ul + ((int64_t)blk * B + a) * d.ld + (ok ? col : 0));
+                        if (!ok) u[a][ch] = make_double2(0.0, 0.0);
+                    }
+#pragma unroll
+                for (int a = 0; a < D; ++a)
+#pragma unroll
+                    for (int ch = 0; ch < NCH; ++ch) {
+                        const int col = 2 * sub + ch * 2 * LPR;
+                        const bool ok = col < d.ld;
+                        y[a][ch] = ld2(Yl + ((int64_t)blk * B + a) * d.ld + (ok ? col : 0));
+                        if (!ok) y[a][ch] = make_double2(0.0, 0.0);
+                    }
+#pragma unroll
+                for (int a = 0; a < D; ++a)
+#pragma unroll
+                    for (int b = 0; b < D; ++b) L[a][b] = Lam[(int64_t)blk * (D * D) + a * D + b];
             }
-            spmm_block<D, LPR, NCH, (D == 3 ? 1 : 2)>(d, blk, sub, Uf, w);
+            spmm_block<B, LPR, NCH, (B == 2 ? 2 : 1)>(d, blk, sub, Uf, w);
 #pragma unroll
             for (int a = 0; a < D; ++a)
 #pragma unroll
@@ -137,15 +179,17 @@ __global__ __launch_bounds__(StfBlock<NCH>::threads) void k_stf_hess(Dev d) {
             double T[D][D];
             msdp_block_symdot<D, LPR, NCH>(w, y, T);
 #pragma unroll
-            for (int a = 0; a < D; ++a)
+            for (int a = 0; a < B; ++a)
 #pragma unroll
                 for (int ch = 0; ch < NCH; ++ch) {
                     const int col = 2 * sub + ch * 2 * LPR;
                     if (col < d.ld) {
                         double2 h = w[a][ch];
+                        if (a < D) {
 #pragma unroll
-                        for (int b = 0; b < D; ++b) { h.x -= T[a][b] * y[b][ch].x; h.y -= T[a][b] * y[b][ch].y; }
-                        st2(H + ((int64_t)blk * D + a) * d.ld + col, h);
+                            for (int b = 0; b < D; ++b) { h.x -= T[a][b] * y[b][ch].x; h.y -= T[a][b] * y[b][ch].y; }
+                        }
+                        st2(H + ((int64_t)blk * B + a) * d.ld + col, h);
                         pd += u[a][ch].x * h.x + u[a][ch].y * h.y;
                     }
                 }
@@ -154,13 +198,14 @@ __global__ __launch_bounds__(StfBlock<NCH>::threads) void k_stf_hess(Dev d) {
     msdp_put_partial(d.P, P_DHD, pd, sh);
 }
 
-// tCG.m:227-287: the scalar decisions (msdp_tcg_upd2_scalars), then mdelta = tangent(r + beta mdelta) block by block (:273, :283)
-template <int D, int LPR, int NCH>
-__global__ __launch_bounds__(StfBlock<NCH>::threads) void k_stf_upd2(Dev d) {
+// tCG.m:227-287: the scalar decisions (msdp_tcg_upd2_scalars), then mdelta = tangent(r + beta mdelta) block by block (:273, :283);
+// on a free row the tangent projection is r + beta mdelta itself
+template <int D, int EF, int LPR, int NCH>
+__global__ __launch_bounds__((BlockRows<D + EF, NCH>::threads)) void k_stf_upd2(Dev d) {
     __shared__ double shb[4];
     double beta;
     if (!msdp_tcg_upd2_scalars(d, shb, beta)) return;
-    constexpr int WAVES = StfBlock<NCH>::threads / 64, BPW = 64 / LPR;
+    constexpr int B = D + EF, WAVES = BlockRows<B, NCH>::threads / 64, BPW = 64 / LPR;
     int lo, hi;
     msdp_chunk_rows(d.nb, d.G, lo, hi);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -169,46 +214,72 @@ __global__ __launch_bounds__(StfBlock<NCH>::threads) void k_stf_upd2(Dev d) {
     for (int b0 = lo + wave * BPW; b0 < hi; b0 += WAVES * BPW) {
         const int blk = b0 + rsub;
         if (blk < hi) {
-            double2 v[D][NCH], y[D][NCH];
+            // v for all B rows, y for the D rotation rows; as in the Hess-vec the order of the loads is the measured one per kind:
+            // y with the row of r and mdelta where there is no free row (after them: +0.6 us a trip at d = 2, p = 32), else after
+            double2 v[B][NCH], y[D][NCH];
+            if constexpr (EF == 0) {
 #pragma unroll
-            for (int a = 0; a < D; ++a)
+                for (int a = 0; a < D; ++a)
 #pragma unroll
-                for (int ch = 0; ch < NCH; ++ch) {
-                    const int col = 2 * sub + ch * 2 * LPR;
-                    v[a][ch] = y[a][ch] = make_double2(0.0, 0.0);
-                    if (col < d.ld) {
-                        const int64_t o = ((int64_t)blk * D + a) * d.ld + col;
-                        const double2 rr = ld2(d.r + o), m = ld2(d.md + o);
-                        y[a][ch] = ld2(Yl + o);
-                        v[a][ch] = make_double2(rr.x + beta * m.x, rr.y + beta * m.y);
+                    for (int ch = 0; ch < NCH; ++ch) {
+                        const int col = 2 * sub + ch * 2 * LPR;
+                        v[a][ch] = y[a][ch] = make_double2(0.0, 0.0);
+                        if (col < d.ld) {
+                            const int64_t o = ((int64_t)blk * D + a) * d.ld + col;
+                            const double2 rr = ld2(d.r + o), m = ld2(d.md + o);
+                            y[a][ch] = ld2(Yl + o);
+                            v[a][ch] = make_double2(rr.x + beta * m.x, rr.y + beta * m.y);
+                        }
                     }
-                }
+            } else {
+#pragma unroll
+                for (int a = 0; a < B; ++a)
+#pragma unroll
+                    for (int ch = 0; ch < NCH; ++ch) {
+                        const int col = 2 * sub + ch * 2 * LPR;
+                        v[a][ch] = make_double2(0.0, 0.0);
+                        if (col < d.ld) {
+                            const int64_t o = ((int64_t)blk * B + a) * d.ld + col;
+                            const double2 rr = ld2(d.r + o), m = ld2(d.md + o);
+                            v[a][ch] = make_double2(rr.x + beta * m.x, rr.y + beta * m.y);
+                        }
+                    }
+#pragma unroll
+                for (int a = 0; a < D; ++a)
+#pragma unroll
+                    for (int ch = 0; ch < NCH; ++ch) {
+                        const int col = 2 * sub + ch * 2 * LPR;
+                        y[a][ch] = (col < d.ld) ? ld2(Yl + ((int64_t)blk * B + a) * d.ld + col) : make_double2(0.0, 0.0);
+                    }
+            }
             double T[D][D];
             msdp_block_symdot<D, LPR, NCH>(v, y, T);
 #pragma unroll
-            for (int a = 0; a < D; ++a)
+            for (int a = 0; a < B; ++a)
 #pragma unroll
                 for (int ch = 0; ch < NCH; ++ch) {
                     const int col = 2 * sub + ch * 2 * LPR;
                     if (col < d.ld) {
                         double2 t = v[a][ch];
+                        if (a < D) {
 #pragma unroll
-                        for (int b = 0; b < D; ++b) { t.x -= T[a][b] * y[b][ch].x; t.y -= T[a][b] * y[b][ch].y; }
-                        st2(d.md + ((int64_t)blk * D + a) * d.ld + col, t);
+                            for (int b = 0; b < D; ++b) { t.x -= T[a][b] * y[b][ch].x; t.y -= T[a][b] * y[b][ch].y; }
+                        }
+                        st2(d.md + ((int64_t)blk * B + a) * d.ld + col, t);
                     }
                 }
         }
     }
 }
 
-// x_prop = retr(x, eta) into the other slot -- the polar factor of every block of x + eta -- and the partial of
-// <eta, grad + .5 * Heta> (trustregions.m:549-550)
-template <int D, int LPR, int NCH>
-__global__ __launch_bounds__(StfBlock<NCH>::threads) void k_stf_retract(Dev d) {
+// x_prop = retr(x, eta) into the other slot -- the polar factor of the rotation rows of every block of x + eta, a free row of
+// x + eta as it is -- and the partial of <eta, grad + .5 * Heta> (trustregions.m:549-550)
+template <int D, int EF, int LPR, int NCH>
+__global__ __launch_bounds__((BlockRows<D + EF, NCH>::threads)) void k_stf_retract(Dev d) {
     __shared__ double sh[3 * MSDP_WAVES];
     const Ctl* c = d.ctl;
     if (c->done) return;
-    constexpr int WAVES = StfBlock<NCH>::threads / 64, BPW = 64 / LPR;
+    constexpr int B = D + EF, WAVES = BlockRows<B, NCH>::threads / 64, BPW = 64 / LPR;
     int lo, hi;
     msdp_chunk_rows(d.nb, d.G, lo, hi);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -223,33 +294,36 @@ __global__ __launch_bounds__(StfBlock<NCH>::threads) void k_stf_retract(Dev d) {
     for (int b0 = lo + wave * BPW; b0 < hi; b0 += WAVES * BPW) {
         const int blk = b0 + rsub;
         if (blk < hi) {
-            double2 x[D][NCH];
+            double2 x[B][NCH];
 #pragma unroll
-            for (int a = 0; a < D; ++a)
+            for (int a = 0; a < B; ++a)
 #pragma unroll
                 for (int ch = 0; ch < NCH; ++ch) {
                     const int col = 2 * sub + ch * 2 * LPR;
                     x[a][ch] = make_double2(0.0, 0.0);
                     if (col < d.ld) {
-                        const int64_t o = ((int64_t)blk * D + a) * d.ld + col;
+                        const int64_t o = ((int64_t)blk * B + a) * d.ld + col;
                         const double2 y = ld2(Yl + o), e = ld2(eta + o), he = ld2(Heta + o), gv = ld2(g + o);
                         x[a][ch] = make_double2(y.x + e.x, y.y + e.y);
                         prd += e.x * (gv.x + 0.5 * he.x) + e.y * (gv.y + 0.5 * he.y);
                     }
                 }
             double Gm[D][D], R[D][D];
-            msdp_block_symdot<D, LPR, NCH>(x, x, Gm);       // A A'
+            msdp_block_symdot<D, LPR, NCH>(x, x, Gm);       // A A' of the rotation rows
             msdp_sym_invsqrt<D>(Gm, R);
 #pragma unroll
-            for (int a = 0; a < D; ++a)
+            for (int a = 0; a < B; ++a)
 #pragma unroll
                 for (int ch = 0; ch < NCH; ++ch) {
                     const int col = 2 * sub + ch * 2 * LPR;
                     if (col < d.ld) {
-                        double2 t = make_double2(0.0, 0.0);
+                        double2 t = x[a][ch];                   // a free row: tau + eta
+                        if (a < D) {
+                            t = make_double2(0.0, 0.0);
 #pragma unroll
-                        for (int b = 0; b < D; ++b) { t.x += R[a][b] * x[b][ch].x; t.y += R[a][b] * x[b][ch].y; }
-                        st2(Yp + ((int64_t)blk * D + a) * d.ld + col, t);
+                            for (int b = 0; b < D; ++b) { t.x += R[a][b] * x[b][ch].x; t.y += R[a][b] * x[b][ch].y; }
+                        }
+                        st2(Yp + ((int64_t)blk * B + a) * d.ld + col, t);
                     }
                 }
         }
@@ -258,12 +332,13 @@ __global__ __launch_bounds__(StfBlock<NCH>::threads) void k_stf_retract(Dev d) {
 }
 
 // M.proj and M.retr for the fine-grained entry points: one thread per block
-template <int D>
+template <int D, int EF>
 __global__ void k_stf_proj_simple(const double* __restrict__ Y, const double* __restrict__ U, double* __restrict__ V, int nb, int ld) {
+    constexpr int B = D + EF;
     for (int blk = blockIdx.x * blockDim.x + threadIdx.x; blk < nb; blk += gridDim.x * blockDim.x) {
-        const double* y = Y + (int64_t)blk * D * ld;
-        const double* u = U + (int64_t)blk * D * ld;
-        double* v = V + (int64_t)blk * D * ld;
+        const double* y = Y + (int64_t)blk * B * ld;
+        const double* u = U + (int64_t)blk * B * ld;
+        double* v = V + (int64_t)blk * B * ld;
         double T[D][D];
 #pragma unroll
         for (int a = 0; a < D; ++a)
@@ -281,16 +356,18 @@ __global__ void k_stf_proj_simple(const double* __restrict__ Y, const double* __
                 for (int b = 0; b < D; ++b) t -= T[a][b] * y[b * ld + c];
                 v[a * ld + c] = t;
             }
+            if constexpr (EF) v[D * ld + c] = u[D * ld + c];
         }
     }
 }
-template <int D>
+template <int D, int EF>
 __global__ void k_stf_retr_simple(const double* __restrict__ Y, const double* __restrict__ U, double* __restrict__ Z, double alpha,
                                   int nb, int ld) {
+    constexpr int B = D + EF;
     for (int blk = blockIdx.x * blockDim.x + threadIdx.x; blk < nb; blk += gridDim.x * blockDim.x) {
-        const double* y = Y + (int64_t)blk * D * ld;
-        const double* u = U + (int64_t)blk * D * ld;
-        double* z = Z + (int64_t)blk * D * ld;
+        const double* y = Y + (int64_t)blk * B * ld;
+        const double* u = U + (int64_t)blk * B * ld;
+        double* z = Z + (int64_t)blk * B * ld;
         double Gm[D][D], R[D][D];
 #pragma unroll
         for (int a = 0; a < D; ++a)
@@ -312,116 +389,101 @@ __global__ void k_stf_retr_simple(const double* __restrict__ Y, const double* __
                 for (int b = 0; b < D; ++b) t += R[a][b] * x[b];
                 z[a * ld + c] = t;
             }
+            if constexpr (EF) z[D * ld + c] = y[D * ld + c] + alpha * u[D * ld + c];
         }
     }
 }
 
-// w = C v - blockdiag(Lambda) v for a vector of n = nb * D entries (the escape's S * v): one thread per block row
-template <int D>
+// w = C v - blockdiag(Lambda (+) 0) v for a vector of n = nb * B entries (the escape's S * v): one thread per block row
+template <int D, int EF>
 __global__ void k_stf_sv(int nb, const int* __restrict__ brp, const int* __restrict__ bci, const double* __restrict__ bval,
                          const double* __restrict__ Lam, const double* __restrict__ v, double* __restrict__ w) {
+    constexpr int B = D + EF;
     for (int blk = blockIdx.x * blockDim.x + threadIdx.x; blk < nb; blk += gridDim.x * blockDim.x) {
-        double acc[D];
+        double acc[B];
 #pragma unroll
-        for (int a = 0; a < D; ++a) acc[a] = 0.0;
+        for (int a = 0; a < B; ++a) acc[a] = 0.0;
         for (int k = brp[blk]; k < brp[blk + 1]; ++k) {
             const int j = bci[k];
 #pragma unroll
-            for (int a = 0; a < D; ++a)
+            for (int a = 0; a < B; ++a)
 #pragma unroll
-                for (int b = 0; b < D; ++b) acc[a] = fma(bval[(int64_t)k * (D * D) + a * D + b], v[(int64_t)j * D + b], acc[a]);
+                for (int b = 0; b < B; ++b) acc[a] = fma(bval[(int64_t)k * (B * B) + a * B + b], v[(int64_t)j * B + b], acc[a]);
         }
 #pragma unroll
-        for (int a = 0; a < D; ++a) {
+        for (int a = 0; a < B; ++a) {
             double t = acc[a];
+            if (a < D) {
 #pragma unroll
-            for (int b = 0; b < D; ++b) t -= Lam[(int64_t)blk * (D * D) + a * D + b] * v[(int64_t)blk * D + b];
-            w[(int64_t)blk * D + a] = t;
+                for (int b = 0; b < D; ++b) t -= Lam[(int64_t)blk * (D * D) + a * D + b] * v[(int64_t)blk * B + b];
+            }
+            w[(int64_t)blk * B + a] = t;
         }
     }
 }
 
 // ------------------------------------------------------------------ launchers
-// One instance per lanes-per-block count: widths up to 2 * 64 * 2 = 256
-#define STF_LAUNCH(KERNEL, DD, L, N, h, ...) \
-    hipLaunchKernelGGL((KERNEL<DD, L, N>), dim3((h)->d.G), dim3(StfBlock<N>::threads), 0, (h)->stream, __VA_ARGS__)
-#define STF_DISPATCH_D(KERNEL, DD, h, ...)                                                           \
+// One instance per lanes-per-block count (MSDP_BLOCK_WIDTH_LADDER, widths up to 256) for each of the four kinds <D, EF> =
+// <d.blk - d.efree, d.efree>: the arguments of STF_KIND after the handle are a statement that names D_ and EF_
+#define STF_KIND(h, ...)                                                                             \
     do {                                                                                             \
-        const int half = (h)->d.ld / 2;                                                              \
-        if (half <= 1) STF_LAUNCH(KERNEL, DD, 1, 1, h, __VA_ARGS__);                                 \
-        else if (half <= 2) STF_LAUNCH(KERNEL, DD, 2, 1, h, __VA_ARGS__);                            \
-        else if (half <= 4) STF_LAUNCH(KERNEL, DD, 4, 1, h, __VA_ARGS__);                            \
-        else if (half <= 8) STF_LAUNCH(KERNEL, DD, 8, 1, h, __VA_ARGS__);                            \
-        else if (half <= 16) STF_LAUNCH(KERNEL, DD, 16, 1, h, __VA_ARGS__);                          \
-        else if (half <= 32) STF_LAUNCH(KERNEL, DD, 32, 1, h, __VA_ARGS__);                          \
-        else if (half <= 64) STF_LAUNCH(KERNEL, DD, 64, 1, h, __VA_ARGS__);                          \
-        else if (half <= 128) STF_LAUNCH(KERNEL, DD, 64, 2, h, __VA_ARGS__);                         \
-        else {                                                                                       \
-            msdp_set_error("unit-block-diagonal handle: factor width p = %d exceeds the supported maximum of 256", (h)->d.p); \
-            return MSDP_EUNSUPPORTED;                                                                \
-        }                                                                                            \
-    } while (0)
-#define STF_DISPATCH(KERNEL, h, ...)                                                                 \
-    do {                                                                                             \
-        if ((h)->d.manifold != MANI_STIEFEL || !(h)->d.brp) { msdp_set_error("not a unit-block-diagonal handle"); return MSDP_ESTATE; } \
-        if ((h)->d.blk == 2) STF_DISPATCH_D(KERNEL, 2, h, __VA_ARGS__);                              \
-        else STF_DISPATCH_D(KERNEL, 3, h, __VA_ARGS__);                                              \
+        const int dd_ = (h)->d.blk - (h)->d.efree;                                                   \
+        if (dd_ == 2 && !(h)->d.efree) { constexpr int D_ = 2, EF_ = 0; __VA_ARGS__; }               \
+        else if (dd_ == 3 && !(h)->d.efree) { constexpr int D_ = 3, EF_ = 0; __VA_ARGS__; }          \
+        else if (dd_ == 2) { constexpr int D_ = 2, EF_ = 1; __VA_ARGS__; }                           \
+        else { constexpr int D_ = 3, EF_ = 1; __VA_ARGS__; }                                         \
         HIPCHK(hipGetLastError());                                                                   \
+    } while (0)
+#define STF_DISPATCH(BLOCK, KERNEL, h, ...)                                                          \
+    do {                                                                                             \
+        if ((h)->d.manifold != MANI_STIEFEL || !(h)->d.brp) { msdp_set_error("not a %s handle", msdp_block_kind_name((h)->d.efree)); return MSDP_ESTATE; } \
+        STF_KIND(h, MSDP_BLOCK_WIDTH_LADDER((h)->d.ld, hipLaunchKernelGGL((KERNEL<D_, EF_, LPR_, NCH_>), dim3((h)->d.G),          \
+                                                                          dim3(BLOCK<D_ + EF_, NCH_>::threads), 0, (h)->stream, __VA_ARGS__)) { \
+            msdp_set_error("%s handle: factor width p = %d exceeds the supported maximum of 256", msdp_block_kind_name((h)->d.efree), (h)->d.p); \
+            return MSDP_EUNSUPPORTED;                                                                \
+        });                                                                                          \
     } while (0)
 
 int msdp_stiefel_costgrad(msdp_handle h, int slot) {
-    if (h->d.efree) return msdp_pose_costgrad(h, slot);      // blocks with a free row: msdp_pose.hip, here and below
-    if (slot < 0 || slot > 1) { msdp_set_error("unit-block-diagonal handle: point slot %d", slot); return MSDP_EINVAL; }
-    STF_DISPATCH(k_stf_costgrad, h, h->d, slot);
+    if (slot < 0 || slot > 1) { msdp_set_error("%s handle: point slot %d", msdp_block_kind_name(h->d.efree), slot); return MSDP_EINVAL; }
+    STF_DISPATCH(BlockRows, k_stf_costgrad, h, h->d, slot);
     return 0;
 }
 int msdp_stiefel_hess(msdp_handle h) {
-    if (h->d.efree) return msdp_pose_hess(h);
-    STF_DISPATCH(k_stf_hess, h, h->d);
+    STF_DISPATCH(BlockRows3, k_stf_hess, h, h->d);
     return 0;
 }
 int msdp_stiefel_upd2(msdp_handle h) {
-    if (h->d.efree) return msdp_pose_upd2(h);
-    STF_DISPATCH(k_stf_upd2, h, h->d);
+    STF_DISPATCH(BlockRows, k_stf_upd2, h, h->d);
     return 0;
 }
 int msdp_stiefel_retract(msdp_handle h) {
-    if (h->d.efree) return msdp_pose_retract(h);
-    STF_DISPATCH(k_stf_retract, h, h->d);
+    STF_DISPATCH(BlockRows, k_stf_retract, h, h->d);
     return 0;
 }
 int msdp_stiefel_proj(msdp_handle h, const double* Y, const double* U, double* V) {
-    if (h->d.efree) return msdp_pose_proj(h, Y, U, V);
     const Dev& d = h->d;
     const dim3 gr((d.nb + 255) / 256), bl(256);
-    if (d.blk == 2) hipLaunchKernelGGL(k_stf_proj_simple<2>, gr, bl, 0, h->stream, Y, U, V, d.nb, d.ld);
-    else hipLaunchKernelGGL(k_stf_proj_simple<3>, gr, bl, 0, h->stream, Y, U, V, d.nb, d.ld);
-    HIPCHK(hipGetLastError());
+    STF_KIND(h, hipLaunchKernelGGL((k_stf_proj_simple<D_, EF_>), gr, bl, 0, h->stream, Y, U, V, d.nb, d.ld));
     return 0;
 }
 int msdp_stiefel_retr(msdp_handle h, const double* Y, const double* U, double* Z, double alpha) {
-    if (h->d.efree) return msdp_pose_retr(h, Y, U, Z, alpha);
     const Dev& d = h->d;
     const dim3 gr((d.nb + 255) / 256), bl(256);
-    if (d.blk == 2) hipLaunchKernelGGL(k_stf_retr_simple<2>, gr, bl, 0, h->stream, Y, U, Z, alpha, d.nb, d.ld);
-    else hipLaunchKernelGGL(k_stf_retr_simple<3>, gr, bl, 0, h->stream, Y, U, Z, alpha, d.nb, d.ld);
-    HIPCHK(hipGetLastError());
+    STF_KIND(h, hipLaunchKernelGGL((k_stf_retr_simple<D_, EF_>), gr, bl, 0, h->stream, Y, U, Z, alpha, d.nb, d.ld));
     return 0;
 }
 int msdp_stiefel_sv(msdp_handle h, const double* Lam, const double* v, double* w) {
-    if (h->d.efree) return msdp_pose_sv(h, Lam, v, w);
     const Dev& d = h->d;
-    if (d.costkind != COST_BLOCK || !d.brp) { msdp_set_error("block product: not a unit-block-diagonal handle"); return MSDP_ESTATE; }
+    if (d.costkind != COST_BLOCK || !d.brp) { msdp_set_error("block product: not a %s handle", msdp_block_kind_name(d.efree)); return MSDP_ESTATE; }
     const dim3 gr((d.nb + 255) / 256), bl(256);
-    if (d.blk == 2) hipLaunchKernelGGL(k_stf_sv<2>, gr, bl, 0, h->stream, d.nb, d.brp, d.bci, d.bval, Lam, v, w);
-    else hipLaunchKernelGGL(k_stf_sv<3>, gr, bl, 0, h->stream, d.nb, d.brp, d.bci, d.bval, Lam, v, w);
-    HIPCHK(hipGetLastError());
+    STF_KIND(h, hipLaunchKernelGGL((k_stf_sv<D_, EF_>), gr, bl, 0, h->stream, d.nb, d.brp, d.bci, d.bval, Lam, v, w));
     return 0;
 }
 
 // Block CSR from the caller's CSC arrays of the symmetric order-N matrix (column j is read as row j, as for the scalar kinds).
 // Block row i collects the block columns its rows touch, ascending; a block the pattern covers only in part is zero-filled.
-// blk = the block order of the storage; efree of its rows are free (the pose-graph kind, msdp_pose.hip), and the multiplier
+// blk = the block order of the storage; efree of its rows are free (the pose-graph kind), and the multiplier
 // blocks Lam are of order blk - efree.
 int msdp_stiefel_setup(msdp_handle h, int blk, int efree, const int64_t* jc, const int64_t* ir, const double* val) {
     Dev& d = h->d;

@@ -1,4 +1,4 @@
-"""The pose-graph handle (msdp_create_posegraph_csc, Handle.posegraph, msdp_pose.hip) against the NumPy restatement of
+"""The pose-graph handle (msdp_create_posegraph_csc, Handle.posegraph, msdp_stiefel.hip) against the NumPy restatement of
 tests/posegraph_ref.py: point operations over every dispatched <LPR, NCH> instance for d = 2 and 3, consistency with the
 unit-block-diagonal handle when the free rows of C are zero, trustregions() counts, the escape's eigenpairs, whole solves
 against the restatement (whose optima carry their own certificate), and the refused calls."""

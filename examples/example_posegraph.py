@@ -8,7 +8,9 @@ argv = [n, default 2000; d, default 3; degree, default 8; sigma_r, default 0.1; 
 persistent launch where the handle is eligible (options["block_persist"]); --precon anywhere on the line: block-Jacobi preconditioned tCG
 (options["precon"] = "blockjacobi": the diagonal blocks of C; the handle then runs the generic trips); --device-factor anywhere on the
 line: the factor stays on the device between the trustregions() calls and the poses are rounded there too
-(options["block_factor"] = "device", options["round_blocks"]: data["R"] and data["t"], which the printed errors are then taken from)."""
+(options["block_factor"] = "device", options["round_blocks"]: data["R"] and data["t"], which the printed errors are then taken from);
+--block-escape anywhere on the line: the device escape and its cold check run the block eigen-solver on block storage instead of
+Lanczos (options["escape_method"] = 2; the device escape serves orders n (d + 1) above 600, data["escape_method"] says what ran)."""
 import sys
 import time
 
@@ -20,7 +22,8 @@ from manisdp_matlab_amd import problems, solvers
 persist = "--persist" in sys.argv
 precon = "--precon" in sys.argv
 device_factor = "--device-factor" in sys.argv
-sys.argv = [a for a in sys.argv if a not in ("--persist", "--precon", "--device-factor")]
+block_escape = "--block-escape" in sys.argv
+sys.argv = [a for a in sys.argv if a not in ("--persist", "--precon", "--device-factor", "--block-escape")]
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
 d = int(sys.argv[2]) if len(sys.argv) > 2 else 3
@@ -30,7 +33,8 @@ sigma_t = float(sys.argv[5]) if len(sys.argv) > 5 else 0.1
 C, R_true, t_true, edges, _, _ = problems.pose_graph(n, d, degree, sigma_r, sigma_t, int(sys.argv[6]) if len(sys.argv) > 6 else 0)
 t = time.time()
 Y, fval, data = solvers.ManiSDP_posegraph(C, d, {"tol": 1e-8, "block_persist": persist, "precon": "blockjacobi" if precon else None,
-                                               "block_factor": "device" if device_factor else "host", "round_blocks": device_factor})
+                                               "block_factor": "device" if device_factor else "host", "round_blocks": device_factor,
+                                               **({"escape_method": 2} if block_escape else {})})
 e = np.sqrt(np.maximum(np.linalg.eigvalsh(Y.T @ Y), 0.0))
 rank = int(np.sum(e >= 1e-3 * e.max()))
 R, pos = (data["R"], data["t"]) if "R" in data else problems.round_poses(Y, d)

@@ -6,7 +6,9 @@ global rotation the problem cannot see (problems.rotation_error).
 argv = [n, default 2000; d, default 3; degree, default 8; sigma, default 0.5; seed, default 0]; --persist anywhere on the line: the tCG of every trust-region iteration as one
 persistent launch where the handle is eligible (options["block_persist"]); --device-factor anywhere on the line: the factor stays on
 the device between the trustregions() calls and the rotations are rounded there too (options["block_factor"] = "device",
-options["round_blocks"]: data["R"], which the printed error is then taken from)."""
+options["round_blocks"]: data["R"], which the printed error is then taken from); --block-escape anywhere on the line: the device
+escape and its cold check run the block eigen-solver on block storage instead of Lanczos (options["escape_method"] = 2; the
+device escape serves orders n d above 600, data["escape_method"] says what ran)."""
 import sys
 import time
 
@@ -17,7 +19,8 @@ from manisdp_matlab_amd import problems, solvers
 
 persist = "--persist" in sys.argv
 device_factor = "--device-factor" in sys.argv
-sys.argv = [a for a in sys.argv if a not in ("--persist", "--device-factor")]
+block_escape = "--block-escape" in sys.argv
+sys.argv = [a for a in sys.argv if a not in ("--persist", "--device-factor", "--block-escape")]
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
 d = int(sys.argv[2]) if len(sys.argv) > 2 else 3
@@ -26,7 +29,7 @@ sigma = float(sys.argv[4]) if len(sys.argv) > 4 else 0.5
 C, R_true, edges = problems.rotation_synchronization(n, d, degree, sigma, int(sys.argv[5]) if len(sys.argv) > 5 else 0)
 t = time.time()
 Y, fval, data = solvers.ManiSDP_onlyunitblockdiag(C, d, {"tol": 1e-8, "block_persist": persist, "block_factor": "device" if device_factor else "host",
-                                                       "round_blocks": device_factor})
+                                                       "round_blocks": device_factor, **({"escape_method": 2} if block_escape else {})})
 e = np.sqrt(np.maximum(np.linalg.eigvalsh(Y.T @ Y), 0.0))
 rank = int(np.sum(e >= 1e-3 * e.max()))
 R = data["R"] if "R" in data else problems.round_rotations(Y, d)

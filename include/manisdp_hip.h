@@ -223,6 +223,15 @@ int msdp_debug_ritz_device(int32_t b, const double* G, const double* H, double* 
 /* Rayleigh-Ritz stages of the block eigen-solver since the handle was created, by where their dense algebra ran: on the
  * device, on the host, and on the host after the device kernel handed the stage back (status 1 or 2 above). */
 int msdp_debug_ritz_stages(msdp_handle h, int64_t* device, int64_t* host, int64_t* fallback);
+/* Test-only: the (panel width, lanes per block) pairs the filter step on block storage (k_be_step_blk, msdp_blockeig.hip) is
+ * instantiated for, pairs[2i], pairs[2i + 1] for the first `cap` of them; returns their number.  No GPU touched. */
+int msdp_debug_be_step_blk_instances(int32_t* pairs, int32_t cap);
+/* Test-only: one launch of that step on host panels at the resident point of a unit-block-diagonal or pose-graph handle.  Xin,
+ * Xio: N x b row-major (N = the handle's order, b = 32 / 64 / 128 columns); Xio <- f1 * (S * Xin) - f1 * cs * Xin - f2 * Xio
+ * with S = C - blockdiag(Lambda_i (+) 0) (prev = 0: without the last term).  lpr: lanes per block; a (b, lpr) pair without an
+ * instance is MSDP_EUNSUPPORTED.  The route's lower limit N >= 256 does not apply. */
+int msdp_debug_be_step_blk(msdp_handle h, int32_t b, int32_t lpr, const double* Xin, double* Xio, double f1, double cs, double f2,
+                           int32_t prev);
 /* Test-only: make a sparse-C handle rank `rank` of `nranks` WITHOUT a communicator (same row split, local CSR/ELL
  * rows with global column indices and gather buffer as msdp_comm_init sets up), so that one GPU can check every
  * shard's kernels against the unsharded result.  Call right after create, before any point is set. */
@@ -533,8 +542,9 @@ int msdp_escape_eigs_matrix(msdp_handle h, const double* S, int32_t k, double to
 
 /* Which eigen-solver the LAST escape call on this handle ran: 1 = block Chebyshev-filtered subspace iteration
  * (msdp_blockeig.hip: sparse C; a 64- or 128-wide panel, reduction-free filter steps on the S*U kernel, Rayleigh-Ritz every
- * few hundred steps; Hermitian C with "escape_method" = 2: a complex panel of 32 or 64 columns), 0 = deflated single-vector
- * Lanczos runs (msdp_escape.hip: dense S, pre-sharded dense C, small n, Hermitian C unless asked). */
+ * few hundred steps; Hermitian C with "escape_method" = 2: a complex panel of 32 or 64 columns; the block kinds with
+ * "escape_method" = 2: the filter step on block storage), 0 = deflated single-vector Lanczos runs (msdp_escape.hip: dense S,
+ * pre-sharded dense C, small n, Hermitian C and the block kinds unless asked). */
 int msdp_escape_method(msdp_handle h, int32_t* method);
 
 /* Collective calls this handle has issued on its communicator so far (row exchange, all-reduce, all-gather; operations grouped
@@ -727,7 +737,10 @@ int msdp_block_reshape(msdp_handle h, int32_t nb, const int64_t* row0, const int
  *                       2 = always (tests); 0 = never
  *   "escape_method" 0 = block eigen-solver where it applies (sparse C, n >= 512), Lanczos otherwise (default); 1 = Lanczos
  *                       always; 2 = block also for small n (tests).  Hermitian C: 0 and 1 = Lanczos on the real view; 2 = the
- *                       block eigen-solver on a complex panel (single rank, n >= 256; Lanczos below that)
+ *                       block eigen-solver on a complex panel (single rank, n >= 256; Lanczos below that).  Block kinds
+ *                       (unit-block-diagonal, pose-graph): 0 and 1 = Lanczos over the one-thread-per-block product; 2 = the
+ *                       block eigen-solver on block storage (k_be_step_blk: panels of 32 / 64 / 128 columns, a lane group per
+ *                       block; order N = nb * B >= 256 and factor width p <= 112, Lanczos otherwise)
  *   "escape_rr"    0/1  block eigen-solver, dense algebra of a Rayleigh-Ritz stage (b x b problem H c = theta G c, residual
  *                       sums): 0 = on the host (default: Cholesky + tred2 / tql2 on one thread between two copies and two
  *                       synchronisations), 1 = on the device for panels of 32 / 64 columns (one workgroup, Cholesky + cyclic

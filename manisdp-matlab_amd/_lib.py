@@ -113,6 +113,8 @@ SIGNATURES = {
     "msdp_debug_ritz_herm": (C.c_int, [C.c_int32, _dp, _dp, _dp, _dp, _P(C.c_int32)]),
     "msdp_debug_ritz_device": (C.c_int, [C.c_int32, _dp, _dp, _dp, _dp, _P(C.c_int32), _P(C.c_int32)]),
     "msdp_debug_ritz_stages": (C.c_int, [C.c_void_p, _P(C.c_int64), _P(C.c_int64), _P(C.c_int64)]),
+    "msdp_debug_be_step_blk_instances": (C.c_int, [_P(C.c_int32), C.c_int32]),
+    "msdp_debug_be_step_blk": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp, C.c_double, C.c_double, C.c_double, C.c_int32]),
     "msdp_get_dual_slack": (C.c_int, [C.c_void_p, _dp]),
     "msdp_get_dual_slack_block": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _dp]),
     "msdp_block_eigs": (C.c_int, [C.c_void_p, C.c_int32, _i64p, _i64p, C.c_int32, C.c_int32, _dp, _dp]),
@@ -261,6 +263,16 @@ def ritz_device(G, H):
     rank, status = C.c_int32(), C.c_int32()
     _check(load().msdp_debug_ritz_device(b, _dptr(G), _dptr(H), _dptr(theta), _dptr(W), C.byref(rank), C.byref(status)))
     return theta, W, rank.value, status.value
+
+
+def be_step_blk_instances():
+    """The (panel width, lanes per block) pairs the block eigen-solver's filter step on block storage is instantiated for
+    (msdp_debug_be_step_blk_instances; no GPU touched), in the order of the dispatch."""
+    buf = (C.c_int32 * 64)()
+    cnt = load().msdp_debug_be_step_blk_instances(buf, 32)
+    if cnt < 0 or cnt > 32:
+        raise RuntimeError(f"be_step_blk_instances: {cnt} instances reported")
+    return [(int(buf[2 * i]), int(buf[2 * i + 1])) for i in range(cnt)]
 
 
 def ritz_herm(G, H):
@@ -875,7 +887,8 @@ class Handle:
         (missing pairs: +inf and a zero vector; escape_info() says how many are real).  V is (n, k), complex on an
         onlyunitdiag_hermitian handle.  Which eigen-solver ran: escape_method().  A Hermitian handle takes the Lanczos path on the
         real view unless set_option("escape_method", 2) asks for the block eigen-solver on a complex panel (single rank,
-        n >= 256, k <= 56); maxit is then the budget of filter steps."""
+        n >= 256, k <= 56); maxit is then the budget of filter steps.  An onlyunitblockdiag or posegraph handle takes the Lanczos
+        path unless set_option("escape_method", 2) asks for the block eigen-solver on block storage (N >= 256, k <= 64)."""
         lam = np.empty(k)
         V = np.empty((self.n, k), order="F", dtype=np.complex128 if self.hermitian else np.float64)   # complex: (re, im) pairs, column by column
         lmax = C.c_double()
@@ -922,6 +935,17 @@ class Handle:
         v = C.c_int32()
         _check(self._lib.msdp_escape_method(self._h, C.byref(v)))
         return v.value
+
+    def be_step_blk(self, b, lpr, Xin, Xio, f1, cs, f2, prev):
+        """One launch of the block eigen-solver's filter step on block storage (msdp_debug_be_step_blk) at the resident point of a
+        unit-block-diagonal or pose-graph handle: returns f1 * (S @ Xin) - f1 * cs * Xin - f2 * Xio (prev false: without the last
+        term) for (N, b) panels, b = 32 / 64 / 128, with lpr lanes per block.  Xio is not modified."""
+        Xin = np.ascontiguousarray(Xin, dtype=np.float64)
+        out = np.array(Xio, dtype=np.float64, order="C")
+        if Xin.shape != (self.n, int(b)) or out.shape != Xin.shape:
+            raise ValueError(f"be_step_blk: panels must be ({self.n}, {int(b)})")
+        _check(self._lib.msdp_debug_be_step_blk(self._h, int(b), int(lpr), _dptr(Xin), _dptr(out), float(f1), float(cs), float(f2), 1 if prev else 0))
+        return out
 
     def ritz_stages(self):
         """(device, host, fallback): Rayleigh-Ritz stages of the block eigen-solver on this handle so far whose dense algebra ran

@@ -43,6 +43,9 @@ struct BeOp {                            // S = C - diag(z) with sparse C (all n
     const double* M;                     // dense operand (n x nS row-major, msdp_dense.hip layout) or null
     const double2* hzv; const double2* hzell;   // Hermitian C (COST_HERM): the complex values of the rows beside rp / ci and ellc (cv and ellv
                                          //   are null); n then counts COMPLEX rows, a panel row is b/2 complex numbers, one per double2
+    const int* brp; const int* bci; const double* bval; const double* Lam;   // block storage (COST_BLOCK): S = C - blockdiag(Lam_i (+) 0) with C in
+    int nb, D, EF;                       //   the handle's block CSR (nb block rows of order D + EF, n = nb * (D + EF)), Lam the D x D multiplier
+                                         //   blocks of the resident point; rp / ci / cv / z are null.  brp null: not this form
 };
 
 #define BE_ELL_MAXW 8
@@ -205,6 +208,96 @@ __global__ __launch_bounds__(MSDP_BLOCK) void k_be_step_herm(BeOp a, const doubl
                 o2.y = fma(f1, acc[ch].y, fma(g, x[ch].y, -f2 * pv[ch].y));
                 st2(Xio + (int64_t)row * a.b + 2 * sub + ch * 2 * LPR, o2);
             }
+        }
+    }
+}
+
+// The filter step on block storage (COST_BLOCK: the unit-block-diagonal and the pose-graph kind): S = C - blockdiag(Lambda_i (+) 0_EF)
+// on N = nb * B rows, B = D + EF, C in the handle's block CSR and Lambda the D x D multiplier blocks of the resident point -- the
+// operator of k_stf_sv (msdp_stiefel.hip) on a panel.  A lane group of LPR lanes owns one BLOCK: its B panel rows of NCH double2
+// each (2 * LPR * NCH == b).  Per stored entry the group reads the B * B values once (the same addresses in every lane of the
+// group), gathers the B contiguous panel rows of the neighbour block once and uses each B times: the panel form of spmm_block
+// (msdp_device.h), entries in ascending block-column order.  The Lambda term takes the place of z[row] * x of k_be_step: a D x D
+// product on the block's own rows of Xin, nothing on the free row.  The block's own rows of Xin and Xio are read behind the
+// gather (the LATE form of k_be_step_herm): the accumulators, one gathered set and the values of an entry are what is live in
+// the loop.  Workgroup chunks are over blocks, so that a block never straddles two workgroups.
+// Every instance runs the 16 waves of MSDP_BLOCK: the largest (B = 4, two chunks per lane: 2 x 32 registers of accumulators and
+// gathered rows beside 32 of values) takes 102 registers of the 128 a lane has there, none uses scratch (DESIGN.md section 4 has
+// the table).
+// (panel width, lanes per block, chunks per lane) of every instance: the dispatch and msdp_debug_be_step_blk_instances read this list
+#define BE_BLK_INSTANCES(X) X(32, 16, 1) X(32, 8, 2) X(64, 32, 1) X(64, 16, 2) X(128, 64, 1) X(128, 32, 2)
+
+template <int D, int EF, int LPR, int NCH, bool PREV>
+__global__ __launch_bounds__(MSDP_BLOCK) void k_be_step_blk(BeOp a, const double* __restrict__ Xin, double* __restrict__ Xio,
+                                                             double f1, double cs, double f2) {
+    constexpr int B = D + EF, WAVES = MSDP_WAVES, BPW = 64 / LPR;
+    int lo, hi;
+    msdp_chunk_rows(a.nb, a.G, lo, hi);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int sub = lane & (LPR - 1), gsub = lane / LPR;
+    const int* __restrict__ bci = a.bci;
+    const double* __restrict__ bval = a.bval;
+    for (int blk0 = lo + wave * BPW; blk0 < hi; blk0 += WAVES * BPW) {
+        const int blk = blk0 + gsub;
+        if (blk < hi) {
+            double2 acc[B][NCH], x[B][NCH];
+#pragma unroll
+            for (int r = 0; r < B; ++r)
+#pragma unroll
+                for (int ch = 0; ch < NCH; ++ch) acc[r][ch] = make_double2(0.0, 0.0);
+            const int start = a.brp[blk], end = a.brp[blk + 1];
+#pragma unroll 1
+            for (int k = start; k < end; ++k) {
+                const int j = bci[k];
+                double c[B][B];
+#pragma unroll
+                for (int r = 0; r < B; ++r)
+#pragma unroll
+                    for (int q = 0; q < B; ++q) c[r][q] = bval[(int64_t)k * (B * B) + r * B + q];
+                const double* src = Xin + (int64_t)j * B * a.b + 2 * sub;
+#pragma unroll
+                for (int q = 0; q < B; ++q)
+#pragma unroll
+                    for (int ch = 0; ch < NCH; ++ch) x[q][ch] = ld2(src + (int64_t)q * a.b + ch * 2 * LPR);
+#pragma unroll
+                for (int r = 0; r < B; ++r)
+#pragma unroll
+                    for (int q = 0; q < B; ++q)
+#pragma unroll
+                        for (int ch = 0; ch < NCH; ++ch) {
+                            acc[r][ch].x = fma(c[r][q], x[q][ch].x, acc[r][ch].x);
+                            acc[r][ch].y = fma(c[r][q], x[q][ch].y, acc[r][ch].y);
+                        }
+            }
+            // the block's own rows: acc <- (S*Xin) = acc - Lambda * x on the D rotation rows, then the recurrence row by row
+            const int64_t own = (int64_t)blk * B * a.b + 2 * sub;
+#pragma unroll
+            for (int q = 0; q < B; ++q)
+#pragma unroll
+                for (int ch = 0; ch < NCH; ++ch) x[q][ch] = ld2(Xin + own + (int64_t)q * a.b + ch * 2 * LPR);
+#pragma unroll
+            for (int r = 0; r < D; ++r)
+#pragma unroll
+                for (int q = 0; q < D; ++q) {
+                    const double l = -a.Lam[(int64_t)blk * (D * D) + r * D + q];
+#pragma unroll
+                    for (int ch = 0; ch < NCH; ++ch) {
+                        acc[r][ch].x = fma(l, x[q][ch].x, acc[r][ch].x);
+                        acc[r][ch].y = fma(l, x[q][ch].y, acc[r][ch].y);
+                    }
+                }
+            const double g = -f1 * cs;
+#pragma unroll
+            for (int r = 0; r < B; ++r)
+#pragma unroll
+                for (int ch = 0; ch < NCH; ++ch) {
+                    double* dst = Xio + own + (int64_t)r * a.b + ch * 2 * LPR;
+                    const double2 pv = PREV ? ld2(dst) : make_double2(0.0, 0.0);
+                    double2 o2;
+                    o2.x = fma(f1, acc[r][ch].x, fma(g, x[r][ch].x, -f2 * pv.x));
+                    o2.y = fma(f1, acc[r][ch].y, fma(g, x[r][ch].y, -f2 * pv.y));
+                    st2(dst, o2);
+                }
         }
     }
 }
@@ -816,8 +909,37 @@ static void be_launch_step(msdp_handle h, const BeOp& a, const double* Xin, doub
         else hipLaunchKernelGGL((k_be_step<LPR, NCH, false, false>), grid, block, 0, h->stream, a, Xin, Xio, f1, cs, f2);
     }
 }
+// Block storage: one instance of k_be_step_blk per entry of BE_BLK_INSTANCES and kind <D, EF>
+template <int D, int EF, int LPR, int NCH>
+static void be_launch_step_blk(msdp_handle h, const BeOp& a, const double* Xin, double* Xio, double f1, double cs, double f2, bool prev) {
+    const dim3 grid(a.G), block(MSDP_BLOCK);
+    if (prev) hipLaunchKernelGGL((k_be_step_blk<D, EF, LPR, NCH, true>), grid, block, 0, h->stream, a, Xin, Xio, f1, cs, f2);
+    else hipLaunchKernelGGL((k_be_step_blk<D, EF, LPR, NCH, false>), grid, block, 0, h->stream, a, Xin, Xio, f1, cs, f2);
+}
+template <int D, int EF>
+static int be_step_blk_kind(msdp_handle h, const BeOp& a, int lpr, const double* Xin, double* Xio, double f1, double cs, double f2, bool prev) {
+#define BE_BLK_TRY(W, L, N) if (a.b == W && lpr == L) { be_launch_step_blk<D, EF, L, N>(h, a, Xin, Xio, f1, cs, f2, prev); HIPCHK(hipGetLastError()); return 0; }
+    BE_BLK_INSTANCES(BE_BLK_TRY)
+#undef BE_BLK_TRY
+    msdp_set_error("block eigen-solver: no block-storage kernel for block width %d with %d lanes per block", a.b, lpr);
+    return MSDP_EUNSUPPORTED;
+}
+// lanes per block (lpr <= 0: chosen here): two chunks per lane (b / 4 lanes) -- twice the blocks per pass of the 16 waves and two
+// gathers in flight per row; measured at n = 10 000 on both kinds and all three widths: never slower than one chunk per lane, up
+// to 28 % faster (64 columns, B = 4: 32.6 against 45.1 us a step)
+static int be_step_blk(msdp_handle h, const BeOp& a, int lpr, const double* Xin, double* Xio, double f1, double cs, double f2, bool prev) {
+    if (lpr <= 0) lpr = a.b / 4;
+    if (a.D == 2 && !a.EF) return be_step_blk_kind<2, 0>(h, a, lpr, Xin, Xio, f1, cs, f2, prev);
+    if (a.D == 3 && !a.EF) return be_step_blk_kind<3, 0>(h, a, lpr, Xin, Xio, f1, cs, f2, prev);
+    if (a.D == 2 && a.EF == 1) return be_step_blk_kind<2, 1>(h, a, lpr, Xin, Xio, f1, cs, f2, prev);
+    if (a.D == 3 && a.EF == 1) return be_step_blk_kind<3, 1>(h, a, lpr, Xin, Xio, f1, cs, f2, prev);
+    msdp_set_error("block eigen-solver: no block-storage kernel for blocks of %d + %d rows", a.D, a.EF);
+    return MSDP_EUNSUPPORTED;
+}
+
 // lanes per row: the fewest (>= 8) that put a workgroup's rows into one pass of its 16 waves, cf. lpr_rebalance
 static int be_step(msdp_handle h, const BeOp& a, const double* Xin, double* Xio, double f1, double cs, double f2, bool prev) {
+    if (a.brp) return be_step_blk(h, a, h->tune.be_lpr, Xin, Xio, f1, cs, f2, prev);
     if (a.M) {
         // the contraction kernels take the panel geometry from the handle: borrow it for the launch (single rank, no graph)
         Dev& d = h->d;
@@ -986,6 +1108,15 @@ static int be_rayleigh_ritz(msdp_handle h, const BeOp& a, BeMem& m, const double
     return 0;
 }
 
+// workgroups of a filter step over `units` rows (block storage: blocks); the rule and its measurements: msdp_blockeig_run
+static int be_pick_grid(msdp_handle h, int units) {
+    int G = (((units + 15) / 16 + 7) / 8) * 8;
+    if (G > 256) G = (units > 256 * 128) ? 512 : 256;
+    if (G < 8) G = 8;
+    if (h->tune.be_grid > 0) G = ((h->tune.be_grid + 7) / 8) * 8;
+    return G;
+}
+
 int msdp_blockeig_eligible(msdp_handle h, const double* Mdev, bool w_loc) {
     if (h->tune.escape_method == 1) return 0;
     if (w_loc) return 0;                                                  // sharded dense product: Lanczos path
@@ -994,6 +1125,19 @@ int msdp_blockeig_eligible(msdp_handle h, const double* Mdev, bool w_loc) {
         // view until the route is timed on the device; single rank (the kind has no sharded form), the real kind's lower limit
         if (h->tune.escape_method != 2) return 0;
         if (h->nranks != 1 || h->use_comm || h->lgroup) return 0;
+        return h->d.n >= 256;
+    }
+    if (!Mdev && h->d.costkind == COST_BLOCK) {
+        // block CSR (the unit-block-diagonal and the pose-graph kind): the panel on block storage (k_be_step_blk) on request only --
+        // auto keeps the Lanczos path over k_stf_sv; single rank (the kinds refuse every communicator), the real kind's lower limit
+        // on N = nb * B
+        if (h->tune.escape_method != 2) return 0;
+        if (h->nranks != 1 || h->use_comm || h->lgroup) return 0;
+        if (!h->d.brp) return 0;
+        // A factor wider than the widest panel can hold beside its noise columns (p + 16 > 128; the kind allows p up to 256)
+        // takes the Lanczos path, which deflates span(Y) whatever its width: the block would sit inside the near-kernel of S
+        // and every call would run its budget out (the dense branch below has the measurement)
+        if (h->d.p + 16 > 128) return 0;
         return h->d.n >= 256;
     }
     if (Mdev || h->d.costkind != COST_SPARSE) {
@@ -1085,6 +1229,14 @@ int msdp_blockeig_run(msdp_handle h, int n, const int* rp, const int* ci, const 
     a.ellW = 0; a.ell_stride = 0; a.ellc = nullptr; a.ellv = nullptr;
     a.M = Mdense;
     a.hzv = herm ? h->d.hzv : nullptr; a.hzell = nullptr;
+    a.brp = nullptr; a.bci = nullptr; a.bval = nullptr; a.Lam = nullptr; a.nb = 0; a.D = 0; a.EF = 0;
+    const bool blockcsr = !Mdense && h->d.costkind == COST_BLOCK;
+    if (blockcsr) {
+        // block storage: the operator is the handle's own (block CSR and the multiplier blocks of the resident point), never the caller's rows
+        const Dev& d = h->d;
+        if (rp || ci || cv || z || !own_rows || n != d.n || !d.brp) { msdp_set_error("block eigen-solver: a %s handle runs on its own %d rows (block CSR and the multiplier blocks of the resident point)", msdp_block_kind_name(d.efree), d.n); return MSDP_ESTATE; }
+        a.brp = d.brp; a.bci = d.bci; a.bval = d.bval; a.Lam = d.Lam[h->h_ctl->cur]; a.nb = d.nb; a.D = d.blk - d.efree; a.EF = d.efree;
+    }
     if (herm && (!a.hzv || n != h->d.n)) { msdp_set_error("block eigen-solver: a Hermitian handle runs on its own %d complex rows", h->d.n); return MSDP_ESTATE; }
     if (Mdense && b != 64) { msdp_set_error("block eigen-solver: the dense route works on 64-wide panels"); return MSDP_EUNSUPPORTED; }
     if (!Mdense && own_rows && h->d.ellW > 0 && h->d.n_loc == n) { a.ellW = h->d.ellW; a.ell_stride = h->d.ell_stride; a.ellc = h->d.ellc; a.ellv = h->d.ellv; a.hzell = herm ? h->d.hzell : nullptr; }
@@ -1093,11 +1245,8 @@ int msdp_blockeig_run(msdp_handle h, int n, const int* rp, const int* ci, const 
         // grid: one workgroup per CU while its rows fit one pass of eight lanes per row (16 waves x 8 rows = 128 rows), two
         // beyond; measured on G81 (tools/archive/blockeig_tune.py): 256 workgroups x 8 lanes 19.2 ms for the cold check, 512 x 16 lanes
         // 21.8, 128 x 8 lanes 24.1
-        int G = (((n + 15) / 16 + 7) / 8) * 8;
-        if (G > 256) G = (n > 256 * 128) ? 512 : 256;
-        if (G < 8) G = 8;
-        if (h->tune.be_grid > 0) G = ((h->tune.be_grid + 7) / 8) * 8;
-        a.G = G;
+        // (block storage: the chunks are over blocks, a lane group per block -- the same arithmetic on nb)
+        a.G = be_pick_grid(h, blockcsr ? a.nb : n);
     }
     const unsigned seed = cold ? 0x9e3779b9u : 0x1234567u;
     hipLaunchKernelGGL(k_be_init, dim3(1024), dim3(256), 0, h->stream, n, b, Ypt, ld, ny, (const double*)m.prevV, nprev, seed, b, P0);
@@ -1283,6 +1432,49 @@ extern "C" int msdp_debug_ritz_herm(int32_t bc, const double* G, const double* H
     memcpy(theta, th.data(), (size_t)bc * sizeof(double));
     for (size_t e = 0; e < nn; ++e) { W[2 * e] = w[e].real(); W[2 * e + 1] = w[e].imag(); }
     *rank = r;
+    return 0;
+}
+// The (panel width, lanes per block) pairs k_be_step_blk is instantiated for, as pairs[2 * i], pairs[2 * i + 1]; returns their number
+// (cap: the pairs the caller's array holds; no GPU touched)
+extern "C" int msdp_debug_be_step_blk_instances(int32_t* pairs, int32_t cap) {
+    int cnt = 0;
+#define BE_BLK_LIST(W, L, N) if (pairs && cnt < cap) { pairs[2 * cnt] = W; pairs[2 * cnt + 1] = L; } ++cnt;
+    BE_BLK_INSTANCES(BE_BLK_LIST)
+#undef BE_BLK_LIST
+    return cnt;
+}
+// One launch of k_be_step_blk<D, EF, lpr, b / (2 lpr), prev> on host panels (N x b row-major, N = the handle's order) at the resident
+// point of a unit-block-diagonal or pose-graph handle: Xio <- f1 * (S * Xin) - f1 * cs * Xin - f2 * Xio (prev = 0: without the
+// last term).  The grid is the one msdp_blockeig_run picks (be_pick_grid, option be_grid included); the route's lower limit on N does not apply.
+extern "C" int msdp_debug_be_step_blk(msdp_handle h, int32_t b, int32_t lpr, const double* Xin, double* Xio, double f1, double cs, double f2, int32_t prev) {
+    if (!h) { msdp_set_error("null handle"); return MSDP_EINVAL; }
+    if (!Xin || !Xio || lpr < 1) { msdp_set_error("debug_be_step_blk: bad argument"); return MSDP_EINVAL; }
+    Dev& d = h->d;
+    if (d.costkind != COST_BLOCK || !d.brp) { msdp_set_error("debug_be_step_blk: only for unit-block-diagonal and pose-graph handles"); return MSDP_ESTATE; }
+    bool known = false;
+#define BE_BLK_KNOWN(W, L, N) known = known || (b == W && lpr == L);
+    BE_BLK_INSTANCES(BE_BLK_KNOWN)
+#undef BE_BLK_KNOWN
+    if (!known) { msdp_set_error("block eigen-solver: no block-storage kernel for block width %d with %d lanes per block", b, lpr); return MSDP_EUNSUPPORTED; }
+    int rc = msdp_ensure_state(h);
+    if (rc) return rc;
+    BeOp a;
+    memset(&a, 0, sizeof(a));
+    a.n = d.n; a.b = b;
+    a.brp = d.brp; a.bci = d.bci; a.bval = d.bval; a.Lam = d.Lam[msdp_host_cur(h)]; a.nb = d.nb; a.D = d.blk - d.efree; a.EF = d.efree;
+    a.G = be_pick_grid(h, a.nb);
+    const size_t panel = (size_t)d.n * b;
+    double* dev = nullptr;
+    if (hipMalloc((void**)&dev, 2 * panel * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); msdp_set_error("debug_be_step_blk: allocation failed"); return MSDP_ENOMEM; }
+    hipError_t e = msdp_memcpy_async(dev, Xin, panel * sizeof(double), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = msdp_memcpy_async(dev + panel, Xio, panel * sizeof(double), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) rc = be_step_blk(h, a, lpr, dev, dev + panel, f1, cs, f2, prev != 0);
+    if (e == hipSuccess && !rc) e = msdp_memcpy_async(Xio, dev + panel, panel * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    const hipError_t es = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess) e = es;
+    (void)hipFree(dev);
+    if (rc) return rc;
+    if (e != hipSuccess) { msdp_set_error("debug_be_step_blk: %s", hipGetErrorString(e)); return MSDP_EHIP; }
     return 0;
 }
 extern "C" int msdp_debug_ritz_stages(msdp_handle h, int64_t* device, int64_t* host, int64_t* fallback) {

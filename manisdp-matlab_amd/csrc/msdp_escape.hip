@@ -997,6 +997,11 @@ static int escape_impl_once(msdp_handle h, int k, double tol, int maxit, double*
         // complex rows and the factor itself (real stride, 2 * complex width real columns) and writes k vectors of length n to Q
         if (!rc && herm) rc = msdp_blockeig_run(h, d.n, d.rowptr, d.colind, nullptr, c.z, true, d.Y[cur], d.ld, d.p, k, tol, maxdeg, lmx, lres, lmin_est,
                                                 cold, use_y, lam_out, Q, &deg, &conv, &err, &lower, nullptr);
+        // Block CSR (COST_BLOCK): the operator is the handle's own block storage and the multiplier blocks of the resident point
+        // (k_be_step_blk) -- no scalar rows and no z; the factor's columns are ordinary N-vectors with S*Y = 0 at a critical point
+        else if (!rc && !Mdev && d.costkind == COST_BLOCK)
+            rc = msdp_blockeig_run(h, d.n, nullptr, nullptr, nullptr, nullptr, true, d.Y[cur], d.ld, d.p, k, tol, maxdeg, lmx, lres, lmin_est,
+                                   cold, use_y, lam_out, Q, &deg, &conv, &err, &lower, nullptr);
         else
         if (!rc) rc = msdp_blockeig_run(h, n, c.rp, c.ci, c.cv, c.z, !rep_sparse, c.Ypt, c.ld, c.p, k, tol, maxdeg, lmx, lres, lmin_est, cold, use_y,
                                         lam_out, Q, &deg, &conv, &err, &lower, Mdense);

@@ -140,15 +140,22 @@ def _extreme_eigs_host(S, k, dense_max):
 def _device_escape(h, run, o, data, default_tol, default_maxit):
     """One device escape call (``run(tol, maxit)`` -> lam, V, lam_max, steps) with the convergence contract of
     ``msdp_escape_info``: a Lanczos run that hit ``maxit`` only bounds lambda_min from above, so it is repeated
-    once with four times the step budget; ``certified`` tells the AL loop whether dinf may end the solve."""
+    once with four times the step budget; ``certified`` tells the AL loop whether dinf may end the solve.
+    ``options["escape_stats"] = True`` (every solver with a device escape shares this helper and _verify_lambda_min; off by
+    default, so ``data`` keeps its fields; the timing tools set it) counts in ``data["eig_calls"]`` / ``data["eig_steps"]`` the
+    calls made here and the steps they report, and in ``data["eig_verify_steps"]`` those of the cold checks."""
     tol = float(o.get("eig_tol", default_tol))
     maxit = int(o.get("eig_maxit", default_maxit))
-    lam, vS, lam_max, _ = run(tol, maxit)
+    lam, vS, lam_max, steps = run(tol, maxit)
     nvalid, conv, res = h.escape_info()
     if not conv:
         data["eig_retries"] = data.get("eig_retries", 0) + 1
-        lam, vS, lam_max, _ = run(tol, 4 * maxit)
+        lam, vS, lam_max, more = run(tol, 4 * maxit)
+        steps += more
         nvalid, conv, res = h.escape_info()
+    if o.get("escape_stats"):                             # on request (timing tools): escape calls and the steps they report -- Lanczos
+        data["eig_calls"] = data.get("eig_calls", 0) + 1    # steps, or filter steps and products of the block eigen-solver with its
+        data["eig_steps"] = data.get("eig_steps", 0) + int(steps)   # lambda_max run; the cold checks under "eig_verify_steps"
     if not conv:
         data["eig_unconverged"] = data.get("eig_unconverged", 0) + 1
     return lam, vS, lam_max, nvalid, conv
@@ -166,7 +173,8 @@ def _verify_lambda_min(h, run1, o, data, default_tol, default_maxit, dense_n=0):
       * otherwise plain Lanczos runs on S itself: no deflation, nothing carried over from earlier calls; the start
         vector is a hashed random combination of the columns of Y plus 5 % hashed noise (span(Y), the near-kernel of S
         at a near-stationary point, is where a lambda_min the deflated estimate missed would live).
-    Returns (lambda_min, its eigenvector as an n x 1 array, lambda_max, converged)."""
+    Returns (lambda_min, its eigenvector as an n x 1 array, lambda_max, converged).  With ``options["escape_stats"]`` the steps
+    of these runs are added to ``data["eig_verify_steps"]`` (see _device_escape)."""
     t1 = time.time()
     data["eig_verifications"] = data.get("eig_verifications", 0) + 1
     if 0 < dense_n <= int(o.get("verify_dense_max", 4000)):
@@ -180,11 +188,14 @@ def _verify_lambda_min(h, run1, o, data, default_tol, default_maxit, dense_n=0):
     # independent of everything the regular calls used; Lanczos path: span(Y) + 5 % noise (33 000 -> 22 000 steps on G81)
     h.set_option("escape_start_y", int(o.get("verify_start_in_span_y", 0 if h.escape_method() == 1 else 1)))
     try:
-        lam, vS, lam_max, _ = run1(float(o.get("eig_tol", default_tol)), int(o.get("eig_maxit", default_maxit)))
+        lam, vS, lam_max, steps = run1(float(o.get("eig_tol", default_tol)), int(o.get("eig_maxit", default_maxit)))
         _, conv, _ = h.escape_info()
         if not conv:                                      # once more with four times the step budget
-            lam, vS, lam_max, _ = run1(float(o.get("eig_tol", default_tol)), 4 * int(o.get("eig_maxit", default_maxit)))
+            lam, vS, lam_max, more = run1(float(o.get("eig_tol", default_tol)), 4 * int(o.get("eig_maxit", default_maxit)))
+            steps += more
             _, conv, _ = h.escape_info()
+        if o.get("escape_stats"):
+            data["eig_verify_steps"] = data.get("eig_verify_steps", 0) + int(steps)
     finally:
         h.set_option("escape_deflate", 1)
         h.set_option("escape_warm", 1)
@@ -541,6 +552,16 @@ def _block_factor_option(o, what):
     return mode
 
 
+def _block_escape_method_option(o, what):
+    """options["escape_method"] of the two block kinds: None (not given) or 0 / 1 / 2; anything else is a ValueError."""
+    if "escape_method" not in o:
+        return None
+    m = o["escape_method"]
+    if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or int(m) not in (0, 1, 2):
+        raise ValueError(f"options['escape_method'] must be 0, 1 or 2 for the {what} problem, not {m!r}")
+    return int(m)
+
+
 def _round_blocks_option(h, d, Y_eval, data):
     """options["round_blocks"]: data["R"] (and data["t"] of a pose-graph handle) from Handle.round_blocks at the evaluated
     point, which both settings of block_factor leave resident when their loop ends; the host functions of problems.py where
@@ -581,6 +602,11 @@ def ManiSDP_onlyunitblockdiag(C, d, options=None, verbose=True, rng=None):
     and the transfers only that path needs (host: get_point and the next set_point; device: the Gram matrix).
     ``options["round_blocks"] = True`` fills ``data["R"]`` (n, d, d) from Handle.round_blocks at the evaluated point before the
     handle closes (problems.round_rotations where the device reports degenerate blocks: ``data["round_fallback"]``).
+    ``options["escape_method"]`` selects the device escape (``eig = "device"``), the independent cold check included: 0 (default)
+    and 1 = single-vector Lanczos runs over the one-thread-per-block product; 2 = the Chebyshev-filtered block eigen-solver on
+    block storage where N = n d >= 256 and the factor is at most 112 columns wide (Lanczos otherwise), which returns whole eigenspaces where an eigenvalue of S is
+    multiple (d = 2: every one is double).  ``data["escape_method"]`` reports what the last escape call ran (1 = block); any
+    other value raises ValueError before a handle is created.
     ``line_search = 1``, ``device_factor``, ``round``, ``comm`` and ``precon`` raise ValueError before the library is loaded."""
     with _host_threads():
         return _onlyunitblockdiag_impl(C, d, options, verbose, rng)
@@ -629,6 +655,7 @@ def _onlyunitblockdiag_impl(C, d, options, verbose, rng):
     if o.get("device_factor"):
         raise ValueError("options['device_factor'] is not available for the unit-block-diagonal problem: the rank cut stays on the host")
     device = _block_factor_option(o, "unit-block-diagonal") == "device"
+    escape_method = _block_escape_method_option(o, "unit-block-diagonal")
     if C.shape[0] != C.shape[1] or C.shape[0] % d:
         raise ValueError(f"the cost matrix must be square of an order that is a multiple of d = {d}, not {C.shape}")
     dense_X_max = int(o.get("dense_X_max", 4000))
@@ -657,6 +684,8 @@ def _onlyunitblockdiag_impl(C, d, options, verbose, rng):
     def setup():
         if o.get("block_persist"):                         # the tCG of a TR iteration in one persistent launch where it applies
             h.set_option("block_persist", 1)
+        if escape_method is not None:                      # 0 auto and 1: Lanczos; 2: block eigen-solver on block storage (N >= 256)
+            h.set_option("escape_method", escape_method)
         _set_device_options(h, o)
 
     def evaluate(blocks):
@@ -721,6 +750,9 @@ def ManiSDP_posegraph(C, d, options=None, verbose=True, rng=None):
     ``options["block_factor"]`` and ``options["round_blocks"]`` as for ManiSDP_onlyunitblockdiag (the polar factors are those
     of the rotation rows; a rerun leaves the resident factor where it is; ``data["R"]`` and ``data["t"]``, from
     problems.round_poses on a fallback).
+    ``options["escape_method"]`` as for ManiSDP_onlyunitblockdiag (0 / 1 = Lanczos, the default; 2 = the block eigen-solver on
+    block storage where N = n (d + 1) >= 256; ``data["escape_method"]`` reports what ran; any other value raises ValueError
+    before a handle is created).
     ``line_search = 1``, ``device_factor``, ``round`` and ``comm`` raise ValueError before the library is loaded."""
     with _host_threads():
         return _posegraph_impl(C, d, options, verbose, rng)
@@ -744,6 +776,7 @@ def _posegraph_impl(C, d, options, verbose, rng):
     if o.get("device_factor"):
         raise ValueError("options['device_factor'] is not available for the pose-graph problem: the rank cut stays on the host")
     device = _block_factor_option(o, "pose-graph") == "device"
+    escape_method = _block_escape_method_option(o, "pose-graph")
     if C.shape[0] != C.shape[1] or C.shape[0] % B:
         raise ValueError(f"the cost matrix must be square of an order that is a multiple of d + 1 = {B}, not {C.shape}")
     dense_X_max = int(o.get("dense_X_max", 4000))
@@ -774,6 +807,8 @@ def _posegraph_impl(C, d, options, verbose, rng):
             h.set_option("block_persist", 1)
         if o.get("precon") == "blockjacobi":               # block-Jacobi preconditioned tCG (msdp_set_option "precon"); a refusal
             h.set_option("precon", 1)                      # (a diagonal block without a Cholesky factor) is the library's own error
+        if escape_method is not None:                      # 0 auto and 1: Lanczos; 2: block eigen-solver on block storage (N >= 256)
+            h.set_option("escape_method", escape_method)
         _set_device_options(h, o)
 
     def evaluate(blocks):

@@ -13,10 +13,11 @@ re-orthonormalisation of the factor on the device between the trustregions() cal
                re-orthonormalisation of the same factor, and the rounding: problems.round_rotations / round_poses against
                Handle.round_blocks() (wall clock, W from the device's Gram matrix included)
 Per solve setting: whole solve seconds, factor_seconds per outer iteration, outer iterations, device calls, host fallbacks,
-optimum.  No ratio is asserted: the figures are reported as they come out.
+optimum, and eig_seconds, the escape's steps and calls and the trustregions() seconds.  --escape-method 2: every solve runs the
+block eigen-solver of the escape on block storage (0: Lanczos).  No ratio is asserted: the figures are reported as they come out.
 Without --step this process opens no device: it runs every step as a child process of its own under `timeout`, one after the
 other, stops at the first step that fails or runs out of time, and prints one JSON line with what the steps returned.
-Usage: python tools/time_block_factor.py [--n N] [--small N] [--d D] [--degree K] [--sigma S] [--p P] [--runs K] [--step NAME]"""
+Usage: python tools/time_block_factor.py [--n N] [--small N] [--d D] [--degree K] [--sigma S] [--p P] [--runs K] [--step NAME] [--escape-method {0,2}]"""
 import argparse
 import json
 import os
@@ -53,7 +54,8 @@ def _solves(solve, C, d, base, runs):
         out[mode] = {"solve_seconds": _med(ts[mode]), "all_solve_seconds": [float(t) for t in ts[mode]],
                      "factor_seconds_per_iter": float(data["factor_seconds"]) / max(int(data["iters"]), 1),
                      "factor_seconds": float(data["factor_seconds"]), "rtr_seconds": float(data["rtr_seconds"]),
-                     "eig_seconds": float(data["eig_seconds"]), "iters": int(data["iters"]), "reruns": int(data.get("reruns", 0)),
+                     "eig_seconds": float(data["eig_seconds"]), "eig_calls": int(data.get("eig_calls", 0)), "eig_steps": int(data.get("eig_steps", 0)),
+                     "eig_verify_steps": int(data.get("eig_verify_steps", 0)), "escape_method_ran": int(data.get("escape_method", -1)), "iters": int(data["iters"]), "reruns": int(data.get("reruns", 0)),
                      "device_calls": int(data["factor_device_calls"]), "host_fallbacks": int(data["factor_host_fallbacks"]),
                      "obj": float(obj), "dinf": float(data["dinf"]), "status": int(data["status"]), "p_final": int(Y.shape[1])}
     return out
@@ -65,7 +67,7 @@ def _pose(a, n):
     out = {"n": n, "N": int(C.shape[0]), "runs": a.runs}
     for name, base in (("default", {}), ("persist", {"block_persist": True}), ("precon", {"precon": "blockjacobi"}),
                        ("precon_persist", {"precon": "blockjacobi", "block_persist": True})):
-        out[name] = _solves(solvers.ManiSDP_posegraph, C, a.d, dict(base, tol=1e-8), a.runs)
+        out[name] = _solves(solvers.ManiSDP_posegraph, C, a.d, dict(base, tol=1e-8, escape_method=a.escape_method, escape_stats=True), a.runs)
     return out
 
 
@@ -74,12 +76,12 @@ def _rot(a, n):
     out = {"n": n, "runs": a.runs}
     for noise in NOISES:                                     # raised until the staircase fires from p0 = d
         C = problems.rotation_synchronization(n, a.d, a.degree, noise, 0)[0]
-        _, _, data = solvers.ManiSDP_onlyunitblockdiag(C, a.d, {"tol": 1e-8, "p0": a.d, "block_factor": "device"}, verbose=False)
+        _, _, data = solvers.ManiSDP_onlyunitblockdiag(C, a.d, {"tol": 1e-8, "p0": a.d, "block_factor": "device", "escape_method": a.escape_method, "escape_stats": True}, verbose=False)
         if data["iters"] >= 2 and data["status"] == 0:
             break
     out.update(noise=noise, N=int(C.shape[0]))
     for name, base in (("default", {}), ("persist", {"block_persist": True})):
-        out[name] = _solves(solvers.ManiSDP_onlyunitblockdiag, C, a.d, dict(base, tol=1e-8, p0=a.d), a.runs)
+        out[name] = _solves(solvers.ManiSDP_onlyunitblockdiag, C, a.d, dict(base, tol=1e-8, p0=a.d, escape_method=a.escape_method, escape_stats=True), a.runs)
     return out
 
 
@@ -159,6 +161,7 @@ def main():
     ap.add_argument("--p", type=int, default=8)
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--step", default=None)
+    ap.add_argument("--escape-method", type=int, choices=(0, 2), default=0)
     a = ap.parse_args()
     if a.step:
         print(json.dumps(run_step(a)), flush=True)

@@ -8,8 +8,10 @@ off-diagonal entries of the diagonal blocks, on problems.rotation_synchronizatio
   (b) with --solve: the whole solve of both (solvers.ManiSDP_onlyunitblockdiag / ManiSDP_unitdiag with their defaults, wall
       clock, alternating, median of --runs after one warm-up solve each).
 The affine handle holds dense order-N operands (N = n d): 8 N^2 bytes each, 7.2 GB at the default size.  --no-affine leaves
-it out (the new handle alone).  One JSON line.
-Usage: python tools/time_blockdiag.py [--n N] [--d D] [--p P] [--reps R] [--rounds K] [--solve] [--runs K] [--no-affine]"""
+it out (the new handle alone).  --escape-method 2: the solves of the block handle run the block eigen-solver of the escape on
+block storage (0: Lanczos); the solve row carries eig_seconds, the escape's steps and calls and the trustregions() seconds beside
+the total.  One JSON line.
+Usage: python tools/time_blockdiag.py [--n N] [--d D] [--p P] [--reps R] [--rounds K] [--solve] [--runs K] [--no-affine] [--escape-method {0,2}]"""
 import argparse
 import json
 import os
@@ -49,6 +51,7 @@ def main():
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--solve", action="store_true")
     ap.add_argument("--no-affine", action="store_true")
+    ap.add_argument("--escape-method", type=int, choices=(0, 2), default=0)
     a = ap.parse_args()
     from manisdp_matlab_amd import _lib, problems, solvers
     _lib.load()
@@ -89,7 +92,7 @@ def main():
             h.close()
     if a.solve:
         def solve_block():
-            Ys, obj, data = solvers.ManiSDP_onlyunitblockdiag(C, d, {"tol": 1e-8}, verbose=False)
+            Ys, obj, data = solvers.ManiSDP_onlyunitblockdiag(C, d, {"tol": 1e-8, "escape_method": a.escape_method, "escape_stats": True}, verbose=False)
             return obj, data, Ys
 
         def solve_affine():
@@ -111,7 +114,10 @@ def main():
             obj, data, Ys = last[k]
             out["solve_" + k] = {"seconds": float(np.median(ts[k])), "all_seconds": [float(t) for t in ts[k]], "obj": float(obj),
                                  "dinf": float(data["dinf"]), "status": int(data["status"]), "p": int(Ys.shape[1]),
-                                 "iters": int(data["iters"]), "hessvecs": int(data["hessvecs"])}
+                                 "iters": int(data["iters"]), "hessvecs": int(data["hessvecs"]),
+                                 "rtr_seconds": float(data["rtr_seconds"]), "eig_seconds": float(data["eig_seconds"]),
+                                 "eig_calls": int(data.get("eig_calls", 0)), "eig_steps": int(data.get("eig_steps", 0)),
+                                 "eig_verify_steps": int(data.get("eig_verify_steps", 0)), "escape_method_ran": int(data.get("escape_method", -1))}
         Rr = problems.round_rotations(last["block"][2], d)
         out["solve_block"]["rotation_error"] = problems.rotation_error(Rr, R_true)
         if "affine" in solves:

@@ -12,7 +12,9 @@ The affine handle holds dense order-N operands, which is why it is timed at n = 
 route is the yardstick, not the code under test.
 Without --step this process opens no device: it runs every step as a child process of its own under `timeout`, one after the
 other, stops at the first step that fails or runs out of time, and prints one JSON line with what the steps returned.
-Usage: python tools/time_posegraph.py [--n N] [--small N] [--d D] [--p P] [--reps R] [--rounds K] [--runs K] [--step NAME]"""
+--escape-method 2: the solves of the pose handle run the block eigen-solver of the escape on block storage (0: Lanczos); a solve
+row carries eig_seconds, the escape's steps and calls and the trustregions() seconds beside the total.
+Usage: python tools/time_posegraph.py [--n N] [--small N] [--d D] [--p P] [--reps R] [--rounds K] [--runs K] [--step NAME] [--escape-method {0,2}]"""
 import argparse
 import json
 import os
@@ -93,7 +95,7 @@ def _solve(a, n, with_affine):
     N = C.shape[0]
 
     def solve_pose():
-        return solvers.ManiSDP_posegraph(C, d, {"tol": 1e-8}, verbose=False)
+        return solvers.ManiSDP_posegraph(C, d, {"tol": 1e-8, "escape_method": a.escape_method, "escape_stats": True}, verbose=False)
 
     solves = {"pose": solve_pose}
     if with_affine:
@@ -112,7 +114,10 @@ def _solve(a, n, with_affine):
         Ys, obj, data = last[k]
         out[k] = {"seconds": float(np.median(ts[k])), "all_seconds": [float(t) for t in ts[k]], "obj": float(obj),
                   "dinf": float(data.get("dinf", float("nan"))), "status": int(data.get("status", -1)),
-                  "iters": int(data.get("iters", 0)), "hessvecs": int(data.get("hessvecs", 0))}
+                  "iters": int(data.get("iters", 0)), "hessvecs": int(data.get("hessvecs", 0)),
+                  "rtr_seconds": float(data.get("rtr_seconds", 0.0)), "eig_seconds": float(data.get("eig_seconds", 0.0)),
+                  "eig_calls": int(data.get("eig_calls", 0)), "eig_steps": int(data.get("eig_steps", 0)),
+                  "eig_verify_steps": int(data.get("eig_verify_steps", 0)), "escape_method_ran": int(data.get("escape_method", -1))}
     Ys, obj, data = last["pose"]
     er, et = problems.pose_error(*problems.round_poses(Ys, d), R_true, t_true)
     out["pose"].update(gap=float(data["gap"]), p=int(Ys.shape[1]), rotation_error=er, position_error=et)
@@ -145,6 +150,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--step", default=None)
+    ap.add_argument("--escape-method", type=int, choices=(0, 2), default=0)
     a = ap.parse_args()
     if a.step:
         print(json.dumps(run_step(a)), flush=True)
